@@ -3,7 +3,7 @@
 1M-pose Manhattan graph (BASELINE.json: "GN iterations/sec + edges/sec (residual+Jac) on 1M-pose
 graph, 1/2/4/8 GPU").
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -13,12 +13,22 @@ rtol 0.1, <= 500 iterations), model decrease, candidate cost (fused edge kernel,
 reject, and on acceptance re-linearisation (fused residual+Jacobian kernel + assembly).  The graph is
 sharded by pose-id range over the ranks (strong scaling: the problem is fixed, 1M poses).
 
-Timing: W untimed LM iterations, then exactly K timed ones between barriers; that pass is repeated
-`--passes` times from the initial poses (same trajectory every time) and the MEDIAN pass is reported
-(`passes_ms_per_step` lists all of them).
+Timing: W untimed LM iterations, then exactly K timed ones between barriers; that pass is run `--passes`
+times from the initial poses (same trajectory every time; default 1, 5 with --full) and the MEDIAN pass is
+reported (`passes_ms_per_step` lists all of them).
 
-Prints ONE JSON line on rank 0:
-  roofline      the dominant kernel (block-CSR SpMV): algorithmic bytes / HIP-event launch time
+A plain run does only that: set up, warm up, time, print ONE JSON line on rank 0 (metric, value, unit,
+higher_is_better, dtype, ms_per_step = milliseconds per timed LM iteration, and what the solver did in them).
+
+--dump-outputs DIR  after the timed passes, rank 0 writes what the timed path computed, as float64 .npy files:
+                    poses.npy (the poses after the last timed LM iteration, [n_poses, 3]; above 64 MB a fixed
+                    seeded sample of rows, listed in pose_rows.npy) and iter_costs.npy (the cost each timed LM
+                    iteration of the last pass recorded).  The inputs are seeded: the same arguments give the same inputs.
+
+--full adds to the line what takes runs of its own:
+  edges_per_sec, kernels, roofline
+                the fused edge kernel, assembly, SpMV and preconditioner back to back (HIP events, --kernel-reps);
+                the dominant kernel (block-CSR SpMV): algorithmic bytes / HIP-event launch time
   parity        GPU vs the CPU port of the same algorithm on the first `--cpu-iters` LM iterations of THIS
                 workload (costs, accept/reject history, PCG counts, final translations)
   workloads     GN it/s of the other workloads north_star names: INTEL + 50 outliers (exact mode) and the
@@ -87,6 +97,24 @@ def cpu_quota():
         return None
 
 
+DUMP_BYTES = 64 << 20   # at most this much under --dump-outputs
+
+
+def dump_outputs(path, poses, costs):
+    """DIR/poses.npy + DIR/iter_costs.npy (float64); the poses as a fixed seeded sample of rows if they exceed the cap"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    poses, costs = np.ascontiguousarray(poses, np.float64), np.asarray(costs, np.float64)
+    cap = DUMP_BYTES - costs.nbytes - 3 * 4096   # (4096: room for each file's .npy header)
+    if poses.nbytes > cap:
+        n = cap // (poses.itemsize * (poses.shape[1] + 1))   # room for the sampled rows and their row numbers
+        rows = np.sort(np.random.default_rng(20260410).choice(len(poses), size=n, replace=False))
+        poses = poses[rows]
+        np.save(os.path.join(path, "pose_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, "poses.npy"), poses)
+    np.save(os.path.join(path, "iter_costs.npy"), costs)
+
+
 def main():
     # thread placement of the CPU-baseline legs (read by the OpenMP runtime when it starts)
     os.environ.setdefault("OMP_PLACES", "cores")
@@ -95,7 +123,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--passes", type=int, default=5, help="timed passes of W + K LM iterations from the initial poses; the median is reported")
+    ap.add_argument("--passes", type=int, default=None,
+                    help="timed passes of W + K LM iterations from the initial poses; the median is reported (default 1, 5 with --full)")
     ap.add_argument("--poses", type=int, default=1_000_000)
     ap.add_argument("--pcg-rtol", type=float, default=0.1)
     ap.add_argument("--pcg-max-iters", type=int, default=500)
@@ -126,7 +155,13 @@ def main():
                     help="A/B switch: 'one-reduction' runs the several-rank PCG loop (Chronopoulos-Gear) on one rank too (test hook single_reduction = 1)")
     ap.add_argument("--comm", choices=["rccl", "shm"], default="rccl",
                     help="shm = rehearsal on ONE GPU: gloo process group + host-staged shared-memory communicator, all ranks on cuda:0")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the poses after the last timed LM iteration and the costs of the timed iterations to DIR/*.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the kernel-level / roofline figures, the parity check, the CPU baseline and the other workloads")
     args = ap.parse_args()
+    if args.passes is None:
+        args.passes = 5 if args.full else 1
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -259,21 +294,21 @@ def main():
     order = sorted(range(len(passes)), key=lambda i: passes[i][0])
     dt, timed, recs, summ, restarts = passes[order[len(order) // 2]]   # the median pass
 
-    # kernel-level numbers, measured live with HIP events on the solver's stream
-    reps = args.kernel_reps
-    k1 = s.bench_eval(reps, True)
-    k1c = s.bench_eval(reps, False)
-    k2 = s.bench_assemble(reps)
-    k3 = s.bench_spmv(reps)
-    pc = s.bench_precond(reps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, s.poses(), [r["cost"] for r in passes[-1][1]])
+
+    # kernel-level numbers (--full), measured live with HIP events on the solver's stream
+    kst = []
+    if args.full:
+        reps = args.kernel_reps
+        kst = [s.bench_eval(reps, True), s.bench_eval(reps, False), s.bench_assemble(reps), s.bench_spmv(reps), s.bench_precond(reps)]
     all_dt = [p[0] for p in passes]
-    vals = torch.tensor([dt, k1.ms_avg, k1c.ms_avg, k2.ms_avg, k3.ms_avg, pc.ms_avg] + all_dt, dtype=torch.float64,
-                        device="cpu" if rehearsal else "cuda")
+    vals = torch.tensor([dt] + [k.ms_avg for k in kst] + all_dt, dtype=torch.float64, device="cpu" if rehearsal else "cuda")
     if dist is not None:
         dist.all_reduce(vals, op=dist.ReduceOp.MAX)
     vals = [float(v) for v in vals.cpu()]
-    dt_max, k1_ms, k1c_ms, k2_ms, k3_ms, pc_ms = vals[:6]
-    all_dt = vals[6:]
+    dt_max, kms = vals[0], vals[1:1 + len(kst)]
+    all_dt = vals[1 + len(kst):]
     if dist is not None:  # the median of the per-pass maxima over the ranks
         dt_max = statistics.median_low(all_dt)
 
@@ -306,30 +341,10 @@ def main():
                 "seed": 20260410,
             },
             "passes_ms_per_step": [1e3 * d / K for d in all_dt],
-            "edges_per_sec": n_edges / (k1_ms * 1e-3),
             "pcg_iters_per_step": sum(r["pcg_iters"] for r in timed) / K,
             "accepted_steps": sum(1 for r in timed if r["step_ok"] == 1),
             "cost_first_last": [recs[0]["cost"], summ.final_cost],
             "restarts": restarts,
-            "roofline": {
-                "kernel": "k_spmv (block-CSR 3x3 SpMV, fp64)",
-                "bound": "hbm",
-                "achieved": gbs(k3, k3_ms),
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": gbs(k3, k3_ms) / HBM_PEAK_GBS,
-                "traffic": None,
-                "ms": k3_ms,
-                "algorithmic_bytes": k3.algorithmic_bytes,
-            },
-            "kernels": {
-                "k_edge_eval<jac>": {"ms": k1_ms, "GB/s": gbs(k1, k1_ms), "frac": gbs(k1, k1_ms) / HBM_PEAK_GBS,
-                                     "edges_per_s": k1.units / (k1_ms * 1e-3)},
-                "k_edge_eval<cost>": {"ms": k1c_ms, "GB/s": gbs(k1c, k1c_ms), "frac": gbs(k1c, k1c_ms) / HBM_PEAK_GBS},
-                "k_assemble": {"ms": k2_ms, "GB/s": gbs(k2, k2_ms), "frac": gbs(k2, k2_ms) / HBM_PEAK_GBS},
-                "k_spmv": {"ms": k3_ms, "GB/s": gbs(k3, k3_ms), "frac": gbs(k3, k3_ms) / HBM_PEAK_GBS},
-                "preconditioner apply (PCG start-up kernel, back to back)": {"ms": pc_ms, "GB/s": gbs(pc, pc_ms), "frac": gbs(pc, pc_ms) / HBM_PEAK_GBS},
-            },
             "seconds": {"generate": t_gen, "create": t_create, "eval": summ.seconds_eval,
                         "assemble": summ.seconds_assemble, "linear": summ.seconds_linear,
                         "candidate": summ.seconds_candidate},
@@ -339,10 +354,33 @@ def main():
                                                                            "host_enqueue_us_per_pcg_iter", "pcg_graph_replay", "pcg_single_reduction", "pcg_coarse_poses",
                                                                            "linear_solver")},
         }
+        if args.full:
+            k1, k1c, k2, k3, pc = kst
+            k1_ms, k1c_ms, k2_ms, k3_ms, pc_ms = kms
+            out["edges_per_sec"] = n_edges / (k1_ms * 1e-3)
+            out["roofline"] = {
+                "kernel": "k_spmv (block-CSR 3x3 SpMV, fp64)",
+                "bound": "hbm",
+                "achieved": gbs(k3, k3_ms),
+                "peak": HBM_PEAK_GBS,
+                "unit": "GB/s",
+                "frac": gbs(k3, k3_ms) / HBM_PEAK_GBS,
+                "traffic": None,
+                "ms": k3_ms,
+                "algorithmic_bytes": k3.algorithmic_bytes,
+            }
+            out["kernels"] = {
+                "k_edge_eval<jac>": {"ms": k1_ms, "GB/s": gbs(k1, k1_ms), "frac": gbs(k1, k1_ms) / HBM_PEAK_GBS,
+                                     "edges_per_s": k1.units / (k1_ms * 1e-3)},
+                "k_edge_eval<cost>": {"ms": k1c_ms, "GB/s": gbs(k1c, k1c_ms), "frac": gbs(k1c, k1c_ms) / HBM_PEAK_GBS},
+                "k_assemble": {"ms": k2_ms, "GB/s": gbs(k2, k2_ms), "frac": gbs(k2, k2_ms) / HBM_PEAK_GBS},
+                "k_spmv": {"ms": k3_ms, "GB/s": gbs(k3, k3_ms), "frac": gbs(k3, k3_ms) / HBM_PEAK_GBS},
+                "preconditioner apply (PCG start-up kernel, back to back)": {"ms": pc_ms, "GB/s": gbs(pc, pc_ms), "frac": gbs(pc, pc_ms) / HBM_PEAK_GBS},
+            }
         # HBM bytes per launch of k_spmv from the committed rocprofv3 --pmc passes -- only if they were taken on THESE
         # kernel sources (the file records a digest of them); otherwise null rather than a stale figure
         pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if world == 1 and args.poses == 1000000 and os.path.exists(pmc):
+        if args.full and world == 1 and args.poses == 1000000 and os.path.exists(pmc):
             try:
                 tr = json.load(open(pmc))
                 if tr.get("kernels_digest") == kernels_digest():
@@ -356,7 +394,7 @@ def main():
 
         # ---- the CPU port on the same trajectory: parity of the bench workload + the CPU baseline
         cpu_iters = min(args.cpu_iters, W + K)
-        if world == 1 and cpu_iters > 0:
+        if args.full and world == 1 and cpu_iters > 0:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import oracle as O
             og = O.Graph(np.array(g.pose_ids), np.array(g.poses), np.array(g.ia), np.array(g.ib), np.array(g.meas),
@@ -490,7 +528,7 @@ def main():
                     out["cpu_baseline"]["intel_plus_50_direct_solve"] = {"error": repr(e)}
 
         # ---- the other workloads north_star names (N = 1): whole 50-iteration solves, GN it/s = iterations / solve seconds
-        if world == 1 and args.workloads:
+        if args.full and world == 1 and args.workloads:
             wl = {}
             data = os.path.join(ROOT, "tests", "golden", "data")
             golden = os.path.join(ROOT, "tests", "golden")

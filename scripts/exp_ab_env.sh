@@ -7,7 +7,7 @@ O=gpurun_out/ab_$NAME; mkdir -p $O
 for rep in 1 2; do
 for v in "$@"; do
 if [ "$v" = "-" ]; then unset $NAME; else export $NAME=$v; fi
-PGO_LIB=$PWD/toy-robust-backend-slam_amd/libpgo_exp.so timeout -k 10 300 python bench.py --poses $POSES --steps 20 --warmup 5 --passes 1 --workloads 0 --cpu-iters 0 --cpu-iters-1t 0 > $O/$POSES.$v.$rep.json 2> $O/$POSES.$v.$rep.err || { tail -5 $O/$POSES.$v.$rep.err; exit 1; }
+PGO_LIB=$PWD/toy-robust-backend-slam_amd/libpgo_exp.so timeout -k 10 300 python bench.py --poses $POSES --steps 20 --warmup 5 --passes 1 --workloads 0 --cpu-iters 0 --cpu-iters-1t 0 --full > $O/$POSES.$v.$rep.json 2> $O/$POSES.$v.$rep.err || { tail -5 $O/$POSES.$v.$rep.err; exit 1; }
 python - <<PY
 import json
 d = json.load(open("$O/$POSES.$v.$rep.json"))

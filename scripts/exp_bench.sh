@@ -6,7 +6,7 @@ O=gpurun_out/r03
 mkdir -p $O
 echo "nproc $(nproc)  cpu.max $(cat /sys/fs/cgroup/cpu.max 2>/dev/null)  cpuset $(cat /sys/fs/cgroup/cpuset.cpus.effective 2>/dev/null | cut -c1-60)"
 lscpu | grep -E "Model name|Socket|Core|Thread|NUMA node\(s\)" | head -6
-timeout -k 10 600 python bench.py --poses 100000 --steps 5 --warmup 2 --passes 1 > $O/bench_small.json 2> $O/bench_small.err || { tail -20 $O/bench_small.err; exit 1; }
+timeout -k 10 600 python bench.py --poses 100000 --steps 5 --warmup 2 --passes 1 --full > $O/bench_small.json 2> $O/bench_small.err || { tail -20 $O/bench_small.err; exit 1; }
 python - <<PY
 import json
 d = json.load(open("$O/bench_small.json"))
@@ -14,7 +14,7 @@ print("100k: GN it/s %.1f" % d["value"], json.dumps(d["cpu_baseline"], indent=No
 print(json.dumps(d["workloads"].get("time_to_cost"))[:1500])
 PY
 T0=$(date +%s)
-timeout -k 10 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_full.json 2> $O/bench_full.err || { tail -20 $O/bench_full.err; exit 1; }
+timeout -k 10 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_full.json 2> $O/bench_full.err || { tail -20 $O/bench_full.err; exit 1; }
 echo "full bench wall $(( $(date +%s) - T0 )) s"
 python - <<PY
 import json

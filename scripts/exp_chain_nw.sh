@@ -2,7 +2,7 @@ set -o pipefail
 export TMPDIR=/tmp
 O=gpurun_out/chain_nw; mkdir -p $O
 run() { # label
-PGO_LIB=$PWD/toy-robust-backend-slam_amd/libpgo_exp.so timeout -k 10 300 python bench.py --steps 20 --warmup 5 --passes 1 --workloads 0 --cpu-iters 0 --cpu-iters-1t 0 > $O/$1.json 2> $O/$1.err || { tail -5 $O/$1.err; exit 1; }
+PGO_LIB=$PWD/toy-robust-backend-slam_amd/libpgo_exp.so timeout -k 10 300 python bench.py --steps 20 --warmup 5 --passes 1 --workloads 0 --cpu-iters 0 --cpu-iters-1t 0 --full > $O/$1.json 2> $O/$1.err || { tail -5 $O/$1.err; exit 1; }
 python - <<PY
 import json
 d = json.load(open("$O/$1.json"))

@@ -10,7 +10,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   tail -3 $O/tests.log
 fi
 for rep in 1 2; do for po in 0 1; do
-  timeout -k 10 300 python bench.py --steps 20 --warmup 5 --passes 3 --workloads 0 --cpu-iters 0 --pose-ordering $po > $O/order_${po}_${rep}.json 2> $O/order_${po}_${rep}.err || { tail -5 $O/order_${po}_${rep}.err; exit 1; }
+  timeout -k 10 300 python bench.py --steps 20 --warmup 5 --passes 3 --workloads 0 --cpu-iters 0 --pose-ordering $po --full > $O/order_${po}_${rep}.json 2> $O/order_${po}_${rep}.err || { tail -5 $O/order_${po}_${rep}.err; exit 1; }
   python - <<PY
 import json
 d = json.load(open("$O/order_${po}_${rep}.json"))

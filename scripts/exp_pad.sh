@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 O=gpurun_out/pad; mkdir -p $O
 for rep in 1 2 3 4 5 6; do
 for lay in auto dense; do
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --passes 1 --workloads 0 --cpu-iters 0 --cpu-iters-1t 0 --layout $lay > $O/$lay.$rep.json 2> $O/$lay.$rep.err || { tail -5 $O/$lay.$rep.err; exit 1; }
+timeout -k 10 300 python bench.py --steps 20 --warmup 5 --passes 1 --workloads 0 --cpu-iters 0 --cpu-iters-1t 0 --layout $lay --full > $O/$lay.$rep.json 2> $O/$lay.$rep.err || { tail -5 $O/$lay.$rep.err; exit 1; }
 python - <<PY
 import json
 d = json.load(open("$O/$lay.$rep.json"))

@@ -61,7 +61,7 @@ def main():
         f = [v for v in d if v > 0.5 * p90]
         return sum(f) / len(f), len(f)
 
-    lines = ["# rocprofv3 --kernel-trace --stats, bench.py --steps 3 --warmup 1 --passes 1 --workloads 0 (1M poses, 1 GPU)", "",
+    lines = ["# rocprofv3 --kernel-trace --stats, bench.py --steps 3 --warmup 1 --passes 1 --workloads 0 --full (1M poses, 1 GPU)", "",
              "| kernel | calls | total ms | avg us | % | full launches | full avg us |", "|---|---|---|---|---|---|---|"]
     with open(os.path.join(prof, f"{tag}_kernel_stats.csv"), "w", newline="") as fh:
         if stats:

@@ -19,16 +19,18 @@
 
 int main(int argc, char** argv) {
   const char* data_dir = argc > 1 ? argv[1] : ".";
+  const std::string out_dir = argc > 2 ? argv[2] : ".";   // where the writers' files go (the test's own temporary directory)
+  const std::string nodes = out_dir + "/pgo_san_nodes.txt", edges = out_dir + "/pgo_san_edges.txt", g2o = out_dir + "/pgo_san.g2o";
   pgo_graph* g = nullptr;
   CHECK(pgo_g2o_load((std::string(data_dir) + "/INTEL.g2o").c_str(), &g) == PGO_OK);
   CHECK(pgo_graph_num_poses(g) == 1228 && pgo_graph_num_edges(g) == 1483);
   CHECK(pgo_inject_outliers(g, 50, 1) == PGO_OK);
   CHECK(pgo_graph_num_edges_of_kind(g, PGO_EDGE_BOGUS) == 50);
-  CHECK(pgo_write_nodes(g, "/tmp/pgo_san_nodes.txt", 0) == PGO_OK);
-  CHECK(pgo_write_edges(g, "/tmp/pgo_san_edges.txt") == PGO_OK);
-  CHECK(pgo_write_g2o(g, "/tmp/pgo_san.g2o") == PGO_OK);
+  CHECK(pgo_write_nodes(g, nodes.c_str(), 0) == PGO_OK);
+  CHECK(pgo_write_edges(g, edges.c_str()) == PGO_OK);
+  CHECK(pgo_write_g2o(g, g2o.c_str()) == PGO_OK);
   pgo_graph* back = nullptr;
-  CHECK(pgo_g2o_load("/tmp/pgo_san.g2o", &back) == PGO_OK);
+  CHECK(pgo_g2o_load(g2o.c_str(), &back) == PGO_OK);
   CHECK(pgo_graph_num_edges(back) == pgo_graph_num_edges(g));
   pgo_graph_free(back);
   // malformed inputs

@@ -16,6 +16,6 @@ def test_host_code_under_asan_ubsan(tmp_path):
            os.path.join(ROOT, "tests", "native", "host_sanitize_main.cpp"), "-o", exe]
     subprocess.check_call(cmd)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    p = subprocess.run([exe, DATA], capture_output=True, text=True, timeout=600, env=env)
+    p = subprocess.run([exe, DATA, str(tmp_path)], capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, p.stdout + p.stderr
     assert "host sanitizer run ok" in p.stdout
