@@ -200,8 +200,8 @@ typedef struct pgo_options {
                                   rotation about the centre) of aggregates of this many consecutive poses -- three unknowns per
                                   aggregate, Galerkin matrix P'(J'J + D'D)P factorised densely per LM iteration (order <= 6143).
                                   It removes the smooth long-range error that block-Jacobi cannot: M3500 METHOD 1, PCG to 1e-10:
-                                  1557 -> 178 iterations with 16-pose aggregates.  Rounded up to a multiple of the one-level
-                                  block (pcg_chain_len / pcg_block_poses).  One rank.  0 = off;
+                                  1557 -> 178 iterations with 16-pose aggregates.  Taken as given (not rounded to the one-level
+                                  block: an aggregate may straddle two groups or segments).  One rank.  0 = off;
                                   -1 (default) = auto, for graphs of >= 512 poses that stay on PCG while pcg_block_poses and
                                   pcg_chain_len are left at auto: on for tight solves
                                   (pcg_rtol <= 1e-3) -- 16 poses per aggregate up to 8192 poses, else 64, doubled until the
@@ -363,7 +363,8 @@ typedef struct pgo_handle_info {
   int32_t pcg_coarse_rank;           /* order of its dense coarse matrix                                               */
   int32_t pcg_single_reduction;      /* 1 = the PCG loop with ONE reduction point per iteration (Chronopoulos-Gear recurrences:
                                         world > 1, pcg_rtol >= 1e-6, chain preconditioner), 0 = the textbook two-reduction loop */
-  int32_t _pad;
+  int32_t pcg_coarse_off_iters;      /* LM iterations whose PCG solve ran WITHOUT the second level because its factorisation was
+                                        not usable (a pivot lost to rounding); 0 on a healthy solve                          */
 } pgo_handle_info;
 int pgo_get_info(const pgo_t* h, pgo_handle_info* out);                           /* [host] */
 
@@ -385,11 +386,17 @@ typedef struct pgo_kernel_stats {
 int pgo_bench_eval(pgo_t* h, int reps, int with_jacobian, pgo_kernel_stats* out); /* [gpu] K1 */
 int pgo_bench_assemble(pgo_t* h, int reps, pgo_kernel_stats* out);                /* [gpu] K2 */
 int pgo_bench_spmv(pgo_t* h, int reps, pgo_kernel_stats* out);                    /* [gpu] K3 */
-int pgo_debug_precond(pgo_t* h, const double* r_3n, double* z_3n);               /* [gpu] z = M^-1 r, current preconditioner */
+/* z = M^-1 r with the preconditioner the next LM iteration applies: current linearisation, current radius (both entry
+ * points first set up the LM diagonal and the preconditioner, as an LM iteration does; the solve itself is not affected).
+ * Needs at least one LM iteration.  r, z: 3N doubles, caller's pose order (world == 1).                               */
+int pgo_debug_precond(pgo_t* h, const double* r_3n, double* z_3n);               /* [gpu] */
 int pgo_bench_precond(pgo_t* h, int reps, pgo_kernel_stats* out);                 /* [gpu] z = M^-1 b as the PCG start-up kernel */
-/* y = (J'J + D'D) x in the scaled space at the current linearisation, with the
- * current LM diagonal; x,y: 3N doubles (world == 1).  For SpMV parity tests.    */
+/* y = (J'J) x in the scaled space at the current linearisation, WITHOUT the LM diagonal; x,y: 3N doubles (world == 1).
+ * For SpMV parity tests.                                                                                              */
 int pgo_debug_spmv(pgo_t* h, const double* x, double* y);                         /* [gpu] */
+/* y = (J'J + D'D) x through the product kernel the PCG loop runs, after the same set-up as pgo_debug_precond (LM diagonal
+ * for the current radius); optionally d2 = the diagonal of D'D (3N).  x, y, d2: caller's pose order (world == 1).     */
+int pgo_debug_system_spmv(pgo_t* h, const double* x, double* y, double* d2_or_null);   /* [gpu] */
 /* normal-equation pieces at the current point, caller's pose order (world == 1):
  * g: 3N gradient J'r (unscaled), hdiag: N x 9 diagonal 3x3 blocks of J'J         */
 int pgo_debug_normal_eq(pgo_t* h, double* g_or_null, double* hdiag_or_null);      /* [gpu] */

@@ -177,6 +177,17 @@ __global__ void k_coarse_pad(double* __restrict__ cap, double* __restrict__ dwor
   dwork[(int64_t)(p >> 5) * 1024 + (p & 31) * 32 + (p & 31)] = 1.0;
 }
 
+// the same on the three unknowns of every listed aggregate: one without a pose in the coarse space (only edge-less poses and
+// the constant pose) has P = 0 and an all-zero block (I, I); its unknowns are decoupled (r_c = 0 there, so e_c = 0)
+template <int PGO_UNIT_ = 0>   // (a template so that only the translation units that launch it carry it)
+__global__ void k_coarse_dead(double* __restrict__ cap, double* __restrict__ dwork, const int32_t* __restrict__ dead, int n_dead, int Kp) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= 3 * n_dead) return;
+  const int p = 3 * dead[k / 3] + k % 3;
+  cap[(int64_t)p * Kp + p] = 1.0;
+  dwork[(int64_t)(p >> 5) * 1024 + (p & 31) * 32 + (p & 31)] = 1.0;
+}
+
 // r_c = P' r: one wavefront per aggregate, fixed order
 template <int PGO_UNIT_ = 0>   // (a template so that only the translation units that launch it carry it)
 __global__ __launch_bounds__(256) void k_coarse_restrict(int n_loc, int agg, int n_agg, const double* __restrict__ pb,

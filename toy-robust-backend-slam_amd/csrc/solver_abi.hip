@@ -367,6 +367,7 @@ int pgo_get_info(const pgo_t* h, pgo_handle_info* out) {
   out->pcg_single_reduction = h->use_sr ? 1 : 0;
   out->pcg_coarse_poses = h->use_coarse ? h->co_agg : 0;
   out->pcg_coarse_rank = h->use_coarse ? h->co_K : 0;
+  out->pcg_coarse_off_iters = h->co_off_iters;
   return PGO_OK;
 }
 
@@ -442,8 +443,49 @@ int pgo_debug_spmv(pgo_t* h, const double* x, double* yout) {
   return PGO_OK;
 }
 
-// z = M^-1 r with the preconditioner of the current LM iteration (whatever family the handle resolved to), through the
-// PCG start-up kernel: for the symmetry / positivity property tests.  Needs at least one LM iteration; world == 1.
+// The LM diagonal for the current radius and the preconditioner on the current linearisation, as the next LM iteration sets
+// them up (after an accepted step H is new and the factors are not; after a rejected one the radius changed).  Every buffer
+// written here is rewritten from H and the radius by the next iteration's prepare_system() before it is read: a solve is
+// not affected.
+static int prepare_for_debug(pgo_handle* h) {
+  PGOC(h->prepare_system());
+  if (h->direct) PGOC(h->prepare_preconditioner());   // (a handle on the direct solve does not factorise it per LM iteration)
+  return PGO_OK;
+}
+
+int pgo_debug_system_spmv(pgo_t* h, const double* x, double* yout, double* d2_out) {
+  if (!h || !x || !yout) return fail(PGO_ERR_INVALID_ARG, "pgo_debug_system_spmv: null");
+  if (h->comm && h->comm->world > 1) return fail(PGO_ERR_UNSUPPORTED, "world == 1 only");
+  if (!h->lin_valid) return fail(PGO_ERR_INVALID_ARG, "pgo_debug_system_spmv: call pgo_lm_begin first");
+  HIPC(hipSetDevice(h->device));
+  PGOC(prepare_for_debug(h));
+  const int64_t N = h->S.n_poses;
+  std::vector<double> tmp;
+  const double* src = x;
+  if (!h->perm.empty()) {
+    h->to_internal(x, &tmp, 3);
+    src = tmp.data();
+  }
+  HIPC(hipMemcpyAsync(h->ap, src, (size_t)3 * N * sizeof(double), hipMemcpyHostToDevice, h->stream));   // ap: scratch input
+  hipLaunchKernelGGL(dev::k_scatter_owned<>, dim3(h->g_flat), dim3(dev::WG), 0, h->stream, h->S.n_loc, h->S.lo, (const double*)h->ap, h->p_full);
+  PGOC(h->check_launch("k_scatter_owned"));
+  PGOC(h->spmv_enqueue(h->p_full, h->ap, h->part[0], 1, nullptr));
+  std::vector<double> ytmp((size_t)3 * N), dtmp(d2_out ? (size_t)3 * N : 0);
+  HIPC(hipMemcpyAsync(ytmp.data(), h->ap, ytmp.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (d2_out) HIPC(hipMemcpyAsync(dtmp.data(), h->d2, dtmp.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  PGOC(h->sync());
+  if (h->perm.empty()) {
+    memcpy(yout, ytmp.data(), ytmp.size() * sizeof(double));
+    if (d2_out) memcpy(d2_out, dtmp.data(), dtmp.size() * sizeof(double));
+  } else {
+    h->to_caller(ytmp, yout, 3);
+    if (d2_out) h->to_caller(dtmp, d2_out, 3);
+  }
+  return PGO_OK;
+}
+
+// z = M^-1 r with the preconditioner the next LM iteration applies (whatever family the handle resolved to), through the
+// PCG start-up kernel: for the restatement and property tests.  Needs at least one LM iteration; world == 1.
 int pgo_debug_precond(pgo_t* h, const double* r_in, double* z_out) {
   if (!h || !r_in || !z_out) return fail(PGO_ERR_INVALID_ARG, "pgo_debug_precond: null");
   if (h->comm && h->comm->world > 1) return fail(PGO_ERR_UNSUPPORTED, "world == 1 only");
@@ -457,7 +499,7 @@ int pgo_debug_precond(pgo_t* h, const double* r_in, double* z_out) {
     src = tmp.data();
   }
   HIPC(hipMemcpyAsync(h->ap, src, (size_t)3 * N * sizeof(double), hipMemcpyHostToDevice, h->stream));  // ap: scratch input
-  if (h->direct) PGOC(h->prepare_preconditioner());   // (a handle on the direct solve does not factorise it per LM iteration)
+  PGOC(prepare_for_debug(h));
   dev::CgVec V = h->cg_vec();
   if (h->chain_len) {
     h->launch_cg_init_chain(h->ap, h->part[0], h->part[1]);
@@ -576,7 +618,7 @@ int pgo_bench_precond(pgo_t* h, int reps, pgo_kernel_stats* out) {
   if (!h || !out || reps < 1) return fail(PGO_ERR_INVALID_ARG, "pgo_bench_precond: bad argument");
   if (!h->lin_valid || h->iter < 1) return fail(PGO_ERR_INVALID_ARG, "pgo_bench_precond: run at least one LM iteration first");
   HIPC(hipSetDevice(h->device));
-  if (h->direct) PGOC(h->prepare_preconditioner());   // (a handle on the direct solve does not factorise it per LM iteration)
+  PGOC(prepare_for_debug(h));
   dev::CgVec V = h->cg_vec();
   double ms = 0;
   const double nl = (double)h->S.n_loc;

@@ -468,6 +468,22 @@ int pgo_handle::coarse_setup() {
     cbp.push_back((int32_t)k);
   }
   co_ncb = (int)cbi.size();
+  // aggregates with no pose in the coarse space: every pose edge-less (no real incidence; k_coarse_basis tests the same through
+  // H_ii = 0) or the constant pose.  Their block (I, I) is zero; k_coarse_dead puts identity there, as on the padding.
+  std::vector<int32_t> dead;
+  for (int I = 0; I < co_nagg; ++I) {
+    bool any = false;
+    for (int32_t r = I * co_agg; r < std::min<int64_t>(NL, (int64_t)(I + 1) * co_agg) && !any; ++r) {
+      if (S.lo + r == fixed_internal) continue;
+      for (int32_t q = S.inc_ptr[r]; q < S.inc_ptr[r + 1] && !any; ++q) any = S.inc_edge[q] >= 0;
+    }
+    if (!any) dead.push_back(I);
+  }
+  co_ndead = (int)dead.size();
+  if (co_ndead) {
+    PGOC(dalloc(&co_dead, co_ndead));
+    PGOC(upload(co_dead, dead));
+  }
   PGOC(dalloc(&co_pb, 5 * NL));
   PGOC(dalloc(&co_cap, (int64_t)co_Kp * co_Kp));
   PGOC(dalloc(&co_nm, (int64_t)co_Kp * co_Kp));

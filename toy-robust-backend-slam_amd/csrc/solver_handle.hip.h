@@ -136,6 +136,10 @@ struct pgo_handle {
   int coarse_factor();     // per LM iteration: basis, Galerkin matrix, Cholesky + inverse factor
   double* co_ainv = nullptr;   // explicit inverse N'N (coarse orders <= COARSE_EXPLICIT_RANK: one product per apply)
   int32_t* co_ok = nullptr;    // device flag: the factorisation of this LM iteration is usable
+  int32_t* co_dead = nullptr;  // aggregates without a pose in the coarse space (identity on their coarse diagonal)
+  int co_ndead = 0;
+  bool co_flag_pending = false;   // pcg() left co_ok in scal[15] for the host fetch of lm_iteration_tail
+  int co_off_iters = 0;        // LM iterations whose PCG solve found the level switched off (co_ok = 0)
   int co_ndot = 0;             // partials of r_c . e_c appended to the r.z partials
   int coarse_solve(double* dot_part, const int32_t* done);   // e_c = (P'(H + D'D)P)^-1 P' r  (+ partials of r_c . e_c)
   // single-reduction PCG loop (k_cg_sr_*: one all-reduce per iteration; several ranks, inexact mode, chain preconditioner)

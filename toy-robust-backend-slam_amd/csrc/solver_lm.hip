@@ -263,8 +263,12 @@ int pgo_handle::lm_iteration_tail(bool* stop, pgo_iter_record& R, double it0, do
     // host synchronisation for the model terms AND the candidate instead of two
     PGOC(allgather(cand));
     PGOC(eval_enqueue(cand, sw_cand, 1, false, 6));
-    PGOC(fetch_scal(0, has_sw ? 15 : 10));
+    PGOC(fetch_scal(0, co_flag_pending ? 16 : (has_sw ? 15 : 10)));
     h_scal[1] = h_scal[0] - h_scal[1] - h_scal[3];   // y.(H y)
+    if (co_flag_pending) {   // scal[15]: the coarse level's flag of this solve (pcg())
+      if (h_scal[15] == 0.0) ++co_off_iters;
+      co_flag_pending = false;
+    }
     if (direct && !dl_retry) R.pcg_rel_residual = dl_rel = (h_scal[9] > 0.0) ? std::sqrt(h_scal[8] / h_scal[9]) : 0.0;
   }
   if (has_sw) {

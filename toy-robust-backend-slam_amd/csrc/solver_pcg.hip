@@ -35,6 +35,11 @@ int pgo_handle::coarse_factor() {
     hipLaunchKernelGGL(dev::k_coarse_pad<>, dim3(1), dim3(32), 0, stream, co_cap, co_dwork, co_K, co_Kp);
     PGOC(check_launch("k_coarse_pad"));
   }
+  if (co_ndead > 0) {
+    hipLaunchKernelGGL(dev::k_coarse_dead<>, dim3((3 * co_ndead + 255) / 256), dim3(256), 0, stream, co_cap, co_dwork, (const int32_t*)co_dead,
+                       co_ndead, co_Kp);
+    PGOC(check_launch("k_coarse_dead"));
+  }
   const int nb = co_Kp / 32;
   for (int kb = 0; kb < nb; ++kb) {
     hipLaunchKernelGGL(dev::k_chol_panel<>, dim3(std::max(1, nb - 1)), dim3(dev::CHOL_THREADS), dev::CHOL_LDS_BYTES, stream, co_cap, co_nm, co_dwork, co_Kp, nb, kb);
@@ -146,6 +151,10 @@ int pgo_handle::pcg(int* iters, double* rel) {
       hipLaunchKernelGGL(dev::k_coarse_prolong<>, dim3((unsigned)std::min<int64_t>((S.n_loc + 255) / 256, 512)), dim3(256), 0, stream, (int)S.n_loc,
                          co_agg, (const double*)co_pb, (const double*)co_ec, z, p_full + dev::PS * (int64_t)S.lo, (const int32_t*)co_ok);
       PGOC(check_launch("k_coarse_prolong"));
+      // whether this solve has the level: read back with the model terms (lm_iteration_tail), counted in co_off_iters
+      hipLaunchKernelGGL(dev::k_flag_to_double<>, dim3(1), dim3(1), 0, stream, (const int*)co_ok, scal + 15);
+      PGOC(check_launch("k_flag_to_double"));
+      co_flag_pending = true;
     }
     PGOC(reduce_to_scal({{part[0], n_rz0, 0}, {part[1], g_u1, 0}}, 4));
     hipLaunchKernelGGL(dev::k_cg_init_fin<>, dim3(1), dim3(1), 0, stream, st, scal + 4, opt.pcg_rtol);
