@@ -201,11 +201,16 @@ typedef struct pgo_options {
                                   aggregate, Galerkin matrix P'(J'J + D'D)P factorised densely per LM iteration (order <= 6143).
                                   It removes the smooth long-range error that block-Jacobi cannot: M3500 METHOD 1, PCG to 1e-10:
                                   1557 -> 178 iterations with 16-pose aggregates.  Taken as given (not rounded to the one-level
-                                  block: an aggregate may straddle two groups or segments).  One rank.  0 = off;
+                                  block: an aggregate may straddle two groups or segments).  0 = off;
                                   -1 (default) = auto, for graphs of >= 512 poses that stay on PCG while pcg_block_poses and
                                   pcg_chain_len are left at auto: on for tight solves
                                   (pcg_rtol <= 1e-3) -- 16 poses per aggregate up to 8192 poses, else 64, doubled until the
-                                  coarse order fits; loose solves (the inexact mode) stay on one level unless asked        */
+                                  coarse order fits; loose solves (the inexact mode) stay on one level unless asked.
+                                  Several ranks (or PGO_FORCE_COLLECTIVES=1): only an explicit value > 0 enables it (auto stays
+                                  one level there); the shard boundaries are then aligned to lcm(block or segment, this value),
+                                  so that the aggregates are those of the one-rank solve.  The coarse problem is replicated on
+                                  every rank (r_c rides in the all-reduce of the PCG dot products) and the PCG loop is the
+                                  two-reduction one; pgo_handle_info reports the global level identically on every rank.     */
 } pgo_options;
 
 void pgo_options_default(pgo_options* o);                                  /* [host] */
@@ -360,7 +365,7 @@ typedef struct pgo_handle_info {
   int32_t direct_switched_at;        /* auto, rank above 2048: the LM iteration after which the direct solve took over from PCG
                                         (its PCG solve cost more than a direct solve of this rank does), 0 = it has not       */
   int32_t pcg_coarse_poses;          /* resolved: poses per aggregate of the second preconditioner level, 0 = one level   */
-  int32_t pcg_coarse_rank;           /* order of its dense coarse matrix                                               */
+  int32_t pcg_coarse_rank;           /* order of its dense coarse matrix (all aggregates of the graph; the same on every rank) */
   int32_t pcg_single_reduction;      /* 1 = the PCG loop with ONE reduction point per iteration (Chronopoulos-Gear recurrences:
                                         world > 1, pcg_rtol >= 1e-6, chain preconditioner), 0 = the textbook two-reduction loop */
   int32_t pcg_coarse_off_iters;      /* LM iterations whose PCG solve ran WITHOUT the second level because its factorisation was
@@ -388,7 +393,9 @@ int pgo_bench_assemble(pgo_t* h, int reps, pgo_kernel_stats* out);              
 int pgo_bench_spmv(pgo_t* h, int reps, pgo_kernel_stats* out);                    /* [gpu] K3 */
 /* z = M^-1 r with the preconditioner the next LM iteration applies: current linearisation, current radius (both entry
  * points first set up the LM diagonal and the preconditioner, as an LM iteration does; the solve itself is not affected).
- * Needs at least one LM iteration.  r, z: 3N doubles, caller's pose order (world == 1).                               */
+ * Needs at least one LM iteration.  r, z: 3N doubles, caller's pose order.  world == 1, or several ranks with the second
+ * preconditioner level on: then a collective call -- every rank passes the whole r and receives z on the rows it owns
+ * (0 on the others), so that the ranks' z add up to the applied M^-1 r.                                               */
 int pgo_debug_precond(pgo_t* h, const double* r_3n, double* z_3n);               /* [gpu] */
 int pgo_bench_precond(pgo_t* h, int reps, pgo_kernel_stats* out);                 /* [gpu] z = M^-1 b as the PCG start-up kernel */
 /* y = (J'J) x in the scaled space at the current linearisation, WITHOUT the LM diagonal; x,y: 3N doubles (world == 1).

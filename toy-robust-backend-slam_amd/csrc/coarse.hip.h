@@ -351,5 +351,221 @@ __global__ __launch_bounds__(WG) void k_cg_update2c(CgVec V, int parity, const d
   }
 }
 
+// ------------------------------------------------------------------------------------------------ several ranks
+// Sharded solves (world > 1, or one rank with the collectives forced on) replicate the coarse problem: every rank holds the
+// whole Kp x Kp matrix, its factor and the whole r_c / e_c, and only the restriction and the prolongation are distributed.
+// The shards are aligned to the aggregate size, so aggregate g is the global rows [g A, min(N, (g + 1) A)) on any world
+// size -- the one-rank aggregation.  Per LM iteration every rank computes the basis planes of ALL poses (poses and scales
+// are replicated; an edge mask stands in for k_coarse_basis's H_ii test, which needs the owner's diagonal blocks), so a
+// halo pose has the same planes on every rank; it sums the Galerkin blocks (I, J) of its own aggregates I with the
+// fixed-order wavefront sum of k_coarse_assemble into a compact value list; the lists are all-gathered and scattered into
+// the dense matrix (one producer per block: the same bits on every rank), which every rank then factorises.  Per PCG
+// iteration each rank writes P'r of its own aggregates into its slice of a zeroed Kp vector that rides in the all-reduce
+// of the r.z / r.r sums; e_c = A_c^-1 r_c and r_c . e_c are then computed redundantly on every rank.
+
+struct CoarseMArgs {
+  int32_t n;            // poses (global)
+  int32_t lo, n_loc;    // owned rows
+  int32_t agg, n_agg;   // poses per aggregate, aggregates (global)
+  const double* poses;  // [n x 3] (replicated)
+  const double* scale;  // [n x 3] (replicated)
+  const uint8_t* live;  // [n] 1 = the pose has an edge (an edge-less pose stays out of the coarse space)
+  double* pb;           // 5 planes [n]
+  const double* hoff;   // this rank's off-diagonal blocks
+  const double* hd;     // 6 planes [n_loc]
+  const double* d2;     // [n_loc x 3]
+  const int32_t* inc_col;
+  // this rank's coarse blocks: global aggregates (cb_i[b], cb_j[b]), fine entries cb_q[cb_ptr[b] .. cb_ptr[b+1]) with GLOBAL rows cb_row[]
+  const int32_t* cb_i;
+  const int32_t* cb_j;
+  const int32_t* cb_ptr;
+  const int32_t* cb_q;
+  const int32_t* cb_row;
+  int32_t n_cb;
+  double* vals;         // [n_cb x 9] block values, row-major (this rank's slot of the gathered list)
+};
+
+// k_coarse_basis over every aggregate of the graph
+template <int PGO_UNIT_ = 0>
+__global__ __launch_bounds__(256) void k_coarse_basis_m(CoarseMArgs A) {
+  const int w = (int)((blockIdx.x * 256 + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+  if (w >= A.n_agg) return;
+  const int i0 = w * A.agg, i1 = min(A.n, i0 + A.agg);
+  double sx = 0.0, sy = 0.0;
+  for (int i = i0 + lane; i < i1; i += 64) {
+    sx += A.poses[3 * (int64_t)i];
+    sy += A.poses[3 * (int64_t)i + 1];
+  }
+  sx = __shfl(wave_sum_fixed(sx), 0, 64);
+  sy = __shfl(wave_sum_fixed(sy), 0, 64);
+  const double cx = sx / (double)(i1 - i0), cy = sy / (double)(i1 - i0);
+  const int64_t n = A.n;
+  for (int i = i0 + lane; i < i1; i += 64) {
+    const double s0 = A.scale[3 * (int64_t)i], s1 = A.scale[3 * (int64_t)i + 1], s2 = A.scale[3 * (int64_t)i + 2];
+    const bool in_graph = A.live[i] != 0;
+    const double a0 = (in_graph && s0 > 0.0) ? 1.0 / s0 : 0.0, a1 = (in_graph && s1 > 0.0) ? 1.0 / s1 : 0.0,
+                 a2 = (in_graph && s2 > 0.0) ? 1.0 / s2 : 0.0;
+    A.pb[i] = a0;
+    A.pb[n + i] = a1;
+    A.pb[2 * n + i] = a2;
+    A.pb[3 * n + i] = -(A.poses[3 * (int64_t)i + 1] - cy) * a0;
+    A.pb[4 * n + i] = (A.poses[3 * (int64_t)i] - cx) * a1;
+  }
+}
+
+// k_coarse_assemble for this rank's blocks, into the compact value list
+template <int PGO_UNIT_ = 0>
+__global__ __launch_bounds__(256) void k_coarse_assemble_m(CoarseMArgs A) {
+  const int b = (int)((blockIdx.x * 256 + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+  if (b >= A.n_cb) return;
+  const int I = A.cb_i[b], J = A.cb_j[b];
+  const int64_t n = A.n, nl = A.n_loc;
+  double C[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int k = A.cb_ptr[b] + lane; k < A.cb_ptr[b + 1]; k += 64) {
+    const int q = A.cb_q[k], row = A.cb_row[k];
+    const int col = A.inc_col[q];
+    double h[9];
+    hoff_load(A.hoff, q, h);
+    coarse_accumulate(C, pb_load(A.pb, n, row), h, pb_load(A.pb, n, col));
+  }
+  if (I == J) {   // an own aggregate: its rows are owned
+    const int i0 = I * A.agg, i1 = min(A.n, i0 + A.agg);
+    for (int i = i0 + lane; i < i1; i += 64) {
+      const int64_t l = i - A.lo;
+      const double d00 = A.hd[l] + A.d2[3 * l], d01 = A.hd[nl + l], d02 = A.hd[2 * nl + l];
+      const double d11 = A.hd[3 * nl + l] + A.d2[3 * l + 1], d12 = A.hd[4 * nl + l], d22 = A.hd[5 * nl + l] + A.d2[3 * l + 2];
+      const double h[9] = {d00, d01, d02, d01, d11, d12, d02, d12, d22};
+      const PBasis p = pb_load(A.pb, n, i);
+      coarse_accumulate(C, p, h, p);
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 9; ++c) C[c] = wave_sum_fixed(C[c]);
+  if (lane == 0) {
+#pragma unroll
+    for (int c = 0; c < 9; ++c) A.vals[9 * (int64_t)b + c] = C[c];
+  }
+}
+
+// the gathered block values into the (zeroed) dense matrix and its diagonal 32 x 32 blocks: one thread per value; every
+// block (I, J) appears once in the list (produced by the rank owning I), padding entries have I < 0
+template <int PGO_UNIT_ = 0>
+__global__ __launch_bounds__(256) void k_coarse_scatter(const double* __restrict__ vals, const int32_t* __restrict__ gi,
+                                                        const int32_t* __restrict__ gj, int64_t n_blk, double* __restrict__ cap,
+                                                        double* __restrict__ dwork, int Kp) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= 9 * n_blk) return;
+  const int64_t b = t / 9;
+  const int I = gi[b], J = gj[b];
+  if (I < 0) return;
+  const int e = (int)(t - 9 * b);
+  const int p = 3 * I + e / 3, q = 3 * J + e % 3;
+  const double v = vals[t];
+  cap[(int64_t)p * Kp + q] = v;
+  if ((p >> 5) == (q >> 5)) dwork[(int64_t)(p >> 5) * 1024 + (p & 31) * 32 + (q & 31)] = v;
+}
+
+// r_c = P'r into the global Kp vector: one wavefront per aggregate slot (ceil(Kp / 3) of them); slots this rank does not
+// own -- the peers' aggregates and the padding -- are written 0, so the all-reduce sums one non-zero term per entry.  After
+// convergence (done) every slot is written 0.
+template <int PGO_UNIT_ = 0>
+__global__ __launch_bounds__(256) void k_coarse_restrict_m(int n_loc, int lo, int agg, int a0, int n_own, int Kp, const double* __restrict__ pb,
+                                                           int64_t n, const double* __restrict__ r, double* __restrict__ rc,
+                                                           const int32_t* __restrict__ done) {
+  const int w = (int)((blockIdx.x * 256 + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+  if (3 * w >= Kp) return;
+  double c0 = 0.0, c1 = 0.0, c2 = 0.0;
+  if (w >= a0 && w < a0 + n_own && !(done && *done)) {
+    const int i0 = w * agg - lo, i1 = min(n_loc, i0 + agg);
+    for (int i = i0 + lane; i < i1; i += 64) {
+      const PBasis p = pb_load(pb, n, lo + i);
+      const double r0 = r[3 * (int64_t)i], r1 = r[3 * (int64_t)i + 1], r2 = r[3 * (int64_t)i + 2];
+      c0 += p.a0 * r0;
+      c1 += p.a1 * r1;
+      c2 += p.b0 * r0 + p.b1 * r1 + p.a2 * r2;
+    }
+    c0 = wave_sum_fixed(c0);
+    c1 = wave_sum_fixed(c1);
+    c2 = wave_sum_fixed(c2);
+  }
+  if (lane == 0) {   // (Kp is a multiple of 32: a slot may hold fewer than 3 entries)
+    rc[3 * w] = c0;
+    if (3 * w + 1 < Kp) rc[3 * w + 1] = c1;
+    if (3 * w + 2 < Kp) rc[3 * w + 2] = c2;
+  }
+}
+
+// k_coarse_prolong on the owned rows (global aggregates, global basis planes)
+template <int PGO_UNIT_ = 0>
+__global__ __launch_bounds__(256) void k_coarse_prolong_m(int n_loc, int lo, int agg, const double* __restrict__ pb, int64_t n,
+                                                          const double* __restrict__ ec, double* __restrict__ z, double* __restrict__ p,
+                                                          const int32_t* __restrict__ ok) {
+  if (!*ok) return;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n_loc; i += gridDim.x * 256) {
+    const PBasis b = pb_load(pb, n, lo + i);
+    const int I = (lo + i) / agg;
+    const double e0 = ec[3 * I], e1 = ec[3 * I + 1], e2 = ec[3 * I + 2];
+    const double z0 = b.a0 * e0 + b.b0 * e2, z1 = b.a1 * e1 + b.b1 * e2, z2 = b.a2 * e2;
+    double* zz = z + 3 * (int64_t)i;
+    zz[0] += z0;
+    zz[1] += z1;
+    zz[2] += z2;
+    if (p) {
+      double* pp = p + PS * (int64_t)(lo + i);
+      pp[0] += z0;
+      pp[1] += z1;
+      pp[2] += z2;
+    }
+  }
+}
+
+// the PCG start-up's scalars: out[0] = r.z + r_c . e_c (the coarse share added once, after the all-reduce), out[1] = b.b
+template <int PGO_UNIT_ = 0>
+__global__ __launch_bounds__(WG) void k_coarse_fin(const double* __restrict__ red, const double* __restrict__ dot_part, int n_dot,
+                                                   double* __restrict__ out) {
+  __shared__ double sh[8];
+  const double c = sum_partials_bcast(dot_part, n_dot, sh);
+  if (threadIdx.x == 0) {
+    out[0] = red[0] + c;
+    out[1] = red[1];
+  }
+}
+
+// k_cg_update2c for several ranks: red = the all-reduced (r.z, r.r) of the one-level preconditioner, to which the coarse
+// share r_c . e_c (the same partials on every rank) is added; the prolongation of the global e_c on the owned rows
+template <int PGO_UNIT_ = 0>
+__global__ __launch_bounds__(WG) void k_cg_update2cm(CgVec V, int parity, const double* __restrict__ red, const double* __restrict__ dot_part,
+                                                     int n_dot, int agg, const double* __restrict__ pb, int64_t n,
+                                                     const double* __restrict__ ec) {
+  __shared__ double sh[8];
+  if (V.st->done) return;
+  const double rz_new = red[0] + sum_partials_bcast(dot_part, n_dot, sh);
+  const double rr = red[1];
+  const double rz_old = V.st->rz[parity];
+  const double tol2 = V.st->tol2;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    V.st->rz[parity ^ 1] = rz_new;
+    V.st->rr = rr;
+    V.st->iters += 1;
+  }
+  if (rr <= tol2) {  // converged (the same decision on every rank: the same reduced scalars)
+    if (blockIdx.x == 0 && threadIdx.x == 0) V.st->done = 1;
+    return;
+  }
+  const double beta = rz_new / rz_old;
+  const int lo = V.lo;
+  double* p = V.p + PS * (int64_t)lo;
+  for (int i = blockIdx.x * WG + threadIdx.x; i < V.n_loc; i += gridDim.x * WG) {
+    const PBasis b = pb_load(pb, n, lo + i);
+    const int I = (lo + i) / agg;
+    const double e0 = ec[3 * I], e1 = ec[3 * I + 1], e2 = ec[3 * I + 2];
+    const double* zz = V.z + 3 * (int64_t)i;
+    double* pp = p + PS * (int64_t)i;
+    pp[0] = (zz[0] + (b.a0 * e0 + b.b0 * e2)) + beta * pp[0];
+    pp[1] = (zz[1] + (b.a1 * e1 + b.b1 * e2)) + beta * pp[1];
+    pp[2] = (zz[2] + b.a2 * e2) + beta * pp[2];
+  }
+}
+
 }  // namespace dev
 }  // namespace pgo

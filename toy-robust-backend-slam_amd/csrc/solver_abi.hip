@@ -485,20 +485,22 @@ int pgo_debug_system_spmv(pgo_t* h, const double* x, double* yout, double* d2_ou
 }
 
 // z = M^-1 r with the preconditioner the next LM iteration applies (whatever family the handle resolved to), through the
-// PCG start-up kernel: for the restatement and property tests.  Needs at least one LM iteration; world == 1.
+// PCG start-up kernel: for the restatement and property tests.  Needs at least one LM iteration; world == 1, or several ranks
+// with the second preconditioner level (a collective call: every rank passes the whole r and receives z on its own rows).
 int pgo_debug_precond(pgo_t* h, const double* r_in, double* z_out) {
   if (!h || !r_in || !z_out) return fail(PGO_ERR_INVALID_ARG, "pgo_debug_precond: null");
-  if (h->comm && h->comm->world > 1) return fail(PGO_ERR_UNSUPPORTED, "world == 1 only");
+  if (h->comm && h->comm->world > 1 && !h->co_multi) return fail(PGO_ERR_UNSUPPORTED, "world == 1 only (several ranks: with pcg_coarse_poses > 0)");
   if (!h->lin_valid || h->iter < 1) return fail(PGO_ERR_INVALID_ARG, "pgo_debug_precond: run at least one LM iteration first");
   HIPC(hipSetDevice(h->device));
-  const int64_t N = h->S.n_poses;
+  const int64_t N = h->S.n_poses, lo = h->S.lo, NL = h->S.n_loc;
   std::vector<double> tmp;
   const double* src = r_in;
   if (!h->perm.empty()) {
     h->to_internal(r_in, &tmp, 3);
     src = tmp.data();
   }
-  HIPC(hipMemcpyAsync(h->ap, src, (size_t)3 * N * sizeof(double), hipMemcpyHostToDevice, h->stream));  // ap: scratch input
+  if (NL > 0)   // ap: scratch input (the owned rows)
+    HIPC(hipMemcpyAsync(h->ap, src + 3 * lo, (size_t)3 * NL * sizeof(double), hipMemcpyHostToDevice, h->stream));
   PGOC(prepare_for_debug(h));
   dev::CgVec V = h->cg_vec();
   if (h->chain_len) {
@@ -515,14 +517,21 @@ int pgo_debug_precond(pgo_t* h, const double* r_in, double* z_out) {
     hipLaunchKernelGGL(dev::k_cg_init<>, dim3(h->g_vec), dim3(dev::WG), 0, h->stream, V, (const double*)h->ap, h->part[0], h->part[1]);
   }
   PGOC(h->check_launch("k_cg_init (debug)"));
-  if (h->use_coarse) {   // the second level's share of z
+  if (h->use_coarse && h->co_multi) {   // several ranks: r_c through the all-reduce, the replicated coarse solve, the own rows of P e_c
+    PGOC(h->coarse_restrict_reduce(h->part[0], 1, h->part[1], 1, nullptr));
+    PGOC(h->coarse_solve(h->co_dotp, nullptr));
+    hipLaunchKernelGGL(dev::k_coarse_prolong_m<>, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((NL + 255) / 256, 512))), dim3(256), 0,
+                       h->stream, (int)NL, (int)lo, h->co_agg, (const double*)h->co_pb, (int64_t)N, (const double*)h->co_ec, h->z, (double*)nullptr,
+                       (const int32_t*)h->co_ok);
+    PGOC(h->check_launch("k_coarse_prolong_m"));
+  } else if (h->use_coarse) {   // the second level's share of z
     PGOC(h->coarse_solve(h->part[3], nullptr));
     hipLaunchKernelGGL(dev::k_coarse_prolong<>, dim3((unsigned)std::min<int64_t>((h->S.n_loc + 255) / 256, 512)), dim3(256), 0, h->stream,
                        (int)h->S.n_loc, h->co_agg, (const double*)h->co_pb, (const double*)h->co_ec, h->z, (double*)nullptr, (const int32_t*)h->co_ok);
     PGOC(h->check_launch("k_coarse_prolong"));
   }
-  std::vector<double> ztmp((size_t)3 * N);
-  HIPC(hipMemcpyAsync(ztmp.data(), h->z, ztmp.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  std::vector<double> ztmp((size_t)3 * N, 0.0);   // (several ranks: the peers' rows stay 0)
+  if (NL > 0) HIPC(hipMemcpyAsync(ztmp.data() + 3 * lo, h->z, (size_t)3 * NL * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   PGOC(h->sync());
   if (h->perm.empty()) memcpy(z_out, ztmp.data(), ztmp.size() * sizeof(double));
   else h->to_caller(ztmp, z_out, 3);

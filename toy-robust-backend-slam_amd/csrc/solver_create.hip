@@ -1,6 +1,8 @@
 // pgo_handle::create -- replaces the problem assembly of DCS-ceres/main.cpp:66-68,95-153: shard structure (structure.cpp) ->
 // device buffers, grids, and the choices made once per handle: preconditioner family, direct solve (direct_setup), second
 // preconditioner level (coarse_setup).
+#include <numeric>
+
 #include "solver_handle.hip.h"
 
 // --------------------------------------------------------------------- create
@@ -86,7 +88,14 @@ int pgo_handle::create(int32_t N, const double* poses_h, int32_t E, const int32_
     poses_h = poses_p.data();
     if (fixed_internal >= 0) fixed_internal = perm[fixed_internal];
   }
-  PGOC(pgo::build_shard_structure(N, E, ia, ib, meas, kind, opt.method, world, rank, chain_len ? chain_len : grp_B, &S,
+  int64_t row_align = chain_len ? chain_len : grp_B;
+  if (opt.pcg_coarse_poses > 0 && multi_rank() && !batch_mode) {
+    // the second preconditioner level on several ranks: shards of whole aggregates, so that the aggregation is the one-rank
+    // aggregation (coarse_setup)
+    row_align = std::lcm(row_align, (int64_t)opt.pcg_coarse_poses);
+    if (row_align * world > (int64_t)1 << 30) return fail(PGO_ERR_INVALID_ARG, "pcg_coarse_poses: too large to align the shards to");
+  }
+  PGOC(pgo::build_shard_structure(N, E, ia, ib, meas, kind, opt.method, world, rank, (int)row_align, &S,
                                   tile_breaks_h.empty() ? nullptr : &tile_breaks_h));
   // Graphs large enough for the one-tile-per-workgroup product kernel (k_spmv_1, below) get the padded-slot layout: every
   // tile's incidences at TILE_INC t (structure.cpp, pad_tiles_to_slots).  Test hook "pad_tiles" = 0 keeps the dense layout.
@@ -387,24 +396,27 @@ int pgo_handle::create(int32_t N, const double* poses_h, int32_t E, const int32_
   }
   if (batch_mode) PGOC(dalloc(&edge_cost, std::max<int64_t>(EL, 1)));
   PGOC(direct_setup(N));
-  PGOC(coarse_setup());   // (after the direct solver's decision: auto adds the coarse level only to solves that stay on PCG)
+  PGOC(coarse_setup(E, ia, ib));   // (after the direct solver's decision: auto adds the coarse level only to solves that stay on PCG)
   return sync();
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // Second preconditioner level (coarse.hip.h).  opt.pcg_coarse_poses: 0 = off, > 0 = poses per aggregate, -1 = auto.
-int pgo_handle::coarse_setup() {
-  const int world = comm ? comm->world : 1;
-  const int64_t NL = S.n_loc;
+int pgo_handle::coarse_setup(int32_t E, const int32_t* ia, const int32_t* ib) {
+  const int world = comm ? comm->world : 1, rank = comm ? comm->rank : 0;
+  const bool multi = multi_rank();
+  const int64_t NL = S.n_loc, N = S.n_poses;
   int want = opt.pcg_coarse_poses;
   if (want == 0) return PGO_OK;
   auto no = [&](const std::string& why) -> int {
     if (want > 0) return fail(PGO_ERR_UNSUPPORTED, "pcg_coarse_poses: " + why);
     return PGO_OK;
   };
-  if (world != 1 || force_collectives) return no("one rank only");
+  // several ranks: only on request (auto stays one level until a multi-GPU box has measured it).  Every decision below is
+  // taken on rank-independent inputs (the graph, the options, the shard size): all ranks enable the level, or none does.
+  if (multi && want < 0) return PGO_OK;
   if (batch_mode) return no("not inside a batched handle");
-  if (NL < 2) return PGO_OK;
+  if (N < 2) return PGO_OK;
   if (want < 0) {
     // auto (measured on MI355X, scripts/exp_coarse.py, GN it/s one level -> two levels):
     //   tight solves (pcg_rtol <= 1e-3) of graphs that stay on PCG -- M3500 METHOD 1 47 -> 156 (16-pose aggregates, coarse
@@ -421,36 +433,42 @@ int pgo_handle::coarse_setup() {
     while (3 * ((NL + want - 1) / want) + 1 > COARSE_MAX_RANK) want *= 2;
   }
   co_agg = want;
-  co_nagg = (int)((NL + co_agg - 1) / co_agg);
+  if (multi && S.rows_per_rank % co_agg != 0) return fail(PGO_ERR_INVALID_ARG, "pcg_coarse_poses: shards not aligned to the aggregates");
+  // aggregates: runs of co_agg consecutive rows, numbered globally; this rank owns [co_aoff, co_aoff + co_nown) (one rank: all)
+  co_nagg = (int)((N + co_agg - 1) / co_agg);
+  co_aoff = (int)(S.lo / co_agg);
+  co_nown = (int)((NL + co_agg - 1) / co_agg);
   co_K = 3 * co_nagg;
   if (co_K + 1 > COARSE_MAX_RANK) return no("the coarse matrix would have order " + std::to_string(co_K) + " (at most " + std::to_string(COARSE_MAX_RANK - 1) + ")");
   co_Kp = ((co_K + dev::CHOL_NB - 1) / dev::CHOL_NB) * dev::CHOL_NB;
-  // coarse blocks and their fine entries: incidences sorted by (aggregate of the row, aggregate of the column, position)
+  // coarse blocks of the own aggregates and their fine entries: incidences sorted by (aggregate of the row, aggregate of the
+  // column, position); the column's aggregate may be a peer's (halo)
   std::vector<uint64_t> key((size_t)S.n_inc);
   {
     size_t k = 0;
     for (int32_t r = 0; r < S.n_loc; ++r)
       for (int32_t q = S.inc_ptr[r]; q < S.inc_ptr[r + 1]; ++q) {
-        const uint64_t I = (uint64_t)(r / co_agg), J = (uint64_t)((S.inc_col[q] - S.lo) / co_agg);
+        const uint64_t I = (uint64_t)((S.lo + r) / co_agg), J = (uint64_t)(S.inc_col[q] / co_agg);
         key[k++] = ((I * (uint64_t)co_nagg + J) << 32) | (uint32_t)q;
       }
   }
   std::sort(key.begin(), key.end());
   std::vector<int32_t> row_of((size_t)S.n_inc);
   for (int32_t r = 0; r < S.n_loc; ++r)
-    for (int32_t q = S.inc_ptr[r]; q < S.inc_ptr[r + 1]; ++q) row_of[q] = r;
+    for (int32_t q = S.inc_ptr[r]; q < S.inc_ptr[r + 1]; ++q) row_of[q] = S.lo + r;
   std::vector<int32_t> cbi, cbj, cbp, cbq((size_t)S.n_inc), cbr((size_t)S.n_inc);
   {
     size_t k = 0;
-    int next_diag = 0;   // every aggregate gets its (I, I) block, also without an off-diagonal fine entry inside
+    int next_diag = co_aoff;   // every aggregate gets its (I, I) block, also without an off-diagonal fine entry inside
+    const int end_diag = co_aoff + co_nown;
     auto open_block = [&](int I, int J) {
       cbi.push_back(I);
       cbj.push_back(J);
       cbp.push_back((int32_t)k);
     };
-    while (k < key.size() || next_diag < co_nagg) {
+    while (k < key.size() || next_diag < end_diag) {
       const uint64_t blk = k < key.size() ? (key[k] >> 32) : ~0ull;
-      const uint64_t dblk = next_diag < co_nagg ? (uint64_t)next_diag * co_nagg + next_diag : ~0ull;
+      const uint64_t dblk = next_diag < end_diag ? (uint64_t)next_diag * co_nagg + next_diag : ~0ull;
       if (dblk < blk) {   // a diagonal block without fine off-diagonal entries
         open_block(next_diag, next_diag);
         ++next_diag;
@@ -471,29 +489,36 @@ int pgo_handle::coarse_setup() {
   // aggregates with no pose in the coarse space: every pose edge-less (no real incidence; k_coarse_basis tests the same through
   // H_ii = 0) or the constant pose.  Their block (I, I) is zero; k_coarse_dead puts identity there, as on the padding.
   std::vector<int32_t> dead;
-  for (int I = 0; I < co_nagg; ++I) {
+  for (int Il = 0; Il < co_nown; ++Il) {
     bool any = false;
-    for (int32_t r = I * co_agg; r < std::min<int64_t>(NL, (int64_t)(I + 1) * co_agg) && !any; ++r) {
+    for (int32_t r = Il * co_agg; r < std::min<int64_t>(NL, (int64_t)(Il + 1) * co_agg) && !any; ++r) {
       if (S.lo + r == fixed_internal) continue;
       for (int32_t q = S.inc_ptr[r]; q < S.inc_ptr[r + 1] && !any; ++q) any = S.inc_edge[q] >= 0;
     }
-    if (!any) dead.push_back(I);
+    if (!any) dead.push_back(co_aoff + Il);
   }
+  if (multi) PGOC(coarse_setup_multi(E, ia, ib, world, rank, cbi, cbj, dead, &dead));   // (dead: every rank's, afterwards)
   co_ndead = (int)dead.size();
   if (co_ndead) {
     PGOC(dalloc(&co_dead, co_ndead));
     PGOC(upload(co_dead, dead));
   }
-  PGOC(dalloc(&co_pb, 5 * NL));
+  PGOC(dalloc(&co_pb, 5 * (multi ? N : NL)));
   PGOC(dalloc(&co_cap, (int64_t)co_Kp * co_Kp));
   PGOC(dalloc(&co_nm, (int64_t)co_Kp * co_Kp));
   PGOC(dalloc(&co_dwork, (int64_t)(co_Kp / 32) * 1024));
-  PGOC(dalloc(&co_rc, co_Kp));
+  if (multi) {
+    PGOC(dalloc(&co_red, co_Kp + 2));
+    co_rc = co_red;
+  } else {
+    PGOC(dalloc(&co_rc, co_Kp));
+  }
   PGOC(dalloc(&co_cy, co_Kp));
   PGOC(dalloc(&co_ec, co_Kp));
   PGOC(dalloc(&co_ok, 1));
   if (co_Kp <= COARSE_EXPLICIT_RANK) PGOC(dalloc(&co_ainv, (int64_t)co_Kp * co_Kp));
   co_ndot = co_ainv ? (co_Kp + 3) / 4 : (co_Kp + 255) / 256;
+  if (multi) PGOC(dalloc(&co_dotp, co_ndot));
   PGOC(dalloc(&co_cb_i, co_ncb));
   PGOC(dalloc(&co_cb_j, co_ncb));
   PGOC(dalloc(&co_cb_ptr, co_ncb + 1));
@@ -507,12 +532,77 @@ int pgo_handle::coarse_setup() {
   PGOC(sync());   // the host lists die with this scope
   HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(dev::k_chol_panel<>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dev::CHOL_LDS_BYTES));
   use_coarse = true;
+  co_multi = multi;
   if (opt.linear_solver == 0) dl_possible = false;   // (ranks above the direct solve's cheap range: two-level PCG instead of the PCG / direct alternation)
   // the loops that fold launches together assume the one-level preconditioner: two-level solves take the plain three-kernel loop
+  // (several ranks: the two-reduction loop on every rank)
   solo = false;
   fused_p = false;
   use_sr = false;
   return PGO_OK;
+}
+
+// Several ranks: the edge mask of the basis planes, and the coarse coordinates of every rank's blocks and dead aggregates --
+// all-gathered once, in lists padded to the longest rank's (the counts agreed by an all-reduce), so that every rank knows
+// where each gathered block value lands in the dense matrix.  A rank that owns no rows contributes empty lists.
+int pgo_handle::coarse_setup_multi(int32_t E, const int32_t* ia, const int32_t* ib, int world, int rank, const std::vector<int32_t>& cbi,
+                                   const std::vector<int32_t>& cbj, const std::vector<int32_t>& dead, std::vector<int32_t>* gdead) {
+  const int64_t N = S.n_poses;
+  {
+    std::vector<uint8_t> live((size_t)N, 0);
+    for (int32_t e = 0; e < E; ++e) live[ia[e]] = live[ib[e]] = 1;
+    PGOC(dalloc(&co_live, N));
+    PGOC(upload(co_live, live));
+    PGOC(sync());   // `live` dies with this scope
+  }
+  double* d_buf = nullptr;
+  auto coll = [&](int64_t n, const std::function<int()>& body) -> int {   // body on a temporary device buffer of n doubles
+    HIPC(hipMalloc((void**)&d_buf, (size_t)std::max<int64_t>(n, 1) * sizeof(double)));
+    const int st_b = body();
+    (void)hipFree(d_buf);
+    d_buf = nullptr;
+    return st_b;
+  };
+  double cnt[2] = {(double)cbi.size(), (double)dead.size()};
+  PGOC(coll(2, [&]() -> int {
+    HIPC(hipMemcpyAsync(d_buf, cnt, sizeof cnt, hipMemcpyHostToDevice, stream));
+    if (comm->allreduce(d_buf, 2, true, stream) != 0) return fail(PGO_ERR_COMM, "coarse level: all-reduce of the block counts failed");
+    HIPC(hipMemcpyAsync(cnt, d_buf, sizeof cnt, hipMemcpyDeviceToHost, stream));
+    return sync();
+  }));
+  co_ncb_max = (int)cnt[0];
+  const int64_t ndm = (int64_t)cnt[1], cpr = 2 * (int64_t)co_ncb_max + ndm;
+  std::vector<double> all((size_t)(world * cpr), -1.0);
+  for (size_t b = 0; b < cbi.size(); ++b) {
+    all[(size_t)(rank * cpr + 2 * b)] = cbi[b];
+    all[(size_t)(rank * cpr + 2 * b + 1)] = cbj[b];
+  }
+  for (size_t d = 0; d < dead.size(); ++d) all[(size_t)(rank * cpr + 2 * co_ncb_max + d)] = dead[d];
+  PGOC(coll(world * cpr, [&]() -> int {
+    HIPC(hipMemcpyAsync(d_buf, all.data(), all.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+    if (comm->allgather_inplace(d_buf, cpr, stream) != 0) return fail(PGO_ERR_COMM, "coarse level: all-gather of the block lists failed");
+    HIPC(hipMemcpyAsync(all.data(), d_buf, all.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    return sync();
+  }));
+  const int64_t nblk = (int64_t)world * co_ncb_max;
+  std::vector<int32_t> gi((size_t)std::max<int64_t>(nblk, 1), -1), gj((size_t)std::max<int64_t>(nblk, 1), -1);
+  gdead->clear();
+  for (int r = 0; r < world; ++r) {
+    for (int b = 0; b < co_ncb_max; ++b) {
+      gi[(size_t)r * co_ncb_max + b] = (int32_t)all[(size_t)(r * cpr + 2 * b)];
+      gj[(size_t)r * co_ncb_max + b] = (int32_t)all[(size_t)(r * cpr + 2 * b + 1)];
+    }
+    for (int64_t d = 0; d < ndm; ++d) {
+      const double v = all[(size_t)(r * cpr + 2 * co_ncb_max + d)];
+      if (v >= 0.0) gdead->push_back((int32_t)v);
+    }
+  }
+  PGOC(dalloc(&co_gi, nblk));
+  PGOC(dalloc(&co_gj, nblk));
+  PGOC(dalloc(&co_gvals, 9 * nblk));
+  PGOC(upload(co_gi, gi));
+  PGOC(upload(co_gj, gj));
+  return sync();   // (the host lists die with this scope)
 }
 
 // ---------------------------------------------------------------------------------------------------------------

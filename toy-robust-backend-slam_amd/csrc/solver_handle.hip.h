@@ -132,7 +132,7 @@ struct pgo_handle {
   int co_agg = 0, co_nagg = 0, co_K = 0, co_Kp = 0, co_ncb = 0;
   double *co_pb = nullptr, *co_cap = nullptr, *co_nm = nullptr, *co_dwork = nullptr, *co_rc = nullptr, *co_cy = nullptr, *co_ec = nullptr;
   int32_t *co_cb_i = nullptr, *co_cb_j = nullptr, *co_cb_ptr = nullptr, *co_cb_q = nullptr, *co_cb_row = nullptr;
-  int coarse_setup();      // create: aggregates, coarse block lists, buffers
+  int coarse_setup(int32_t E, const int32_t* ia, const int32_t* ib);   // create: aggregates, coarse block lists, buffers
   int coarse_factor();     // per LM iteration: basis, Galerkin matrix, Cholesky + inverse factor
   double* co_ainv = nullptr;   // explicit inverse N'N (coarse orders <= COARSE_EXPLICIT_RANK: one product per apply)
   int32_t* co_ok = nullptr;    // device flag: the factorisation of this LM iteration is usable
@@ -142,6 +142,19 @@ struct pgo_handle {
   int co_off_iters = 0;        // LM iterations whose PCG solve found the level switched off (co_ok = 0)
   int co_ndot = 0;             // partials of r_c . e_c appended to the r.z partials
   int coarse_solve(double* dot_part, const int32_t* done);   // e_c = (P'(H + D'D)P)^-1 P' r  (+ partials of r_c . e_c)
+  // several ranks (coarse.hip.h, "several ranks"): replicated coarse problem, aggregates numbered globally
+  bool co_multi = false;
+  int co_aoff = 0, co_nown = 0;   // this rank's aggregates: [co_aoff, co_aoff + co_nown) (co_nagg counts all of them)
+  int co_ncb_max = 0;             // blocks per rank in the gathered list (the largest rank's count)
+  uint8_t* co_live = nullptr;     // [N] poses with an edge
+  double* co_red = nullptr;       // [Kp + 2]: r_c (global), then the r.z / r.r sums -- one all-reduce
+  double* co_gvals = nullptr;     // [world x co_ncb_max x 9] block values, rank r's at r x co_ncb_max x 9
+  int32_t *co_gi = nullptr, *co_gj = nullptr;   // [world x co_ncb_max] their coarse coordinates (-1: padding)
+  double* co_dotp = nullptr;      // [co_ndot] partials of r_c . e_c
+  int coarse_setup_multi(int32_t E, const int32_t* ia, const int32_t* ib, int world, int rank, const std::vector<int32_t>& cbi,
+                         const std::vector<int32_t>& cbj, const std::vector<int32_t>& dead, std::vector<int32_t>* gdead);
+  int coarse_assemble_multi();
+  int coarse_restrict_reduce(const double* rz_part, int n_rz, const double* rr_part, int n_rr, const int32_t* done);
   // single-reduction PCG loop (k_cg_sr_*: one all-reduce per iteration; several ranks, inexact mode, chain preconditioner)
   bool use_sr = false;
   bool verify_residual = false;   // test hook: pcg() reports the true residual of its solution
@@ -318,6 +331,7 @@ struct pgo_handle {
 
   // ---- reductions to scalars: scal[first..first+k) = reduce(parts) [+ all-reduce], no host sync
   int reduce_to_scal(std::initializer_list<PartRef> parts, int first, bool allreduce_max = false);
+  int reduce_parts(std::initializer_list<PartRef> parts, double* out, double* ar, int ar_n, bool allreduce_max);
   int fetch_scal(int first, int count) {
     HIPC(hipMemcpyAsync(h_scal + first, scal + first, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, stream));
     return sync();

@@ -4,6 +4,11 @@
 #include "solver_handle.hip.h"
 
 int pgo_handle::reduce_to_scal(std::initializer_list<PartRef> parts, int first, bool allreduce_max) {
+  return reduce_parts(parts, scal + first, scal + first, (int)parts.size(), allreduce_max);
+}
+
+// k_finalize of the partial arrays into out[0 .. #parts); several ranks: then the all-reduce of ar[0 .. ar_n), which holds out
+int pgo_handle::reduce_parts(std::initializer_list<PartRef> parts, double* out, double* ar, int ar_n, bool allreduce_max) {
   dev::FinArgs F;
   memset(&F, 0, sizeof F);
   int k = 0;
@@ -21,10 +26,10 @@ int pgo_handle::reduce_to_scal(std::initializer_list<PartRef> parts, int first, 
     ++k;
   }
   F.count = k;
-  F.out = scal + first;
+  F.out = out;
   hipLaunchKernelGGL(dev::k_finalize<>, dim3(1), dim3(dev::WG), 0, stream, F);
   PGOC(check_launch("k_finalize"));
-  if (multi_rank()) PGOC(comm->allreduce(scal + first, k, allreduce_max, stream));
+  if (multi_rank()) PGOC(comm->allreduce(ar, ar_n, allreduce_max, stream));
   return PGO_OK;
 }
 

@@ -25,12 +25,15 @@ int pgo_handle::coarse_factor() {
   A.n_cb = co_ncb;
   A.cap = co_cap;
   A.dwork = co_dwork;
-  hipLaunchKernelGGL(dev::k_coarse_basis<>, dim3((co_nagg + 3) / 4), dim3(256), 0, stream, A);
-  PGOC(check_launch("k_coarse_basis"));
-  HIPC(hipMemsetAsync(co_cap, 0, (size_t)co_Kp * co_Kp * sizeof(double), stream));
-  HIPC(hipMemsetAsync(co_dwork, 0, (size_t)(co_Kp / 32) * 1024 * sizeof(double), stream));
-  hipLaunchKernelGGL(dev::k_coarse_assemble<>, dim3((co_ncb + 3) / 4), dim3(256), 0, stream, A);
-  PGOC(check_launch("k_coarse_assemble"));
+  if (co_multi) PGOC(coarse_assemble_multi());
+  else {
+    hipLaunchKernelGGL(dev::k_coarse_basis<>, dim3((co_nagg + 3) / 4), dim3(256), 0, stream, A);
+    PGOC(check_launch("k_coarse_basis"));
+    HIPC(hipMemsetAsync(co_cap, 0, (size_t)co_Kp * co_Kp * sizeof(double), stream));
+    HIPC(hipMemsetAsync(co_dwork, 0, (size_t)(co_Kp / 32) * 1024 * sizeof(double), stream));
+    hipLaunchKernelGGL(dev::k_coarse_assemble<>, dim3((co_ncb + 3) / 4), dim3(256), 0, stream, A);
+    PGOC(check_launch("k_coarse_assemble"));
+  }
   if (co_Kp > co_K) {
     hipLaunchKernelGGL(dev::k_coarse_pad<>, dim3(1), dim3(32), 0, stream, co_cap, co_dwork, co_K, co_Kp);
     PGOC(check_launch("k_coarse_pad"));
@@ -60,10 +63,64 @@ int pgo_handle::coarse_factor() {
   return check_launch("coarse level probe");
 }
 
+// several ranks: basis planes of every pose, this rank's Galerkin blocks, all-gather, scatter into the dense matrix (which,
+// with its factorisation, is then the same on every rank)
+int pgo_handle::coarse_assemble_multi() {
+  dev::CoarseMArgs M;
+  M.n = S.n_poses;
+  M.lo = S.lo;
+  M.n_loc = S.n_loc;
+  M.agg = co_agg;
+  M.n_agg = co_nagg;
+  M.poses = poses;
+  M.scale = scale;
+  M.live = co_live;
+  M.pb = co_pb;
+  M.hoff = hoff;
+  M.hd = hd;
+  M.d2 = d2;
+  M.inc_col = inc_col;
+  M.cb_i = co_cb_i;
+  M.cb_j = co_cb_j;
+  M.cb_ptr = co_cb_ptr;
+  M.cb_q = co_cb_q;
+  M.cb_row = co_cb_row;
+  M.n_cb = co_ncb;
+  M.vals = co_gvals + (int64_t)comm->rank * co_ncb_max * 9;
+  hipLaunchKernelGGL(dev::k_coarse_basis_m<>, dim3((co_nagg + 3) / 4), dim3(256), 0, stream, M);
+  PGOC(check_launch("k_coarse_basis_m"));
+  HIPC(hipMemsetAsync(co_cap, 0, (size_t)co_Kp * co_Kp * sizeof(double), stream));
+  HIPC(hipMemsetAsync(co_dwork, 0, (size_t)(co_Kp / 32) * 1024 * sizeof(double), stream));
+  if (co_ncb > 0) {
+    hipLaunchKernelGGL(dev::k_coarse_assemble_m<>, dim3((co_ncb + 3) / 4), dim3(256), 0, stream, M);
+    PGOC(check_launch("k_coarse_assemble_m"));
+  }
+  if (comm->allgather_inplace(co_gvals, (int64_t)9 * co_ncb_max, stream) != 0)
+    return fail(PGO_ERR_COMM, "coarse level: all-gather of the Galerkin blocks failed");
+  const int64_t nblk = (int64_t)comm->world * co_ncb_max;
+  if (nblk > 0) {
+    hipLaunchKernelGGL(dev::k_coarse_scatter<>, dim3((unsigned)((9 * nblk + 255) / 256)), dim3(256), 0, stream, (const double*)co_gvals,
+                       (const int32_t*)co_gi, (const int32_t*)co_gj, nblk, co_cap, co_dwork, co_Kp);
+    PGOC(check_launch("k_coarse_scatter"));
+  }
+  return PGO_OK;
+}
+
+// several ranks: r_c = P'r of the own aggregates into the zeroed global vector, and the partial sums of r.z and r.r next to it,
+// all in ONE all-reduce -- afterwards every rank holds the whole r_c and the reduced (r.z, r.r) at co_red + Kp
+int pgo_handle::coarse_restrict_reduce(const double* rz_part, int n_rz, const double* rr_part, int n_rr, const int32_t* done) {
+  const int slots = (co_Kp + 2) / 3;
+  hipLaunchKernelGGL(dev::k_coarse_restrict_m<>, dim3((slots + 3) / 4), dim3(256), 0, stream, (int)S.n_loc, (int)S.lo, co_agg, co_aoff, co_nown,
+                     co_Kp, (const double*)co_pb, (int64_t)S.n_poses, (const double*)r, co_red, done);
+  PGOC(check_launch("k_coarse_restrict_m"));
+  return reduce_parts({{rz_part, n_rz, 0}, {rr_part, n_rr, 0}}, co_red + co_Kp, co_red, co_Kp + 2, false);
+}
+
 int pgo_handle::coarse_solve(double* dot_part, const int32_t* done) {
   const int nb = co_Kp / 32;
-  hipLaunchKernelGGL(dev::k_coarse_restrict<>, dim3((co_nagg + 3) / 4), dim3(256), 0, stream, (int)S.n_loc, co_agg, co_nagg, (const double*)co_pb,
-                     (const double*)r, co_rc, done);
+  if (!co_multi)   // (several ranks: r_c came with the all-reduce, coarse_restrict_reduce)
+    hipLaunchKernelGGL(dev::k_coarse_restrict<>, dim3((co_nagg + 3) / 4), dim3(256), 0, stream, (int)S.n_loc, co_agg, co_nagg, (const double*)co_pb,
+                       (const double*)r, co_rc, done);
   if (co_ainv) {
     hipLaunchKernelGGL(dev::k_coarse_matvec<>, dim3(co_ndot), dim3(256), 0, stream, (const double*)co_ainv, co_Kp, (const double*)co_rc, co_ec,
                        dot_part, (const int32_t*)co_ok, done);
@@ -146,7 +203,21 @@ int pgo_handle::pcg(int* iters, double* rel) {
   } else {
     // two levels: z (= p) of the start-up kernel gets the coarse correction, r.z one more partial
     const int n_rz0 = use_coarse ? g_u1 + co_ndot : g_u1;
-    if (use_coarse) {
+    if (use_coarse && co_multi) {
+      // several ranks: r_c rides in the all-reduce of the start-up sums; the coarse share is added to the reduced r.z once
+      PGOC(coarse_restrict_reduce(part[0], g_u1, part[1], g_u1, nullptr));
+      PGOC(coarse_solve(co_dotp, nullptr));
+      hipLaunchKernelGGL(dev::k_coarse_fin<>, dim3(1), dim3(dev::WG), 0, stream, (const double*)(co_red + co_Kp), (const double*)co_dotp, co_ndot,
+                         scal + 4);
+      PGOC(check_launch("k_coarse_fin"));
+      hipLaunchKernelGGL(dev::k_coarse_prolong_m<>, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((S.n_loc + 255) / 256, 512))), dim3(256), 0,
+                         stream, (int)S.n_loc, (int)S.lo, co_agg, (const double*)co_pb, (int64_t)S.n_poses, (const double*)co_ec, z, p_full,
+                         (const int32_t*)co_ok);
+      PGOC(check_launch("k_coarse_prolong_m"));
+      hipLaunchKernelGGL(dev::k_flag_to_double<>, dim3(1), dim3(1), 0, stream, (const int*)co_ok, scal + 15);
+      PGOC(check_launch("k_flag_to_double"));
+      co_flag_pending = true;
+    } else if (use_coarse) {
       PGOC(coarse_solve(part[0] + g_u1, nullptr));
       hipLaunchKernelGGL(dev::k_coarse_prolong<>, dim3((unsigned)std::min<int64_t>((S.n_loc + 255) / 256, 512)), dim3(256), 0, stream, (int)S.n_loc,
                          co_agg, (const double*)co_pb, (const double*)co_ec, z, p_full + dev::PS * (int64_t)S.lo, (const int32_t*)co_ok);
@@ -156,7 +227,7 @@ int pgo_handle::pcg(int* iters, double* rel) {
       PGOC(check_launch("k_flag_to_double"));
       co_flag_pending = true;
     }
-    PGOC(reduce_to_scal({{part[0], n_rz0, 0}, {part[1], g_u1, 0}}, 4));
+    if (!(use_coarse && co_multi)) PGOC(reduce_to_scal({{part[0], n_rz0, 0}, {part[1], g_u1, 0}}, 4));
     hipLaunchKernelGGL(dev::k_cg_init_fin<>, dim3(1), dim3(1), 0, stream, st, scal + 4, opt.pcg_rtol);
     PGOC(check_launch("k_cg_init_fin"));
     if (!overlap) PGOC(share_gather_vector(p_full));
@@ -206,6 +277,15 @@ int pgo_handle::pcg(int* iters, double* rel) {
     else hipLaunchKernelGGL(dev::k_cg_update1<>, dim3(g_u1), dim3(dev::WG), 0, stream, Vi, par, pap, n_pap, part[1], part[2]);
     PGOC(check_launch("k_cg_update1"));
     if (fused) return PGO_OK;  // its r.z / r.r partials are booked by the next SpMV, or by k_cg_book at the end of the slice
+    if (use_coarse && co_multi) {   // second level, several ranks: r_c in the all-reduce of (r.z, r.r), replicated coarse solve
+      PGOC(coarse_restrict_reduce(part[1], g_u1, part[2], g_u1, &st->done));
+      PGOC(coarse_solve(co_dotp, &st->done));
+      hipLaunchKernelGGL(dev::k_cg_update2cm<>, dim3(g_vec), dim3(dev::WG), 0, stream, V, par, (const double*)(co_red + co_Kp), (const double*)co_dotp,
+                         co_ndot, co_agg, (const double*)co_pb, (int64_t)S.n_poses, (const double*)co_ec);
+      PGOC(check_launch("k_cg_update2cm"));
+      if (!overlap) PGOC(share_gather_vector(p_full));
+      return PGO_OK;
+    }
     if (use_coarse) {   // second level (single rank): e_c, its share of r.z as more partials, prolongation inside the direction update
       PGOC(coarse_solve(part[1] + g_u1, &st->done));
       hipLaunchKernelGGL(dev::k_cg_update2c<>, dim3(g_vec), dim3(dev::WG), 0, stream, V, par, (const double*)part[1], g_u1 + co_ndot,
