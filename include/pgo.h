@@ -379,6 +379,39 @@ int pgo_get_poses(pgo_t* h, double* out_xyt /* N x 3 */);                       
 int pgo_get_switches(pgo_t* h, double* switches /* E */, double* js_or_null /* E x 3 */);   /* [gpu] */
 int pgo_set_poses(pgo_t* h, const double* poses_xyt);                             /* [gpu] */
 
+/* ------------------------------------------------------- pose covariances
+ * ceres::Covariance with a constant parameter block: Sigma = (J'J)^-1 at the handle's CURRENT poses, J the Jacobian of the LM
+ * loop (Huber corrector, DCS scaling; no LM diagonal).  The constant pose has zero blocks.
+ * Blocks are row-major 3x3 in (x, y, theta), symmetric: Sigma_ab is stored as 1/2 (Sigma_ab + Sigma_ba').  METHOD 2: the pose
+ * marginal of the joint (poses, switches) system, at the switches of the latest LM iteration (needs pgo_lm_begin / pgo_solve).
+ * Solved by PCG on the Jacobi-scaled undamped normal equations, 3 x poses_per_pass right-hand sides per pass, with the
+ * handle's preconditioner set up for D'D = 0, plus the rigid-body coarse level on graphs of >= 512 poses (built at the first
+ * call where the handle has none; the LM loop keeps running without it).  A column stops when its TRUE residual
+ * ||S e - A x|| <= rtol ||S e||: where the PCG recurrence drifts from it, the column restarts from x with the true residual
+ * while that lowers it; a true residual that stops falling above rtol is accepted up to 1e-5 (the double-precision floor
+ * of an ill-conditioned system, reported in max_rel_residual), above that it is PGO_ERR_NUMERIC.  The LM state is left as
+ * it was: pgo_lm_step afterwards gives bitwise the records and poses it gives without the call.
+ * Errors: PGO_ERR_UNSUPPORTED for world > 1, fixed_pose = -1, info_weighting = 1 (not accurate enough yet) and batched
+ * handles; PGO_ERR_INVALID_ARG for a bad index or a null pointer (duplicate indices are allowed); PGO_ERR_NUMERIC for a
+ * non-finite pose or Jacobian, a pose without edges, a PCG breakdown, a stalled true residual or max_iters reached
+ * (pgo_last_error names the pose).                                                                                       */
+typedef struct pgo_covariance_options {
+  double  rtol;             /* 1e-10: per column, TRUE residual ||b - A x|| <= rtol ||b||                              */
+  int32_t max_iters;        /* 20000: PCG iterations per pass before PGO_ERR_NUMERIC                                   */
+  int32_t poses_per_pass;   /* 8: columns per pass = 3 x this (1..16)                                                  */
+  int32_t cross;            /* 0: out = n x 9 diagonal blocks; 1: out = the (3n x 3n) matrix of all blocks, row-major  */
+  int32_t _pad;
+} pgo_covariance_options;
+typedef struct pgo_covariance_report {
+  int32_t columns, passes, pcg_iters_max, pcg_iters_total;
+  double  max_rel_residual;  /* max over columns of the TRUE ||S e - A x|| / ||S e|| (<= max(rtol, floor) on success)      */
+  double  seconds;
+} pgo_covariance_report;
+void pgo_covariance_options_default(pgo_covariance_options* o);                            /* [host] */
+int  pgo_pose_covariance(pgo_t* h, int32_t n, const int32_t* poses /* caller's numbering */,
+                         const pgo_covariance_options* opt_or_null, double* out,
+                         pgo_covariance_report* report_or_null);                           /* [gpu]  */
+
 /* ------------------------------------------------ kernel-level entry points
  * Used by the parity tests and by bench.py's roofline leg: each launches exactly
  * one kind of kernel `reps` times on the handle's stream, brackets the launches
@@ -425,6 +458,8 @@ int pgo_debug_normal_eq(pgo_t* h, double* g_or_null, double* hdiag_or_null);    
  *   "pad_tiles"          0 = large graphs keep the dense incidence layout (default: every row tile padded to 256 incidence
  *                        slots of its own, so that K3 finds a tile's blocks from its number alone; same results);
  *                        1 = that layout and its product kernel (k_spmv_1) on a graph of any size
+ *   "cov_poses_per_pass" 1..16 = overrides pgo_covariance_options.poses_per_pass of every pgo_pose_covariance call (read per call;
+ *                        the results agree with every value up to the solver tolerance)
  * Unknown name: PGO_ERR_INVALID_ARG.                                                                              */
 int pgo_debug_set_knob(const char* name, long long value);                        /* [host] */
 /* sharding plan of a graph over `world` ranks: for rank r, rows [lo, hi) and the

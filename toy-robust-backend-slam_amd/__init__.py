@@ -21,7 +21,8 @@ import numpy as np
 from . import _build
 
 __all__ = ["PgoError", "Options", "Summary", "IterRecord", "ReadG2O", "Graph", "Solver", "Batch", "Comm", "lib", "build",
-           "HandleInfo", "synth_manhattan", "solve_batch", "shard_plan", "shard_halo", "pose_order", "set_knob", "KernelStats", "EXPORTS", "TERMINATION"]
+           "HandleInfo", "synth_manhattan", "solve_batch", "shard_plan", "shard_halo", "pose_order", "set_knob", "KernelStats", "EXPORTS", "TERMINATION",
+           "CovarianceOptions", "CovarianceReport"]
 
 EDGE_ODOMETRY, EDGE_CLOSURE, EDGE_BOGUS = 0, 1, 2
 TERMINATION = {1: "CONVERGENCE_FTOL", 2: "CONVERGENCE_GTOL", 3: "CONVERGENCE_PTOL", 4: "NO_CONVERGENCE",
@@ -44,6 +45,7 @@ EXPORTS = [
     "pgo_bench_eval", "pgo_bench_assemble", "pgo_bench_spmv", "pgo_bench_precond", "pgo_debug_precond", "pgo_debug_spmv", "pgo_debug_system_spmv", "pgo_debug_normal_eq",
     "pgo_debug_set_knob",
     "pgo_shard_plan", "pgo_shard_halo", "pgo_pose_order",
+    "pgo_covariance_options_default", "pgo_pose_covariance",
 ]
 
 
@@ -113,6 +115,28 @@ class HandleInfo(C.Structure):
 
 class KernelStats(C.Structure):
     _fields_ = [("ms_avg", C.c_double), ("algorithmic_bytes", C.c_double), ("units", C.c_int64)]
+
+
+class CovarianceOptions(C.Structure):
+    """mirror of pgo_covariance_options (defaults: pgo_covariance_options_default)"""
+    _fields_ = [("rtol", C.c_double), ("max_iters", C.c_int32), ("poses_per_pass", C.c_int32), ("cross", C.c_int32),
+                ("_pad", C.c_int32)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().pgo_covariance_options_default(C.byref(self))
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError("unknown covariance option " + k)
+            setattr(self, k, v)
+
+
+class CovarianceReport(C.Structure):
+    _fields_ = [("columns", C.c_int32), ("passes", C.c_int32), ("pcg_iters_max", C.c_int32), ("pcg_iters_total", C.c_int32),
+                ("max_rel_residual", C.c_double), ("seconds", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 _LIB = None
@@ -214,6 +238,9 @@ def lib():
                                  C.POINTER(C.c_int64)]
     L.pgo_pose_order.argtypes = [C.c_int32, C.c_int32, ip, ip, C.c_int32, ip]
     L.pgo_debug_set_knob.argtypes = [C.c_char_p, C.c_longlong]
+    L.pgo_covariance_options_default.argtypes = [C.POINTER(CovarianceOptions)]
+    L.pgo_covariance_options_default.restype = None
+    L.pgo_pose_covariance.argtypes = [vp, C.c_int32, ip, C.POINTER(CovarianceOptions), dp, C.POINTER(CovarianceReport)]
     _LIB = L
     return L
 
@@ -559,6 +586,17 @@ class Solver:
     def set_poses(self, poses):
         p = np.ascontiguousarray(poses, np.float64)
         _check(lib().pgo_set_poses(self._h, _dp(p)))
+
+    def covariance(self, poses, cross=False, **opts):
+        """ceres::Covariance at the current poses (pgo_pose_covariance): poses = indices in the caller's numbering.
+        Returns ((n, 3, 3) diagonal blocks, or the (3n, 3n) matrix with cross=True), report dict)."""
+        idx = np.ascontiguousarray(np.asarray(poses, np.int64).reshape(-1), np.int32)
+        n = idx.size
+        o = CovarianceOptions(cross=int(bool(cross)), **opts)
+        out = np.zeros((3 * n, 3 * n) if cross else (n, 3, 3))
+        rep = CovarianceReport()
+        _check(lib().pgo_pose_covariance(self._h, n, _ip(idx), C.byref(o), _dp(out), C.byref(rep)))
+        return out, rep.as_dict()
 
     def write_back(self):
         """poses are optimised IN PLACE in Node::p in the reference (main.cpp:99,163)"""

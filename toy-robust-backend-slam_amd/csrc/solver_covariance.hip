@@ -1,0 +1,420 @@
+// Pose marginal covariances (ceres::Covariance with a constant parameter block): Sigma = (J'J)^-1 at the handle's current
+// poses, by PCG on 3 x (poses per pass) right-hand sides at once (covariance.hip.h).  The system is the undamped one of the LM
+// loop, A = S J'J S + I_fixed (k_prepare at radius = infinity), right-hand side S e_k, Sigma = S X.  The preconditioner is the
+// handle's own (one level + the coarse level where the handle has it), set up for D'D = 0 and applied column by column.
+#include "solver_handle.hip.h"
+#include "covariance.hip.h"
+
+namespace {
+
+// largest true relative residual |S e - A x| / |S e| a column may end with when residual replacement no longer lowers it
+// (the double-precision floor of an ill-conditioned system: MIT's columns stop near 2e-7 at rtol 1e-10, INTEL with information
+// weighting near 1.5e-6)
+constexpr double COV_RES_FLOOR_MAX = 1e-5;
+
+struct DevScratch {   // buffers of one call, freed on every return path
+  std::vector<void*> p;
+  ~DevScratch() {
+    for (void* q : p) (void)hipFree(q);
+  }
+  template <class T>
+  int alloc(T** out, int64_t n) {
+    void* q = nullptr;
+    hipError_t e = hipMalloc(&q, (size_t)std::max<int64_t>(n, 1) * sizeof(T));
+    if (e != hipSuccess) return fail(PGO_ERR_NOMEM, std::string("pgo_pose_covariance: hipMalloc: ") + hipGetErrorString(e));
+    p.push_back(q);
+    *out = (T*)q;
+    return PGO_OK;
+  }
+};
+
+// z = M^-1 b with the handle's preconditioner, through the PCG start-up kernel the LM loop runs (it also overwrites the LM
+// loop's per-solve vectors y, r and the gather vector, which every PCG solve initialises afresh)
+int precond_column(pgo_handle* h, const double* b, double* zc) {
+  double* z_saved = h->z;
+  h->z = zc;
+  const dev::CgVec V = h->cg_vec();
+  if (h->chain_len) {
+    h->launch_cg_init_chain(b, h->part[0], h->part[1]);
+  } else if (h->grp_B > 1) {
+    dev::GroupPre GP;
+    GP.ginv = h->ginv;
+    GP.B = h->grp_B;
+    GP.nb = h->grp_nb;
+    GP.nb_pad = h->grp_pad;
+    GP.n_groups = h->n_groups;
+    hipLaunchKernelGGL(dev::k_cg_init_g<>, dim3(h->g_grp), dim3(dev::WG), 0, h->stream, V, GP, b, h->part[0], h->part[1]);
+  } else {
+    hipLaunchKernelGGL(dev::k_cg_init<>, dim3(h->g_vec), dim3(dev::WG), 0, h->stream, V, b, h->part[0], h->part[1]);
+  }
+  int st = h->check_launch("k_cg_init (covariance)");
+  if (st == PGO_OK && h->use_coarse) {   // the second level's share: restriction of r (= b), coarse solve, prolongation into z
+    st = h->coarse_solve(h->part[3], nullptr);
+    if (st == PGO_OK) {
+      hipLaunchKernelGGL(dev::k_coarse_prolong<>, dim3((unsigned)std::min<int64_t>((h->S.n_loc + 255) / 256, 512)), dim3(256), 0, h->stream,
+                         (int)h->S.n_loc, h->co_agg, (const double*)h->co_pb, (const double*)h->co_ec, zc, (double*)nullptr, (const int32_t*)h->co_ok);
+      st = h->check_launch("k_coarse_prolong (covariance)");
+    }
+  }
+  h->z = z_saved;
+  return st;
+}
+
+int spmm(pgo_handle* h, int m, int64_t ld, const double* p, double* y, double* part, int g) {
+  for (int c0 = 0; c0 < m; c0 += dev::COV_MC) {
+    dev::SpmmArgs A;
+    A.inc_ptr = h->inc_ptr;
+    A.inc_col = h->inc_col;
+    A.hoff = h->hoff;
+    A.hd = h->hd;
+    A.d2 = h->d2;
+    A.n = h->S.n_loc;
+    A.c0 = c0;
+    A.nc = std::min(dev::COV_MC, m - c0);
+    A.ld = ld;
+    A.p = p;
+    A.y = y;
+    A.part = part;
+    if (A.nc <= 3) hipLaunchKernelGGL(dev::k_spmm<3>, dim3(g), dim3(dev::WG), 0, h->stream, A);
+    else if (A.nc <= 6) hipLaunchKernelGGL(dev::k_spmm<6>, dim3(g), dim3(dev::WG), 0, h->stream, A);
+    else if (A.nc <= 12) hipLaunchKernelGGL(dev::k_spmm<12>, dim3(g), dim3(dev::WG), 0, h->stream, A);
+    else hipLaunchKernelGGL(dev::k_spmm<24>, dim3(g), dim3(dev::WG), 0, h->stream, A);
+    PGOC(h->check_launch("k_spmm"));
+  }
+  return PGO_OK;
+}
+
+// The rigid-body coarse level for handles that were created without it (direct solves, the inexact mode, pcg_coarse_poses = 0)
+// on graphs of >= 512 poses: its structure is built once, with the aggregate size of the auto rule, and used by covariance
+// calls only -- use_coarse stays off for the LM loop, and what coarse_setup changes in the LM loop's choices is put back.
+int coarse_for_covariance(pgo_handle* h) {
+  if (h->use_coarse || h->co_cov_ready || h->S.n_loc < 512) return PGO_OK;
+  const int64_t NL = h->S.n_loc;
+  int want = NL <= 8192 ? 16 : 64;
+  while (3 * ((NL + want - 1) / want) + 1 > COARSE_MAX_RANK) want *= 2;
+  const int saved_want = h->opt.pcg_coarse_poses;
+  const bool solo = h->solo, fused_p = h->fused_p, use_sr = h->use_sr, dl_possible = h->dl_possible;
+  h->opt.pcg_coarse_poses = want;
+  const int st = h->coarse_setup(0, nullptr, nullptr);   // (one rank: the edge lists are not read)
+  h->opt.pcg_coarse_poses = saved_want;
+  h->solo = solo;
+  h->fused_p = fused_p;
+  h->use_sr = use_sr;
+  h->dl_possible = dl_possible;
+  h->co_cov_ready = st == PGO_OK && h->use_coarse;
+  h->use_coarse = false;
+  return st;
+}
+
+// the level is on for the duration of a covariance call only
+struct CoarseOn {
+  pgo_handle* h;
+  bool was;
+  explicit CoarseOn(pgo_handle* hh) : h(hh), was(hh->use_coarse) {
+    if (h->co_cov_ready) h->use_coarse = true;
+  }
+  ~CoarseOn() { h->use_coarse = was; }
+};
+
+// the undamped system at the current poses: linearisation (when the LM loop's is not current), METHOD 2's switch
+// elimination without damping, D'D = 0 and the preconditioner for it.  Afterwards the LM loop's own set-up is redone by its
+// next iteration from unchanged inputs (prepare_system; METHOD 2: refresh_switch_system), so its results do not change.
+int setup_system(pgo_handle* h) {
+  if (!h->lin_valid) {   // (not for METHOD 2: refused earlier) Jacobi scales and J'J at the current poses, as pgo_lm_begin
+    hipLaunchKernelGGL(dev::k_jacobi_scale<>, dim3(h->g_rows), dim3(dev::WG), 0, h->stream, h->hd, h->S.n_loc, h->S.lo, h->fixed_internal, 0, h->scale,
+                       (const uint8_t*)h->fixed_mask);
+    PGOC(h->check_launch("k_jacobi_scale"));
+    PGOC(h->linearize(false));
+    if (h->opt.jacobi_scaling) {
+      hipLaunchKernelGGL(dev::k_jacobi_scale<>, dim3(h->g_rows), dim3(dev::WG), 0, h->stream, h->hd, h->S.n_loc, h->S.lo, h->fixed_internal, 1,
+                         h->scale, (const uint8_t*)h->fixed_mask);
+      PGOC(h->check_launch("k_jacobi_scale"));
+      PGOC(h->linearize(true));
+    }
+  }
+  const double radius_saved = h->radius;
+  h->radius = std::numeric_limits<double>::infinity();
+  int st = PGO_OK;
+  if (h->has_sw) {   // switches eliminated per edge with zero damping: the pose marginal of the joint system
+    const int g_sw = std::min(std::max(1, (h->S.n_edges_local + dev::WG - 1) / dev::WG), 1024);
+    hipLaunchKernelGGL(dev::k_switch_prepare<>, dim3(g_sw), dim3(dev::WG), 0, h->stream, h->switch_arrays(), (const double*)h->jr, h->radius,
+                       h->opt.min_lm_diagonal, h->opt.max_lm_diagonal, h->part[2], h->part[3]);
+    st = h->check_launch("k_switch_prepare (covariance)");
+    if (st == PGO_OK) st = h->assemble_enqueue();
+    h->sw_fresh = false;   // the next LM iteration re-assembles for its radius (refresh_switch_system)
+  }
+  if (st == PGO_OK) st = h->prepare_system();
+  if (st == PGO_OK && h->direct) st = h->prepare_preconditioner();   // (a handle on the direct solve does not set it up per iteration)
+  h->radius = radius_saved;
+  return st;
+}
+
+}  // namespace
+
+extern "C" {
+
+void pgo_covariance_options_default(pgo_covariance_options* o) {
+  if (!o) return;
+  memset(o, 0, sizeof *o);
+  o->rtol = 1e-10;
+  o->max_iters = 20000;
+  o->poses_per_pass = 8;
+  o->cross = 0;
+}
+
+int pgo_pose_covariance(pgo_t* h, int32_t n, const int32_t* poses, const pgo_covariance_options* opt_or_null, double* out,
+                        pgo_covariance_report* report) {
+  const double t0 = wall_s();
+  if (!h) return fail(PGO_ERR_INVALID_ARG, "pgo_pose_covariance: null handle");
+  if (n < 0 || (n > 0 && (!poses || !out))) return fail(PGO_ERR_INVALID_ARG, "pgo_pose_covariance: bad argument");
+  pgo_covariance_options o;
+  if (opt_or_null) o = *opt_or_null;
+  else pgo_covariance_options_default(&o);
+  const long long kp = knob("cov_poses_per_pass");
+  if (kp >= 0) o.poses_per_pass = (int32_t)kp;
+  if (!(o.rtol > 0.0) || !std::isfinite(o.rtol) || o.max_iters < 1 || o.poses_per_pass < 1 || o.poses_per_pass > dev::COV_MAX_COLS / 3)
+    return fail(PGO_ERR_INVALID_ARG, "pgo_pose_covariance: rtol > 0, max_iters >= 1 and poses_per_pass in 1..16 required");
+  if ((h->comm && h->comm->world > 1) || h->co_multi) return fail(PGO_ERR_UNSUPPORTED, "pgo_pose_covariance: one rank only");
+  if (h->batch_mode) return fail(PGO_ERR_UNSUPPORTED, "pgo_pose_covariance: not on batched handles");
+  // information weighting: even the columns whose true residual reaches 1e-5 differ from a sparse direct inverse by ~1e-3 on
+  // INTEL (others stall at 2e-5) -- refused rather than returning blocks of that quality
+  if (h->info_mode) return fail(PGO_ERR_UNSUPPORTED, "pgo_pose_covariance: not available with info_weighting = 1");
+  if (h->fixed_internal < 0)
+    return fail(PGO_ERR_UNSUPPORTED, "pgo_pose_covariance: fixed_pose = -1 leaves the gauge free (J'J is singular)");
+  const int64_t N = h->S.n_poses;
+  for (int32_t k = 0; k < n; ++k)
+    if (poses[k] < 0 || poses[k] >= N)
+      return fail(PGO_ERR_INVALID_ARG, "pgo_pose_covariance: pose index " + std::to_string(poses[k]) + " (entry " + std::to_string(k) + ") out of range");
+  if (h->has_sw && !h->lin_valid)
+    return fail(PGO_ERR_INVALID_ARG, "pgo_pose_covariance: METHOD 2 needs the switches of a solve: call pgo_lm_begin or pgo_solve first");
+  if (report) memset(report, 0, sizeof *report);
+  if (n == 0) return PGO_OK;
+  HIPC(hipSetDevice(h->device));
+  auto internal = [&](int64_t i) -> int64_t { return h->perm.empty() ? i : (int64_t)h->perm[i]; };
+  auto caller = [&](int64_t k) -> int64_t {   // internal row -> caller's pose
+    if (h->perm.empty()) return k;
+    for (int64_t i = 0; i < N; ++i)
+      if (h->perm[i] == k) return i;
+    return k;
+  };
+  {   // a non-finite pose is named before anything is evaluated at it
+    std::vector<double> x((size_t)3 * N);
+    HIPC(hipMemcpyAsync(x.data(), h->poses, x.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PGOC(h->sync());
+    for (int64_t k = 0; k < N; ++k)
+      if (!std::isfinite(x[3 * k]) || !std::isfinite(x[3 * k + 1]) || !std::isfinite(x[3 * k + 2]))
+        return fail(PGO_ERR_NUMERIC, "pgo_pose_covariance: pose " + std::to_string(caller(k)) + " is not finite");
+  }
+  PGOC(coarse_for_covariance(h));
+  CoarseOn coarse_on(h);
+  PGOC(setup_system(h));
+
+  const int64_t n3 = 3 * N, ld = n3;
+  const int g = std::min(std::max(1, (int)((n3 + dev::WG - 1) / dev::WG)), 1024);     // vector kernels
+  const int gs = std::min(std::max(1, (int)((N + dev::WG - 1) / dev::WG)), 1024);     // k_spmm
+  const int gp = std::max(g, gs);
+  {   // every row of A needs a positive diagonal: a pose without edges has none
+    DevScratch tmp;
+    int32_t* bad = nullptr;
+    PGOC(tmp.alloc(&bad, gs));
+    hipLaunchKernelGGL(dev::k_cov_check_rows<>, dim3(gs), dim3(dev::WG), 0, h->stream, (int)N, (const double*)h->hd, (const double*)h->d2, bad);
+    PGOC(h->check_launch("k_cov_check_rows"));
+    std::vector<int32_t> hb((size_t)gs);
+    HIPC(hipMemcpyAsync(hb.data(), bad, hb.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    PGOC(h->sync());
+    const int32_t first = *std::min_element(hb.begin(), hb.end());
+    if (first < N)
+      return fail(PGO_ERR_NUMERIC, "pgo_pose_covariance: pose " + std::to_string(caller(first)) +
+                                       " has a singular diagonal block in J'J (no edge constrains it, or a non-finite Jacobian)");
+  }
+
+  const int kpp = o.poses_per_pass;
+  const int mcap = 3 * std::min<int64_t>(kpp, n);
+  DevScratch buf;
+  double *X, *R, *Z, *P, *AP, *part_a, *part_b, *gath;
+  dev::CovCol* cs;
+  int32_t *rows, *rows_out;
+  const int n_out_max = o.cross ? 3 * n : mcap;
+  PGOC(buf.alloc(&X, mcap * ld));
+  PGOC(buf.alloc(&R, mcap * ld));
+  PGOC(buf.alloc(&Z, mcap * ld));
+  PGOC(buf.alloc(&P, mcap * ld));
+  PGOC(buf.alloc(&AP, mcap * ld));
+  PGOC(buf.alloc(&part_a, (int64_t)mcap * gp));
+  PGOC(buf.alloc(&part_b, (int64_t)mcap * gp));
+  PGOC(buf.alloc(&cs, mcap));
+  PGOC(buf.alloc(&rows, mcap));
+  PGOC(buf.alloc(&rows_out, n_out_max));
+  PGOC(buf.alloc(&gath, (int64_t)mcap * n_out_max));
+  uint8_t* rmask = nullptr;
+  PGOC(buf.alloc(&rmask, mcap));
+  if (o.cross) {
+    std::vector<int32_t> ro((size_t)3 * n);
+    for (int32_t j = 0; j < n; ++j)
+      for (int a = 0; a < 3; ++a) ro[3 * j + a] = (int32_t)(3 * internal(poses[j]) + a);
+    HIPC(hipMemcpyAsync(rows_out, ro.data(), ro.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    PGOC(h->sync());
+  }
+  const int every = std::max(1, h->opt.pcg_check_every);
+  std::vector<dev::CovCol> hc((size_t)mcap);
+  std::vector<double> hg, hpart;
+  int passes = 0, it_max = 0;
+  int64_t it_total = 0;
+  double rel_max = 0.0;
+  for (int32_t j0 = 0; j0 < n; j0 += kpp) {
+    const int k = (int)std::min<int64_t>(kpp, n - j0), m = 3 * k;
+    std::vector<int32_t> rr((size_t)m);
+    for (int j = 0; j < k; ++j)
+      for (int a = 0; a < 3; ++a) rr[3 * j + a] = (int32_t)(3 * internal(poses[j0 + j]) + a);
+    HIPC(hipMemcpyAsync(rows, rr.data(), rr.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    if (!o.cross) HIPC(hipMemcpyAsync(rows_out, rr.data(), rr.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    // start: X = 0, R = B, Z = M^-1 R, P = Z
+    std::vector<uint8_t> hdone((size_t)m, 0);   // columns known stopped at the latest host check: no preconditioner apply
+    auto precond_open = [&]() -> int {
+      for (int c = 0; c < m; ++c)
+        if (!hdone[c]) PGOC(precond_column(h, R + c * ld, Z + c * ld));
+      return PGO_OK;
+    };
+    hipLaunchKernelGGL(dev::k_cov_rhs<>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, (const int32_t*)rows, (const double*)h->scale, X, R, P, part_a);
+    PGOC(h->check_launch("k_cov_rhs"));
+    PGOC(precond_open());
+    // (k_cov_dot skips done columns: cs must read "running" before the start kernel has written it)
+    HIPC(hipMemsetAsync(cs, 0, (size_t)m * sizeof(dev::CovCol), h->stream));
+    hipLaunchKernelGGL(dev::k_cov_dot<>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, (const double*)R, (const double*)Z, (const dev::CovCol*)cs, part_b);
+    hipLaunchKernelGGL(dev::k_cov_start<>, dim3(m), dim3(dev::WG), 0, h->stream, cs, (const double*)part_a, (const double*)part_b, g, o.rtol);
+    hipLaunchKernelGGL(dev::k_cov_pupdate<>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, (const dev::CovCol*)cs, (const double*)Z, P);
+    PGOC(h->check_launch("covariance PCG start"));
+    int it = 0;
+    std::vector<double> res_prev((size_t)m, std::numeric_limits<double>::infinity()), res((size_t)m, 0.0);
+    while (true) {
+      // PCG until every column has stopped on its recurrence residual
+      while (true) {
+        const int chunk = std::min(every, o.max_iters - it);
+        for (int s = 0; s < chunk; ++s) {
+          PGOC(spmm(h, m, ld, P, AP, part_a, gs));
+          hipLaunchKernelGGL(dev::k_cov_alpha<>, dim3(m), dim3(dev::WG), 0, h->stream, cs, (const double*)part_a, gs);
+          hipLaunchKernelGGL(dev::k_cov_update1<>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, (const dev::CovCol*)cs, X, R, (const double*)P,
+                             (const double*)AP, part_a);
+          PGOC(h->check_launch("k_cov_update1"));
+          PGOC(precond_open());
+          hipLaunchKernelGGL(dev::k_cov_dot<>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, (const double*)R, (const double*)Z, (const dev::CovCol*)cs,
+                             part_b);
+          hipLaunchKernelGGL(dev::k_cov_beta<>, dim3(m), dim3(dev::WG), 0, h->stream, cs, (const double*)part_a, (const double*)part_b, g);
+          hipLaunchKernelGGL(dev::k_cov_pupdate<>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, (const dev::CovCol*)cs, (const double*)Z, P);
+          PGOC(h->check_launch("covariance PCG iteration"));
+        }
+        it += chunk;
+        HIPC(hipMemcpyAsync(hc.data(), cs, (size_t)m * sizeof(dev::CovCol), hipMemcpyDeviceToHost, h->stream));
+        PGOC(h->sync());
+        bool all = true;
+        for (int c = 0; c < m; ++c) {
+          if (hc[c].done >= 2)
+            return fail(PGO_ERR_NUMERIC, "pgo_pose_covariance: PCG breakdown on column " + std::to_string(c % 3) + " of pose " +
+                                             std::to_string(poses[j0 + c / 3]) + (hc[c].done == 2 ? " (p'Ap <= 0)" : " (r'z <= 0)"));
+          hdone[c] = hc[c].done == 1;
+          all = all && hdone[c];
+        }
+        if (all) break;
+        if (it >= o.max_iters) {
+          for (int c = 0; c < m; ++c)
+            if (!hc[c].done)
+              return fail(PGO_ERR_NUMERIC, "pgo_pose_covariance: PCG reached max_iters = " + std::to_string(o.max_iters) + " on pose " +
+                                               std::to_string(poses[j0 + c / 3]) + " (relative residual " +
+                                               std::to_string(std::sqrt(hc[c].rr / hc[c].bb)) + ")");
+        }
+      }
+      // the TRUE residual |S e - A X| / |S e| of every column (one more product): the recurrence drifts from it on
+      // ill-conditioned systems.  Columns above rtol restart from X with the true residual (residual replacement) as long
+      // as that lowers it by 10 % or more.  Once it no longer does, the column has reached what double precision allows for this
+      // system: accepted when that floor is <= COV_RES_FLOOR_MAX (reported in max_rel_residual), else PGO_ERR_NUMERIC.
+      PGOC(spmm(h, m, ld, X, AP, part_a, gs));
+      hipLaunchKernelGGL(dev::k_cov_resid<>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, (const int32_t*)rows, (const double*)h->scale,
+                         (const double*)AP, part_b);
+      PGOC(h->check_launch("k_cov_resid"));
+      hpart.resize((size_t)m * g);
+      HIPC(hipMemcpyAsync(hpart.data(), part_b, hpart.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      PGOC(h->sync());
+      std::vector<uint8_t> mask((size_t)m, 0);
+      bool any = false;
+      for (int c = 0; c < m; ++c) {
+        double s = 0.0;
+        for (int b = 0; b < g; ++b) s += hpart[(size_t)c * g + b];
+        res[c] = hc[c].bb > 0.0 ? std::sqrt(s / hc[c].bb) : 0.0;
+        if (!(res[c] <= o.rtol)) {
+          if (!(res[c] <= 0.9 * res_prev[c]) || it >= o.max_iters) {   // no further gain from a replacement
+            if (res[c] <= COV_RES_FLOOR_MAX) continue;
+            char msg[200];
+            snprintf(msg, sizeof msg, "pgo_pose_covariance: the true residual of pose %d stalls at %.3e relative (rtol %.1e)",
+                     (int)poses[j0 + c / 3], res[c], o.rtol);
+            return fail(PGO_ERR_NUMERIC, msg);
+          }
+          mask[c] = 1;
+          hdone[c] = 0;
+          any = true;
+        }
+      }
+      if (!any) break;
+      res_prev = res;
+      HIPC(hipMemcpyAsync(rmask, mask.data(), (size_t)m, hipMemcpyHostToDevice, h->stream));
+      hipLaunchKernelGGL(dev::k_cov_replace<>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, (const int32_t*)rows, (const double*)h->scale,
+                         (const double*)AP, R, (const uint8_t*)rmask);
+      hipLaunchKernelGGL(dev::k_cov_reopen<>, dim3(1), dim3(64), 0, h->stream, cs, (const uint8_t*)rmask, m);
+      PGOC(h->check_launch("k_cov_replace"));
+      PGOC(precond_open());
+      hipLaunchKernelGGL(dev::k_cov_dot<>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, (const double*)R, (const double*)Z, (const dev::CovCol*)cs, part_b);
+      hipLaunchKernelGGL(dev::k_cov_restart<>, dim3(m), dim3(dev::WG), 0, h->stream, cs, (const double*)part_b, g, (const uint8_t*)rmask);
+      hipLaunchKernelGGL(dev::k_cov_pupdate<>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, (const dev::CovCol*)cs, (const double*)Z, P);
+      PGOC(h->check_launch("covariance PCG restart"));
+      PGOC(h->sync());   // (mask is read by the kernels above)
+    }
+    for (int c = 0; c < m; ++c) {
+      it_max = std::max(it_max, hc[c].iters);
+      it_total += hc[c].iters;
+      rel_max = std::max(rel_max, res[c]);
+    }
+    const int n_out = o.cross ? 3 * n : m;
+    hipLaunchKernelGGL(dev::k_cov_gather<>, dim3((unsigned)(((int64_t)m * n_out + 255) / 256)), dim3(256), 0, h->stream, m, ld, (const double*)X,
+                       (const double*)h->scale, (const int32_t*)rows_out, n_out, gath);
+    PGOC(h->check_launch("k_cov_gather"));
+    hg.resize((size_t)m * n_out);
+    HIPC(hipMemcpyAsync(hg.data(), gath, hg.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PGOC(h->sync());
+    // column (pose j0 + jc, component b), row entry i of rows_out
+    if (o.cross) {
+      const int64_t W = 3 * (int64_t)n;
+      for (int c = 0; c < m; ++c)
+        for (int64_t i = 0; i < W; ++i) out[i * W + 3 * (int64_t)j0 + c] = hg[(size_t)c * n_out + i];
+    } else {
+      for (int jc = 0; jc < k; ++jc)
+        for (int a = 0; a < 3; ++a)
+          for (int b = 0; b < 3; ++b) out[9 * (int64_t)(j0 + jc) + 3 * a + b] = hg[(size_t)(3 * jc + b) * n_out + 3 * jc + a];
+    }
+    ++passes;
+  }
+  // symmetric blocks: 1/2 (Sigma_ab + Sigma_ba')
+  if (o.cross) {
+    const int64_t W = 3 * (int64_t)n;
+    for (int64_t i = 0; i < W; ++i)
+      for (int64_t j = i + 1; j < W; ++j) {
+        const double v = 0.5 * (out[i * W + j] + out[j * W + i]);
+        out[i * W + j] = out[j * W + i] = v;
+      }
+  } else {
+    for (int32_t j = 0; j < n; ++j) {
+      double* B = out + 9 * (int64_t)j;
+      for (int a = 0; a < 3; ++a)
+        for (int b = a + 1; b < 3; ++b) B[3 * a + b] = B[3 * b + a] = 0.5 * (B[3 * a + b] + B[3 * b + a]);
+    }
+  }
+  if (report) {
+    report->columns = 3 * n;
+    report->passes = passes;
+    report->pcg_iters_max = it_max;
+    report->pcg_iters_total = (int32_t)std::min<int64_t>(it_total, INT32_MAX);
+    report->max_rel_residual = rel_max;
+    report->seconds = wall_s() - t0;
+  }
+  return PGO_OK;
+}
+
+}  // extern "C"

@@ -140,6 +140,7 @@ struct pgo_handle {
   int co_ndead = 0;
   bool co_flag_pending = false;   // pcg() left co_ok in scal[15] for the host fetch of lm_iteration_tail
   int co_off_iters = 0;        // LM iterations whose PCG solve found the level switched off (co_ok = 0)
+  bool co_cov_ready = false;   // the level was built for pgo_pose_covariance only (solver_covariance.hip): the LM loop runs without it
   int co_ndot = 0;             // partials of r_c . e_c appended to the r.z partials
   int coarse_solve(double* dot_part, const int32_t* done);   // e_c = (P'(H + D'D)P)^-1 P' r  (+ partials of r_c . e_c)
   // several ranks (coarse.hip.h, "several ranks"): replicated coarse problem, aggregates numbered globally
