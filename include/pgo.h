@@ -215,6 +215,41 @@ typedef struct pgo_options {
 
 void pgo_options_default(pgo_options* o);                                  /* [host] */
 
+/* ------------------------------------------------------------ robust losses
+ * Ceres 2.x LossFunction semantics.  s = |e|^2 of one residual block: after the DCS scaling (METHOD 1) or the switch
+ * (METHOD 2: s = |s_sw e|^2), and after whitening when info_weighting = 1.  The block's cost is 1/2 rho(s).  Every loss
+ * below has rho'' <= 0, so Ceres' Corrector reduces to scaling the block's residual and Jacobian rows (and, METHOD 2,
+ * d e / d s) by sqrt(rho'(s)).  Every loss has rho(0) = 0 and rho'(0) = 1.  DBL_MIN = 2.2250738585072014e-308.
+ *
+ *   type                  parameters          rho(s)                      rho'(s)                     rho''(s)
+ *   PGO_LOSS_TRIVIAL      (Ceres' NULL loss)  s                           1                           0
+ *   PGO_LOSS_HUBER        b = a^2             s <= b: s                   1                           0
+ *                                             s >  b: 2 a sqrt(s) - b     max(DBL_MIN, a / sqrt(s))   -rho' / (2 s)
+ *   PGO_LOSS_SOFTLONE     b = a^2, c = 1/b    2 b (sqrt(1 + c s) - 1)     max(DBL_MIN, 1/sqrt(1+cs))  -c rho' / (2 (1 + c s))
+ *   PGO_LOSS_CAUCHY       b = a^2, c = 1/b    b log(1 + c s)              max(DBL_MIN, 1 / (1 + c s)) -c / (1 + c s)^2
+ *   PGO_LOSS_ARCTAN       b = 1/a^2           a atan2(s, a)               max(DBL_MIN, 1/(1 + b s^2)) -2 b s / (1 + b s^2)^2
+ *   PGO_LOSS_TUKEY        v = 1 - s/a^2       s <= a^2: a^2/3 (1 - v^3)   v^2                         -2 v / a^2
+ *                                             s >  a^2: a^2/3             0                           0
+ *
+ * Under Tukey a block beyond a contributes a constant cost and zero residual and Jacobian rows, as in Ceres.
+ * a must be finite and > 0 (Trivial ignores it).                                                                  */
+typedef enum pgo_loss_type {
+  PGO_LOSS_TRIVIAL = 0,
+  PGO_LOSS_HUBER,
+  PGO_LOSS_SOFTLONE,
+  PGO_LOSS_CAUCHY,
+  PGO_LOSS_ARCTAN,
+  PGO_LOSS_TUKEY
+} pgo_loss_type;
+typedef struct pgo_loss {
+  int32_t type;   /* pgo_loss_type */
+  int32_t _pad;
+  double  a;      /* scale */
+} pgo_loss;
+/* LossFunction::Evaluate: rho[0..2] = rho(s), rho'(s), rho''(s).  PGO_ERR_INVALID_ARG for a null pointer, an unknown type
+ * or a bad scale.                                                                                                    */
+int pgo_loss_evaluate(const pgo_loss* l, double s, double rho[3]);                /* [host] */
+
 typedef enum pgo_termination {
   PGO_TERM_CONVERGENCE_FTOL = 1,
   PGO_TERM_CONVERGENCE_GTOL = 2,
@@ -287,12 +322,24 @@ void pgo_destroy(pgo_t* h);
 
 /* Problem::Evaluate equivalent.  poses_or_null == NULL evaluates at the handle's
  * current poses.  r: E x 3, J: E x 18 = [d e/d P1 (3x3 row-major) | d e/d P2],
- * both in the caller's edge order.  apply_loss != 0 applies the Huber corrector
- * (r <- sqrt(rho') r, J <- sqrt(rho') J) as Ceres' ResidualBlock::Evaluate does.
- * cost = 1/2 sum rho(|e|^2) (always with the loss when huber_delta > 0).
- * r/J outputs need world == 1.                                                  */
+ * both in the caller's edge order.  apply_loss != 0 applies the corrector of each
+ * block's loss (r <- sqrt(rho') r, J <- sqrt(rho') J) as Ceres' ResidualBlock::Evaluate
+ * does.  cost = 1/2 sum rho(|e|^2), always with the losses (pgo_set_losses; by default
+ * Huber(huber_delta), no loss when huber_delta <= 0).  r/J outputs need world == 1.  */
 int pgo_eval(pgo_t* h, const double* poses_or_null, int apply_loss,
              double* cost, double* r_or_null, double* J_or_null);                 /* [gpu] */
+
+/* The loss of every residual block (a pose-graph edge) by loss class.  n_classes = 1..4 losses; edge_class lists each
+ * edge's class in the caller's edge order (a batch: the problems' edges concatenated).  edge_class NULL: an edge's class is
+ * min(kind, n_classes - 1) -- 1 class is one loss for every block, 2 are odometry / loops, 3 follow the edge kind.
+ * A new handle has one class, Huber(huber_delta), or Trivial when huber_delta <= 0; after this call huber_delta is
+ * ignored.  The losses apply to every later evaluation: pgo_eval, the LM loop, the batched solve, pgo_pose_covariance.
+ * pgo_edge_chi2 and the METHOD 2 switch prior have no loss.  A solve begun with pgo_lm_begin becomes stale: pgo_lm_step
+ * returns PGO_ERR_INVALID_ARG until pgo_lm_begin runs again.  Several ranks: every rank passes the same arguments.
+ * PGO_ERR_INVALID_ARG: an unknown type, a non-Trivial scale that is not finite or not > 0, n_classes outside 1..4, a class
+ * index >= n_classes, a null pointer.                                                                                 */
+int pgo_set_losses(pgo_t* h, int32_t n_classes, const pgo_loss* losses,
+                   const uint8_t* edge_class_or_null);                            /* [gpu] */
 
 /* compute_edge_mahalanobis (src/layer_manager.cpp:230-282; the layer managers' edge gate) for every edge at once:
  * chi2[e] = r' Omega r of the PLAIN residual r = (ex, ey, asin(clamp(sin delta, -1, 1))), clamped at 0, in the
@@ -328,6 +375,9 @@ int32_t pgo_batch_size(const pgo_batch_t* b);
 int pgo_batch_solve(pgo_batch_t* b, pgo_summary* summaries);                      /* [gpu] */
 int pgo_batch_get_poses(pgo_batch_t* b, int32_t problem, double* out_xyt);        /* [gpu] */
 int pgo_batch_set_poses(pgo_batch_t* b, int32_t problem, const double* poses_xyt); /* [gpu] */
+/* pgo_set_losses for the whole batch: edge_class (or NULL) over the problems' edges concatenated in problem order */
+int pgo_batch_set_losses(pgo_batch_t* b, int32_t n_classes, const pgo_loss* losses,
+                         const uint8_t* edge_class_or_null);                      /* [gpu] */
 int32_t pgo_batch_num_iter_records(const pgo_batch_t* b, int32_t problem);
 int pgo_batch_get_iter_records(const pgo_batch_t* b, int32_t problem, pgo_iter_record* out, int32_t cap);
 
@@ -375,13 +425,13 @@ int pgo_get_info(const pgo_t* h, pgo_handle_info* out);                         
 
 int pgo_get_poses(pgo_t* h, double* out_xyt /* N x 3 */);                         /* [gpu] */
 /* METHOD 2: current switch per edge in the caller's edge order (1.0 for odometry edges); optionally also
- * d e / d s (E x 3, after the Huber corrector) of the latest Jacobian evaluation.  world == 1.             */
+ * d e / d s (E x 3, after the loss corrector) of the latest Jacobian evaluation.  world == 1.              */
 int pgo_get_switches(pgo_t* h, double* switches /* E */, double* js_or_null /* E x 3 */);   /* [gpu] */
 int pgo_set_poses(pgo_t* h, const double* poses_xyt);                             /* [gpu] */
 
 /* ------------------------------------------------------- pose covariances
  * ceres::Covariance with a constant parameter block: Sigma = (J'J)^-1 at the handle's CURRENT poses, J the Jacobian of the LM
- * loop (Huber corrector, DCS scaling; no LM diagonal).  The constant pose has zero blocks.
+ * loop (the corrector of each block's loss, pgo_set_losses; DCS scaling; no LM diagonal).  The constant pose has zero blocks.
  * Blocks are row-major 3x3 in (x, y, theta), symmetric: Sigma_ab is stored as 1/2 (Sigma_ab + Sigma_ba').  METHOD 2: the pose
  * marginal of the joint (poses, switches) system, at the switches of the latest LM iteration (needs pgo_lm_begin / pgo_solve).
  * Solved by PCG on the Jacobi-scaled undamped normal equations, 3 x poses_per_pass right-hand sides per pass, with the

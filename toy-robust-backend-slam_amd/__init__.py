@@ -22,7 +22,7 @@ from . import _build
 
 __all__ = ["PgoError", "Options", "Summary", "IterRecord", "ReadG2O", "Graph", "Solver", "Batch", "Comm", "lib", "build",
            "HandleInfo", "synth_manhattan", "solve_batch", "shard_plan", "shard_halo", "pose_order", "set_knob", "KernelStats", "EXPORTS", "TERMINATION",
-           "CovarianceOptions", "CovarianceReport"]
+           "CovarianceOptions", "CovarianceReport", "Loss", "LOSS_TYPES"]
 
 EDGE_ODOMETRY, EDGE_CLOSURE, EDGE_BOGUS = 0, 1, 2
 TERMINATION = {1: "CONVERGENCE_FTOL", 2: "CONVERGENCE_GTOL", 3: "CONVERGENCE_PTOL", 4: "NO_CONVERGENCE",
@@ -46,7 +46,9 @@ EXPORTS = [
     "pgo_debug_set_knob",
     "pgo_shard_plan", "pgo_shard_halo", "pgo_pose_order",
     "pgo_covariance_options_default", "pgo_pose_covariance",
+    "pgo_loss_evaluate", "pgo_set_losses", "pgo_batch_set_losses",
 ]
+LOSS_TYPES = {"trivial": 0, "huber": 1, "softlone": 2, "cauchy": 3, "arctan": 4, "tukey": 5}   # pgo_loss_type
 
 
 class PgoError(RuntimeError):
@@ -129,6 +131,41 @@ class CovarianceOptions(C.Structure):
             if k not in dict(self._fields_):
                 raise TypeError("unknown covariance option " + k)
             setattr(self, k, v)
+
+
+class Loss(C.Structure):
+    """mirror of pgo_loss: Loss("cauchy", 0.1) is ceres::CauchyLoss(0.1); names: LOSS_TYPES.  Loss("trivial") is no loss
+    (Ceres' NULL loss; the scale is ignored)."""
+    _fields_ = [("type", C.c_int32), ("_pad", C.c_int32), ("a", C.c_double)]
+
+    def __init__(self, name: str = "trivial", a: float = 0.0):
+        if name not in LOSS_TYPES:
+            raise ValueError(f"unknown loss {name!r} (one of {', '.join(LOSS_TYPES)})")
+        super().__init__(LOSS_TYPES[name], 0, float(a))
+        self.name = name
+
+    def evaluate(self, s: float):
+        """LossFunction::Evaluate: np.array([rho(s), rho'(s), rho''(s)]) (pgo_loss_evaluate, host only)"""
+        rho = np.zeros(3)
+        _check(lib().pgo_loss_evaluate(C.byref(self), float(s), _dp(rho)))
+        return rho
+
+    def __repr__(self):
+        return f"Loss({self.name!r}, {self.a!r})"
+
+
+def _loss_args(losses, edge_class, n_edges):
+    """(n, pgo_loss array, edge class pointer or None, keep-alive) for pgo_set_losses / pgo_batch_set_losses"""
+    ls = [losses] if isinstance(losses, Loss) else list(losses)
+    if not all(isinstance(x, Loss) for x in ls):
+        raise TypeError("losses: a Loss or a list of Loss")
+    arr = (Loss * max(len(ls), 1))(*ls)
+    if edge_class is None:
+        return len(ls), arr, None, None
+    cls = np.ascontiguousarray(edge_class, np.uint8).reshape(-1)
+    if cls.size != n_edges:
+        raise ValueError(f"edge_class: {cls.size} entries for {n_edges} edges")
+    return len(ls), arr, _bp(cls), cls
 
 
 class CovarianceReport(C.Structure):
@@ -241,6 +278,9 @@ def lib():
     L.pgo_covariance_options_default.argtypes = [C.POINTER(CovarianceOptions)]
     L.pgo_covariance_options_default.restype = None
     L.pgo_pose_covariance.argtypes = [vp, C.c_int32, ip, C.POINTER(CovarianceOptions), dp, C.POINTER(CovarianceReport)]
+    L.pgo_loss_evaluate.argtypes = [C.POINTER(Loss), C.c_double, dp]
+    L.pgo_set_losses.argtypes = [vp, C.c_int32, C.POINTER(Loss), bp]
+    L.pgo_batch_set_losses.argtypes = [vp, C.c_int32, C.POINTER(Loss), bp]
     _LIB = L
     return L
 
@@ -468,7 +508,7 @@ class Batch:
     ceres::Solve calls, reference src/simple_layer_manager.cpp:457-622); per-problem LM state, one workgroup per problem
     for the linear solves."""
 
-    def __init__(self, graphs, options: "Options | None" = None, device: int = 0):
+    def __init__(self, graphs, options: "Options | None" = None, device: int = 0, losses=None, edge_class=None):
         self.graphs = list(graphs)
         self.options = options if options is not None else Options()
         n = len(self.graphs)
@@ -476,6 +516,14 @@ class Batch:
         self._h = C.c_void_p()
         _check(lib().pgo_batch_create(C.byref(self._h), n, hs, C.byref(self.options), device))
         self.n = n
+        if losses is not None:
+            self.set_losses(losses, edge_class)
+
+    def set_losses(self, losses, edge_class=None):
+        """pgo_batch_set_losses: losses = a Loss or a list of 1-4 (classes); edge_class over the problems' edges
+        concatenated, or None (class = min(kind, n_classes - 1))"""
+        n, arr, cls, keep = _loss_args(losses, edge_class, sum(g.n_edges for g in self.graphs))
+        _check(lib().pgo_batch_set_losses(self._h, n, arr, cls))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -512,7 +560,8 @@ class Batch:
 class Solver:
     """Problem assembly + ceres::Solve replacement (reference main.cpp:66-163)."""
 
-    def __init__(self, graph: Graph, options: Options | None = None, comm: Comm | None = None, device: int = 0):
+    def __init__(self, graph: Graph, options: Options | None = None, comm: Comm | None = None, device: int = 0,
+                 losses=None, edge_class=None):
         self.graph = graph
         self.options = options if options is not None else Options()
         self.comm = comm
@@ -520,6 +569,15 @@ class Solver:
         _check(lib().pgo_create_from_graph(C.byref(self._h), graph._h, C.byref(self.options),
                                            comm._h if comm else None, device))
         self.n_poses, self.n_edges = graph.n_poses, graph.n_edges
+        if losses is not None:
+            self.set_losses(losses, edge_class)
+
+    def set_losses(self, losses, edge_class=None):
+        """pgo_set_losses: losses = a Loss or a list of 1-4 (the loss classes); edge_class = each edge's class, or None
+        (class = min(kind, n_classes - 1): one loss for all, odometry / loops, or by edge kind).  A solve begun with
+        lm_begin is stale afterwards."""
+        n, arr, cls, keep = _loss_args(losses, edge_class, self.n_edges)
+        _check(lib().pgo_set_losses(self._h, n, arr, cls))
 
     def close(self):
         if getattr(self, "_h", None):

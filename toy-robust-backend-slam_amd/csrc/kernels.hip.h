@@ -1,8 +1,8 @@
 // HIP kernels of the pose-graph backend, written for gfx950 (CDNA4, wave64).
 // Everything here is HBM-bandwidth bound fp64 work on 3x3 blocks: no MFMA.
 //
-//   K1  k_edge_eval      fused per-edge SE(2) residual + 3x6 Jacobian + DCS weight + Huber
-//                        corrector (reference: src/ceres_error.cpp:42-94, 135-196 evaluated through
+//   K1  k_edge_eval      fused per-edge SE(2) residual + 3x6 Jacobian + DCS weight + Huber (or, with pgo_set_losses,
+//                        any loss of loss.h per edge class) corrector (reference: src/ceres_error.cpp:42-94, 135-196 evaluated through
 //                        AutoDiffCostFunction, main.cpp:66-68 loss); writes a 112-byte record per edge
 //   K2  k_assemble       row-tiled segmented reduction of (JS)'(JS) and S J'r (S = Jacobi column
 //                        scaling) into diagonal planes + one off-diagonal 3x3 block per incidence
@@ -13,6 +13,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "loss.h"
 
 namespace pgo {
 namespace dev {
@@ -209,11 +211,12 @@ struct EdgeArgs {
   const double* mx;
   const double* my;
   const double* mt;
-  const uint8_t* flags;   // bit0 robust edge (DCS for METHOD 1, switchable for METHOD 2), bit1 cost counted on this rank
+  const uint8_t* flags;   // bit0 robust edge (DCS for METHOD 1, switchable for METHOD 2), bit1 cost counted on this rank,
+                          // bits 2-3 loss class (read by k_edge_eval<*, *, true> only)
   int32_t n_edges;
   int32_t apply_loss;
   double phi;
-  double huber_delta;
+  double huber_delta;     // the default instantiation's loss: Huber(huber_delta), none when <= 0
   // METHOD 2 (switchable constraints, src/ceres_error.cpp:237-317, main.cpp:115-125): e = s e_plain per robust
   // edge plus the prior sqrt(lambda) (1 - s); nullptr for METHOD 0/1
   const double* sw;       // [n_edges] switch per local edge
@@ -225,7 +228,21 @@ struct EdgeArgs {
   // batched handles: cost of every edge (NaN where the residual or Jacobian is not finite), summed per problem by
   // k_prob_reduce; nullptr otherwise
   double* cost_out;
+  // pgo_set_losses: the loss of each class (k_edge_eval<*, *, true>); four named fields, not an array: a lane-dependent
+  // index into an array argument is lowered through scratch
+  LossClass loss0, loss1, loss2, loss3;
 };
+
+// the loss class of an edge, picked field by field with selects
+__device__ __forceinline__ LossClass pick_loss(const EdgeArgs& A, unsigned k) {
+  LossClass L;
+  L.type = k == 0u ? A.loss0.type : k == 1u ? A.loss1.type : k == 2u ? A.loss2.type : A.loss3.type;
+  L._pad = 0;
+  L.a = k == 0u ? A.loss0.a : k == 1u ? A.loss1.a : k == 2u ? A.loss2.a : A.loss3.a;
+  L.b = k == 0u ? A.loss0.b : k == 1u ? A.loss1.b : k == 2u ? A.loss2.b : A.loss3.b;
+  L.c = k == 0u ? A.loss0.c : k == 1u ? A.loss1.c : k == 2u ? A.loss2.c : A.loss3.c;
+  return L;
+}
 
 // Cholesky factor of a 3x3 information matrix, Omega = L L' (positive definiteness is checked on the host at create)
 struct Chol3 {
@@ -245,7 +262,9 @@ __device__ __forceinline__ Chol3 chol3(double w00, double w01, double w02, doubl
 
 // One lane per edge.  Algorithmic bytes per edge: 8 (ia,ib) + 24 (meas) + 1 (flags) +
 // 48 (two poses) read, 112 written with the Jacobian, 0 without (INFO: + 48 read, 128 written).
-template <bool WITH_JAC, bool INFO>
+// LOSSES = false: the loss is Huber(A.huber_delta) or none for every edge (a new handle; one Huber / Trivial class);
+// true: each edge's loss is that of its class (flags bits 2-3), any of pgo_set_losses' family.
+template <bool WITH_JAC, bool INFO, bool LOSSES = false>
 __global__ __launch_bounds__(WG) void k_edge_eval(EdgeArgs A, double* __restrict__ jr,
                                                   double* __restrict__ cost_part, int* __restrict__ bad) {
   constexpr int RN = RecLayout<INFO>::N, RL = RecLayout<INFO>::LDS;
@@ -351,7 +370,12 @@ __global__ __launch_bounds__(WG) void k_edge_eval(EdgeArgs A, double* __restrict
     }
     const double s = ex * ex + ey * ey + et * et;
     double rho0 = s, sc = 1.0;
-    if (A.huber_delta > 0.0) {  // ceres::HuberLoss(a): b = a^2
+    if constexpr (LOSSES) {  // the class's loss; rho'' <= 0 for all of them: the corrector scales by sqrt(rho')
+      double rho[3];
+      loss_rho(pick_loss(A, (fl >> 2) & 3u), s, rho);
+      rho0 = rho[0];
+      if (A.apply_loss) sc = sqrt(rho[1]);
+    } else if (A.huber_delta > 0.0) {  // ceres::HuberLoss(a): b = a^2
       const double bq = A.huber_delta * A.huber_delta;
       if (s > bq) {
         const double rs = sqrt(s);

@@ -2,6 +2,39 @@
 // kernel-bench entry points the parity tests and bench.py use.
 #include "solver_handle.hip.h"
 
+// every argument is checked before anything changes; then the class bits of the local edges' flags are rewritten and the
+// running solve (if any) is stale: pgo_lm_step refuses until pgo_lm_begin, and the next linearisation uses the new losses
+int pgo_handle::set_losses(int32_t n_classes, const pgo_loss* losses, const uint8_t* edge_class) {
+  if (n_classes < 1 || n_classes > pgo::MAX_LOSS_CLASSES) return fail(PGO_ERR_INVALID_ARG, "pgo_set_losses: n_classes must be 1..4");
+  if (!losses) return fail(PGO_ERR_INVALID_ARG, "pgo_set_losses: null losses");
+  for (int32_t k = 0; k < n_classes; ++k)
+    if (!pgo::loss_valid(losses[k]))
+      return fail(PGO_ERR_INVALID_ARG, "pgo_set_losses: class " + std::to_string(k) + ": unknown type or a scale that is not finite and > 0");
+  if (edge_class)
+    for (int64_t e = 0; e < n_edges_total; ++e)
+      if (edge_class[e] >= n_classes)
+        return fail(PGO_ERR_INVALID_ARG, "pgo_set_losses: edge " + std::to_string(e) + ": class " + std::to_string(edge_class[e]) + " >= n_classes");
+  const int32_t t0 = losses[0].type;
+  loss_n = n_classes;
+  loss_general = !(n_classes == 1 && (t0 == PGO_LOSS_TRIVIAL || t0 == PGO_LOSS_HUBER));
+  loss_huber = (n_classes == 1 && t0 == PGO_LOSS_HUBER) ? losses[0].a : 0.0;
+  for (int k = 0; k < pgo::MAX_LOSS_CLASSES; ++k) {
+    const pgo_loss& l = losses[std::min<int32_t>(k, n_classes - 1)];
+    loss_cls[k] = pgo::make_loss_class(l.type, l.a);
+  }
+  const int64_t EL = S.n_edges_local;
+  for (int64_t k = 0; k < EL; ++k) {
+    const int c = edge_class ? edge_class[S.orig_edge[k]] : std::min<int>(kind_local[k], n_classes - 1);
+    S.flags[k] = (uint8_t)((S.flags[k] & 3u) | ((unsigned)c << 2));
+  }
+  lin_valid = false;
+  lm_active = false;
+  if (EL == 0) return PGO_OK;
+  HIPC(hipSetDevice(device));
+  PGOC(upload(e_flags, S.flags));
+  return sync();
+}
+
 // ====================================================================== C-ABI
 namespace {
 struct Knob {
@@ -208,6 +241,18 @@ int pgo_eval(pgo_t* h, const double* poses_or_null, int apply_loss, double* cost
   }
   if (h->h_scal[1] > 0.0) return fail(PGO_ERR_NUMERIC, "non-finite residual or Jacobian");
   return PGO_OK;
+}
+
+int pgo_loss_evaluate(const pgo_loss* l, double s, double rho[3]) {
+  if (!l || !rho) return fail(PGO_ERR_INVALID_ARG, "pgo_loss_evaluate: null");
+  if (!pgo::loss_valid(*l)) return fail(PGO_ERR_INVALID_ARG, "pgo_loss_evaluate: unknown type or a scale that is not finite and > 0");
+  pgo::loss_rho(pgo::make_loss_class(l->type, l->a), s, rho);
+  return PGO_OK;
+}
+
+int pgo_set_losses(pgo_t* h, int32_t n_classes, const pgo_loss* losses, const uint8_t* edge_class) {
+  if (!h) return fail(PGO_ERR_INVALID_ARG, "pgo_set_losses: null handle");
+  return h->set_losses(n_classes, losses, edge_class);
 }
 
 int pgo_edge_chi2(pgo_t* h, const double* poses_or_null, double* chi2_out) {

@@ -386,6 +386,12 @@ int pgo_batch_set_poses(pgo_batch_t* b, int32_t k, const double* poses) {
   return H.sync();
 }
 
+int pgo_batch_set_losses(pgo_batch_t* b, int32_t n_classes, const pgo_loss* losses, const uint8_t* edge_class) {
+  if (!b) return fail(PGO_ERR_INVALID_ARG, "pgo_batch_set_losses: null");
+  b->begun = false;
+  return b->U->set_losses(n_classes, losses, edge_class);   // (the union's edges are the problems' edges concatenated)
+}
+
 int32_t pgo_batch_num_iter_records(const pgo_batch_t* b, int32_t k) {
   return (b && k >= 0 && k < b->n) ? (int32_t)b->st[k].recs.size() : 0;
 }

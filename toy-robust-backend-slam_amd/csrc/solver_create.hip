@@ -97,6 +97,9 @@ int pgo_handle::create(int32_t N, const double* poses_h, int32_t E, const int32_
   }
   PGOC(pgo::build_shard_structure(N, E, ia, ib, meas, kind, opt.method, world, rank, (int)row_align, &S,
                                   tile_breaks_h.empty() ? nullptr : &tile_breaks_h));
+  default_losses();
+  kind_local.resize((size_t)S.n_edges_local);   // (pgo_set_losses' default classes follow the edge kind)
+  for (int32_t k = 0; k < S.n_edges_local; ++k) kind_local[k] = kind[S.orig_edge[k]];
   // Graphs large enough for the one-tile-per-workgroup product kernel (k_spmv_1, below) get the padded-slot layout: every
   // tile's incidences at TILE_INC t (structure.cpp, pad_tiles_to_slots).  Test hook "pad_tiles" = 0 keeps the dense layout.
   int one_tile_min = 4096;

@@ -358,14 +358,31 @@ struct pgo_handle {
     A.n_edges = S.n_edges_local;
     A.apply_loss = apply_loss;
     A.phi = opt.phi;
-    A.huber_delta = opt.huber_delta;
+    A.huber_delta = loss_huber;
     A.sw = has_sw ? sw_vals : nullptr;
     A.sw_js = sw_js;
     A.sc_lambda = opt.sc_prior_lambda;
     A.info = e_info;
     A.cost_out = edge_cost;
+    A.loss0 = loss_cls[0];
+    A.loss1 = loss_cls[1];
+    A.loss2 = loss_cls[2];
+    A.loss3 = loss_cls[3];
     return A;
   }
+  // robust losses (pgo_set_losses): the loss of each class; an edge's class sits in bits 2-3 of its flags byte
+  pgo::LossClass loss_cls[pgo::MAX_LOSS_CLASSES] = {};
+  int loss_n = 1;
+  bool loss_general = false;       // K1's general instantiation: anything but one Huber / Trivial class
+  double loss_huber = 0.0;         // the default instantiation's Huber scale (<= 0: no loss)
+  std::vector<uint8_t> kind_local;   // edge kind per local edge (the default classes)
+  void default_losses() {          // a new handle: Huber(huber_delta), Trivial when huber_delta <= 0
+    loss_n = 1;
+    loss_general = false;
+    loss_huber = opt.huber_delta;
+    for (auto& L : loss_cls) L = pgo::make_loss_class(opt.huber_delta > 0.0 ? PGO_LOSS_HUBER : PGO_LOSS_TRIVIAL, opt.huber_delta);
+  }
+  int set_losses(int32_t n_classes, const pgo_loss* losses, const uint8_t* edge_class);
   dev::SwitchArrays switch_arrays() const {
     dev::SwitchArrays W;
     W.flags = e_flags;

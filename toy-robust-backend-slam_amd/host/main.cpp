@@ -16,14 +16,34 @@
 #include "graph.h"
 #include "pgo_problem.h"
 
+// --loss / --loop-loss NAME[:A]: trivial, huber, softlone, cauchy, arctan, tukey; A defaults to main.cpp:68's 0.01
+static std::unique_ptr<pgo::LossFunction> make_loss(const std::string& spec) {
+  const size_t colon = spec.find(':');
+  const std::string name = spec.substr(0, colon);
+  const double a = colon == std::string::npos ? 0.01 : std::stod(spec.substr(colon + 1));
+  std::unique_ptr<pgo::LossFunction> l;
+  if (name == "trivial") l.reset(new pgo::TrivialLoss());
+  else if (name == "huber") l.reset(new pgo::HuberLoss(a));
+  else if (name == "softlone") l.reset(new pgo::SoftLOneLoss(a));
+  else if (name == "cauchy") l.reset(new pgo::CauchyLoss(a));
+  else if (name == "arctan") l.reset(new pgo::ArctanLoss(a));
+  else if (name == "tukey") l.reset(new pgo::TukeyLoss(a));
+  else throw std::invalid_argument("unknown loss " + name + " (trivial, huber, softlone, cauchy, arctan, tukey)");
+  double rho[3];
+  l->Evaluate(0.0, rho);   // checks the scale
+  return l;
+}
+
 int main(int argc, char* argv[]) {
   if (argc < 4) {
     std::cout << "Usage: " << argv[0] << " DATASET NUM_OUTLIER_LOOPS METHOD [--seed S] [--data DIR] [--save DIR] [--device D]\n"
+              << "       [--precision P] [--loss NAME[:A]] [--loop-loss NAME[:A]]  (losses: trivial huber softlone cauchy arctan tukey;\n"
+              << "       --loss sets every block's, default huber:0.01; --loop-loss overrides it on closure and bogus blocks)\n"
               << "METHOD: 0=baseline, 1=DCS, 2=Switchable (3=Layer, 4=Simple Layer MCTS: not in this backend)\n"
               << "Example: " << argv[0] << " INTEL 50 1\n";
     return -1;
   }
-  std::string base = "../data", save = "../save";
+  std::string base = "../data", save = "../save", loss_spec = "huber:0.01", loop_spec;
   long long seed = -1;
   int device = 0, precision = 0;
   for (int i = 4; i + 1 < argc; i += 2) {
@@ -32,8 +52,19 @@ int main(int argc, char* argv[]) {
     else if (!strcmp(argv[i], "--save")) save = argv[i + 1];
     else if (!strcmp(argv[i], "--device")) device = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "--precision")) precision = atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "--loss")) loss_spec = argv[i + 1];
+    else if (!strcmp(argv[i], "--loop-loss")) loop_spec = argv[i + 1];
     else { std::cerr << "unknown option " << argv[i] << "\n"; return -1; }
   }
+  std::unique_ptr<pgo::LossFunction> loss_function, loop_loss;
+  try {
+    loss_function = make_loss(loss_spec);
+    if (!loop_spec.empty()) loop_loss = make_loss(loop_spec);
+  } catch (const std::exception& e) {
+    std::cerr << "error: " << e.what() << std::endl;
+    return -1;
+  }
+  pgo::LossFunction* closure_loss = loop_loss ? loop_loss.get() : loss_function.get();
   const int method = atoi(argv[3]);
   if (method < 0 || method > 2) {
     std::cerr << "METHOD " << method << " is not part of the MI355X backend (METHOD 0, 1 and 2 only)\n";
@@ -51,26 +82,25 @@ int main(int argc, char* argv[]) {
     std::cout << "total nEdgesClosure : " << g2o_manager.nEdgesClosure.size() << std::endl;
     std::cout << "total nEdgesBogus : " << g2o_manager.nEdgesBogus.size() << std::endl;
 
-    pgo::Problem problem;
-    pgo::LossFunction* loss_function = new pgo::HuberLoss(0.01);
+    pgo::Problem problem;   // (the loss: main.cpp:68's HuberLoss(0.01) unless --loss / --loop-loss say otherwise)
     const bool DCS_ON = (method == 1), SC_ON = (method == 2);
     std::vector<double> switch_priors;      // for SC (reference main.cpp:105-107)
     std::vector<double*> switch_variables;
     const double sc_prior_lambda = 1.0;
     for (Edge* ed : g2o_manager.nEdgesOdometry)
-      problem.AddResidualBlock(OdometryResidue::Create(ed->x, ed->y, ed->theta), loss_function, ed->a->p, ed->b->p);
+      problem.AddResidualBlock(OdometryResidue::Create(ed->x, ed->y, ed->theta), loss_function.get(), ed->a->p, ed->b->p);
     for (auto* list : {&g2o_manager.nEdgesClosure, &g2o_manager.nEdgesBogus})
       for (Edge* ed : *list) {
         if (SC_ON) {
           double* s = new double(1.0);
           switch_variables.push_back(s);
           switch_priors.push_back(1.0);
-          problem.AddResidualBlock(SwitchableClosureResidue::Create(ed->x, ed->y, ed->theta), loss_function, ed->a->p, ed->b->p, s);
+          problem.AddResidualBlock(SwitchableClosureResidue::Create(ed->x, ed->y, ed->theta), closure_loss, ed->a->p, ed->b->p, s);
           problem.AddResidualBlock(SwitchPriorResidue::Create(sc_prior_lambda), nullptr, s);
         } else {
           problem.AddResidualBlock(DCS_ON ? DCSClosureResidue::Create(ed->x, ed->y, ed->theta)
                                           : OdometryResidue::Create(ed->x, ed->y, ed->theta),
-                                   loss_function, ed->a->p, ed->b->p);
+                                   closure_loss, ed->a->p, ed->b->p);
         }
       }
     problem.SetParameterBlockConstant(g2o_manager.nNodes[0]->p);
@@ -82,7 +112,6 @@ int main(int argc, char* argv[]) {
     pgo::Solver::Summary summary;
     pgo::Solve(options, &problem, &summary);
     std::cout << summary.FullReport() << std::endl;
-    delete loss_function;
 
     g2o_manager.writePoseGraph_nodes(save + "/opt_nodes.txt", precision);
     g2o_manager.writePoseGraph_edges(save + "/opt_edges.txt");

@@ -19,15 +19,31 @@
 
 namespace pgo {
 
+// ceres::LossFunction and the family the device evaluates (include/pgo.h, "robust losses").  A residual block added with
+// a NULL loss has the Trivial one, as in Ceres.
 struct LossFunction {
+  explicit LossFunction(int32_t type, double a = 0.0) {
+    l_.type = type;
+    l_._pad = 0;
+    l_.a = type == PGO_LOSS_TRIVIAL ? 0.0 : a;
+  }
   virtual ~LossFunction() {}
-  virtual double huber_delta() const = 0;
+  // rho[0..2] = rho(s), rho'(s), rho''(s)
+  void Evaluate(double s, double rho[3]) const {
+    const int st = pgo_loss_evaluate(&l_, s, rho);
+    if (st != PGO_OK) throw std::invalid_argument(std::string("loss: ") + pgo_last_error());
+  }
+  const pgo_loss& loss() const { return l_; }
+
+ private:
+  pgo_loss l_;
 };
-struct HuberLoss : LossFunction {  // ceres::HuberLoss(a), main.cpp:68
-  explicit HuberLoss(double a) : a_(a) {}
-  double huber_delta() const override { return a_; }
-  double a_;
-};
+struct TrivialLoss : LossFunction { TrivialLoss() : LossFunction(PGO_LOSS_TRIVIAL) {} };
+struct HuberLoss : LossFunction { explicit HuberLoss(double a) : LossFunction(PGO_LOSS_HUBER, a) {} };  // main.cpp:68
+struct SoftLOneLoss : LossFunction { explicit SoftLOneLoss(double a) : LossFunction(PGO_LOSS_SOFTLONE, a) {} };
+struct CauchyLoss : LossFunction { explicit CauchyLoss(double a) : LossFunction(PGO_LOSS_CAUCHY, a) {} };
+struct ArctanLoss : LossFunction { explicit ArctanLoss(double a) : LossFunction(PGO_LOSS_ARCTAN, a) {} };
+struct TukeyLoss : LossFunction { explicit TukeyLoss(double a) : LossFunction(PGO_LOSS_TUKEY, a) {} };
 
 enum LinearSolverType { SPARSE_NORMAL_CHOLESKY, BLOCK_JACOBI_PCG };
 
@@ -36,6 +52,7 @@ class Problem {
   void AddResidualBlock(CostFunction* cost, LossFunction* loss, double* p1, double* p2) {
     std::unique_ptr<CostFunction> own(cost);  // TAKE_OWNERSHIP, as Ceres does by default
     if (p1 == p2) throw std::invalid_argument("duplicate parameter block in a residual block");
+    const uint8_t cls = loss_class(loss);
     ia_.push_back(block(p1));
     ib_.push_back(block(p2));
     meas_.insert(meas_.end(), {cost->dx, cost->dy, cost->dtheta});
@@ -45,24 +62,21 @@ class Problem {
     kind_.push_back(dcs ? PGO_EDGE_CLOSURE : PGO_EDGE_ODOMETRY);
     switch_.push_back(nullptr);
     any_dcs_ = any_dcs_ || dcs;
-    const double d = loss ? loss->huber_delta() : 0.0;
-    if (!ia_.empty() && ia_.size() > 1 && d != delta_) mixed_loss_ = true;
-    delta_ = d;
+    class_.push_back(cls);
   }
   // SwitchableClosureResidue: (P1, P2, S)  (reference main.cpp:122,143)
   void AddResidualBlock(CostFunction* cost, LossFunction* loss, double* p1, double* p2, double* s) {
     std::unique_ptr<CostFunction> own(cost);
     if (cost->kind != CostFunction::SWITCHABLE) throw std::invalid_argument("three parameter blocks: SwitchableClosureResidue only");
     if (p1 == p2) throw std::invalid_argument("duplicate parameter block in a residual block");
+    const uint8_t cls = loss_class(loss);
     ia_.push_back(block(p1));
     ib_.push_back(block(p2));
     meas_.insert(meas_.end(), {cost->dx, cost->dy, cost->dtheta});
     kind_.push_back(PGO_EDGE_CLOSURE);
     switch_.push_back(s);
     any_sc_ = true;
-    const double d = loss ? loss->huber_delta() : 0.0;
-    if (ia_.size() > 1 && d != delta_) mixed_loss_ = true;
-    delta_ = d;
+    class_.push_back(cls);
   }
   // SwitchPriorResidue: (S), no loss  (reference main.cpp:124-125,144-145)
   void AddResidualBlock(CostFunction* cost, LossFunction* loss, double* s) {
@@ -76,6 +90,15 @@ class Problem {
 
  private:
   friend struct SolverAccess;
+  // the block's loss class: every distinct loss value (type, a) is one class, NULL = Trivial; the device has 4 classes
+  uint8_t loss_class(const LossFunction* loss) {
+    const pgo_loss l = loss ? loss->loss() : TrivialLoss().loss();
+    for (size_t k = 0; k < losses_.size(); ++k)
+      if (losses_[k].type == l.type && losses_[k].a == l.a) return (uint8_t)k;
+    if (losses_.size() == 4) throw std::invalid_argument("this backend takes at most 4 distinct loss functions per problem");
+    losses_.push_back(l);
+    return (uint8_t)(losses_.size() - 1);
+  }
   int32_t block(double* p) {
     auto it = id_.find(p);
     if (it != id_.end()) return it->second;
@@ -90,10 +113,11 @@ class Problem {
   std::vector<double> meas_;
   std::vector<uint8_t> kind_;
   int32_t fixed_ = -1;
-  double delta_ = 0.0;
+  std::vector<pgo_loss> losses_;                   // the distinct losses (pgo_set_losses' classes)
+  std::vector<uint8_t> class_;                     // per residual block: its loss class
   std::vector<double*> switch_;                    // per residual block: its switch variable or nullptr
   std::unordered_map<double*, double> prior_lambda_;  // switch -> lambda of its prior
-  bool any_dcs_ = false, any_sc_ = false, mixed_loss_ = false;
+  bool any_dcs_ = false, any_sc_ = false;
 };
 
 namespace Solver {
@@ -137,8 +161,18 @@ struct SolverAccess {
     if (st != PGO_OK) throw std::runtime_error(std::string("pgo: ") + pgo_strerror(st) + ": " + pgo_last_error());
   }
   // Problem -> device handle (the arrays the residual blocks were recorded into)
+  // the problem's loss classes on a handle or a batch (one Huber or NULL loss for all blocks: the library's default path)
+  static std::vector<pgo_loss> LossTable(const Problem* pr) {
+    return pr->losses_.empty() ? std::vector<pgo_loss>{TrivialLoss().loss()} : pr->losses_;
+  }
+  static bool SameLosses(const Problem* a, const Problem* b) {
+    const std::vector<pgo_loss> x = LossTable(a), y = LossTable(b);
+    if (x.size() != y.size()) return false;
+    for (size_t k = 0; k < x.size(); ++k)
+      if (x[k].type != y[k].type || x[k].a != y[k].a) return false;
+    return true;
+  }
   static pgo_t* Prepare(const Solver::Options& opt, Problem* pr) {
-    if (pr->mixed_loss_) throw std::invalid_argument("this backend needs one shared loss for all residual blocks (as main.cpp:68)");
     const int32_t N = (int32_t)pr->ptr_.size(), E = (int32_t)pr->ia_.size();
     std::vector<double> poses((size_t)3 * N);
     for (int32_t i = 0; i < N; ++i)
@@ -159,7 +193,6 @@ struct SolverAccess {
       }
       o.sc_prior_lambda = lam;
     }
-    o.huber_delta = pr->delta_;
     o.fixed_pose = pr->fixed_;
     o.max_iters = opt.max_num_iterations;
     o.ftol = opt.function_tolerance;
@@ -172,6 +205,13 @@ struct SolverAccess {
     o.verbose = opt.minimizer_progress_to_stdout ? 1 : 0;
     pgo_t* h = nullptr;
     check(pgo_create(&h, N, poses.data(), E, pr->ia_.data(), pr->ib_.data(), pr->meas_.data(), pr->kind_.data(), &o, nullptr, opt.device));
+    const std::vector<pgo_loss> L = LossTable(pr);
+    const int st = pgo_set_losses(h, (int32_t)L.size(), L.data(), E ? pr->class_.data() : nullptr);
+    if (st != PGO_OK) {
+      const std::string msg = pgo_last_error();
+      pgo_destroy(h);
+      throw std::runtime_error(std::string("pgo: ") + pgo_strerror(st) + ": " + msg);
+    }
     return h;
   }
   // results back into the caller's parameter blocks (in place, like Ceres); destroys the handle
@@ -205,8 +245,8 @@ struct SolverAccess {
   static bool BatchEligible(const std::vector<Problem*>& prs) {
     if (prs.empty()) return false;
     for (Problem* pr : prs)
-      if (pr->mixed_loss_ || pr->any_sc_ || pr->any_dcs_ != prs[0]->any_dcs_ || pr->delta_ != prs[0]->delta_ ||
-          pr->fixed_ != prs[0]->fixed_ || pr->ptr_.empty())
+      if (pr->any_sc_ || pr->any_dcs_ != prs[0]->any_dcs_ || !SameLosses(pr, prs[0]) || pr->fixed_ != prs[0]->fixed_ ||
+          pr->ptr_.empty())
         return false;
     return true;
   }
@@ -231,7 +271,6 @@ struct SolverAccess {
         pgo_options o;
         pgo_options_default(&o);
         o.method = prs[0]->any_dcs_ ? 1 : 0;
-        o.huber_delta = prs[0]->delta_;
         o.fixed_pose = prs[0]->fixed_;
         o.max_iters = opt.max_num_iterations;
         o.ftol = opt.function_tolerance;
@@ -244,6 +283,10 @@ struct SolverAccess {
         int st = pgo_batch_create(&b, (int32_t)prs.size(), gs.data(), &o, opt.device);
         if (st != PGO_ERR_UNSUPPORTED) {
           check(st);
+          std::vector<uint8_t> cls;   // the problems' blocks concatenated
+          for (Problem* pr : prs) cls.insert(cls.end(), pr->class_.begin(), pr->class_.end());
+          const std::vector<pgo_loss> L = LossTable(prs[0]);
+          check(pgo_batch_set_losses(b, (int32_t)L.size(), L.data(), cls.empty() ? nullptr : cls.data()));
           std::vector<pgo_summary> raw(prs.size());
           check(pgo_batch_solve(b, raw.data()));
           sums->assign(prs.size(), Solver::Summary());
