@@ -420,6 +420,10 @@ typedef struct pgo_handle_info {
                                         world > 1, pcg_rtol >= 1e-6, chain preconditioner), 0 = the textbook two-reduction loop */
   int32_t pcg_coarse_off_iters;      /* LM iterations whose PCG solve ran WITHOUT the second level because its factorisation was
                                         not usable (a pivot lost to rounding); 0 on a healthy solve                          */
+  int32_t direct_separators;         /* direct solve: separator poses the chain is cut at (0 below 256 poses)              */
+  int32_t direct_segments;           /* direct solve: segments of the chain sweeps (32, fewer on chains shorter than that)   */
+  int32_t direct_refine_kernel;      /* direct solve: the refinement's column is solved by 1 = k_dlr_solve1 (one launch, up to
+                                        4096 poses), 2 = the batched sweep kernels; 0 = not on the direct solve             */
 } pgo_handle_info;
 int pgo_get_info(const pgo_t* h, pgo_handle_info* out);                           /* [host] */
 
@@ -487,6 +491,15 @@ int pgo_debug_spmv(pgo_t* h, const double* x, double* y);                       
 /* y = (J'J + D'D) x through the product kernel the PCG loop runs, after the same set-up as pgo_debug_precond (LM diagonal
  * for the current radius); optionally d2 = the diagonal of D'D (3N).  x, y, d2: caller's pose order (world == 1).     */
 int pgo_debug_system_spmv(pgo_t* h, const double* x, double* y, double* d2_or_null);   /* [gpu] */
+/* y = (J'J + D'D)^-1 b by the handle's direct solve (chain + low rank) at its current LM state, through the launch sequence
+ * an LM iteration runs; b, y: 3N doubles in the conventions of pgo_debug_system_spmv, whose product of y gives b back.  The
+ * rows of the constant pose must be 0 in b, as they are in LM's gradient.  refine_steps: -1 = the handle's own number of
+ * iterative-refinement steps (what LM runs), 0 = the raw Woodbury result, 1 .. 3 = that many.  The solve is not affected.
+ * METHOD 2 after a rejected step: the reduced pose system is the one assembled for the previous radius until the next LM
+ * iteration re-assembles it; this entry point and pgo_debug_system_spmv both see that one.
+ * PGO_ERR_UNSUPPORTED on a handle that is not on the direct solve (pgo_handle_info.linear_solver), PGO_ERR_INVALID_ARG
+ * for a null pointer, refine_steps outside -1 .. 3 or a handle without pgo_lm_begin.                                    */
+int pgo_debug_direct_solve(pgo_t* h, const double* b_3n, int32_t refine_steps, double* y_3n);   /* [gpu] */
 /* normal-equation pieces at the current point, caller's pose order (world == 1):
  * g: 3N gradient J'r (unscaled), hdiag: N x 9 diagonal 3x3 blocks of J'J         */
 int pgo_debug_normal_eq(pgo_t* h, double* g_or_null, double* hdiag_or_null);      /* [gpu] */

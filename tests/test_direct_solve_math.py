@@ -2,7 +2,7 @@
 recurrence the kernel runs, every other edge as a low-rank term V'V through the Woodbury identity, one step of iterative
 refinement -- against the oracle's sparse direct solve (SuperLU) of the same LM system.  Pins the algebra (splitting,
 recurrence, segment-parallel sweeps with prefix products) independently of the GPU; the GPU path itself is checked in
-tests/test_gpu_parity.py::test_direct_solve_*."""
+tests/test_gpu_direct.py (as an operator, against tests/_direct_restatement.py) and tests/test_gpu_parity.py::test_direct_solve_*."""
 import os
 
 import numpy as np
@@ -11,6 +11,7 @@ import scipy.linalg as sl
 import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
+from _direct_restatement import _chain_split, _factor, _solve_segmented
 from conftest import DATA
 
 
@@ -31,76 +32,6 @@ def _system(oracle, name, n_out, method, radius):
     D2 = np.clip(H.diagonal(), 1e-6, 1e32) / radius
     gs = s * (A.T @ r.reshape(-1))
     return g, As, H, D2, gs
-
-
-def _chain_split(g):
-    chain = -np.ones(g.n_poses, np.int64)
-    for e, (a, b) in enumerate(zip(g.ia, g.ib)):
-        lo, hi = min(a, b), max(a, b)
-        if hi == lo + 1 and chain[lo] < 0:
-            chain[lo] = e
-    is_chain = np.zeros(g.n_edges, bool)
-    is_chain[chain[chain >= 0]] = True
-    return is_chain
-
-
-def _factor(T):
-    """k_dlr_factor: W_i = C_i S_{i-1}^-1, S_i = M_i - W_i C_i'"""
-    n = T.shape[0] // 3
-    Td = T.toarray()
-    W, Sinv = [np.zeros((3, 3))] * n, [None] * n
-    Sinv[0] = np.linalg.inv(Td[:3, :3])
-    for i in range(1, n):
-        C = Td[3 * i:3 * i + 3, 3 * i - 3:3 * i]
-        W[i] = C @ Sinv[i - 1]
-        Sinv[i] = np.linalg.inv(Td[3 * i:3 * i + 3, 3 * i:3 * i + 3] - W[i] @ C.T)
-    return W, Sinv
-
-
-def _solve_segmented(W, Sinv, B, nseg=32):
-    """k_dlr_prefix / _fwd / _mid / _fix: sweeps cut into segments, joined through the prefix products G, Gb"""
-    n = len(W)
-    L = -(-n // nseg)
-    segs = [(s0, min(n, s0 + L)) for s0 in range(0, n, L)]
-    Wn = W + [np.zeros((3, 3))]
-    G, Gb = [None] * n, [None] * n
-    for i0, i1 in segs:
-        g = np.eye(3)
-        for i in range(i0, i1):
-            g = -W[i] @ g
-            G[i] = g
-        g = np.eye(3)
-        for i in range(i1 - 1, i0 - 1, -1):
-            g = -Wn[i + 1].T @ g
-            Gb[i] = g
-    X = B.copy().reshape(n, 3, -1)
-    E = []
-    for i0, i1 in segs:                       # local forward sweeps
-        t = np.zeros_like(X[0])
-        for i in range(i0, i1):
-            t = X[i] - W[i] @ t
-            X[i] = t
-        E.append(t)
-    tin, E2 = np.zeros_like(X[0]), []
-    tins = []
-    for q, (i0, i1) in enumerate(segs):
-        tins.append(tin)
-        tin = E[q] + G[i1 - 1] @ tin
-    for q, (i0, i1) in enumerate(segs):       # true t on the fly, local backward sweeps
-        z = np.zeros_like(X[0])
-        for i in range(i1 - 1, i0 - 1, -1):
-            t = X[i] + G[i] @ tins[q]
-            z = Sinv[i] @ t - Wn[i + 1].T @ z
-            X[i] = z
-        E2.append(z)
-    xin = np.zeros_like(X[0])
-    for q in range(len(segs) - 1, -1, -1):    # incoming x from the right
-        i0, i1 = segs[q]
-        if q < len(segs) - 1:
-            for i in range(i0, i1):
-                X[i] = X[i] + Gb[i] @ xin
-        xin = E2[q] + Gb[i0] @ xin
-    return X.reshape(3 * n, -1)
 
 
 @pytest.mark.parametrize("radius", [1e4, 1e12])

@@ -123,13 +123,39 @@ def test_kernels_and_one_lm_iteration_against_the_oracle(pgo, oracle, case, layo
         s2.close()
 
 
+DIRECT_TALLY = dict(examples=0, direct=0, fell_back_in_iteration_1=0, fell_back_later=0)
+
+
+def restated_first_system(oracle, og, poses, fixed, method):
+    """the first LM system (initial poses, radius0 = 1e4; METHOD 2: the METHOD 1 system, oracle.lm_system has no other) solved
+    by the numpy restatement of the direct solve with one refinement step: (rho = |b - A y|_2 / |b|_2, model decrease
+    y.b - y.A y / 2), or None where its Cholesky factorisation breaks down or the result is not finite"""
+    from _direct_restatement import restate, system_matrix
+    sysm = oracle.lm_system(og, poses, poses, 1e4, method=min(method, 1), fixed_pose=fixed)
+    A = system_matrix(sysm)
+    b = np.array(sysm.b, np.float64)
+    try:
+        y = restate(sysm, og, fixed, b[:, None], 1)[:, 0]
+    except np.linalg.LinAlgError:
+        return None
+    if not np.isfinite(y).all():
+        return None
+    nb = np.linalg.norm(b)
+    return (float(np.linalg.norm(b - A @ y) / nb) if nb > 0 else 0.0), float(y @ b - 0.5 * (y @ (A @ y)))
+
+
 @settings(**dict(SETTINGS, max_examples=FUZZ_N or 20))
 @given(pose_graphs())
-def test_direct_solve_is_taken_or_refused_never_replaced(pgo, case):
+def test_direct_solve_is_taken_or_refused_never_replaced(pgo, oracle, case):
     """linear_solver = 2 on an arbitrary graph: either the handle IS on the direct solve and its LM iterations agree with
     PCG to 1e-10, or pgo_create fails with PGO_ERR_UNSUPPORTED (missing chain edge, no constant pose, too many edges
-    outside the chain ...) -- a silent fallback to PCG would hide a wrong answer about which solver ran"""
+    outside the chain ...) -- a silent fallback to PCG would hide a wrong answer about which solver ran.
+    The first LM system is also solved by the numpy restatement of the direct solve (_direct_restatement.restate): the
+    direct solve's residual of LM iteration 1 is bounded by the restatement's (these tiny random graphs are far worse
+    conditioned than any chain, so no fixed bound is known; 1e-14: a hundred roundings), and a fallback to PCG in
+    iteration 1 is accepted only where the restatement fails too."""
     poses, ia, ib, meas, kind, fixed, method = case
+    DIRECT_TALLY["examples"] += 1
     g = pgo.Graph.from_arrays(poses, ia, ib, meas, kind)
     kw = dict(method=method, fixed_pose=fixed, max_iters=2, pcg_rtol=1e-12, pcg_max_iters=100000)
     try:
@@ -147,6 +173,19 @@ def test_direct_solve_is_taken_or_refused_never_replaced(pgo, case):
     ref = pgo.Solver(g, pgo.Options(linear_solver=1, pcg_coarse_poses=0, **kw))
     sr = ref.solve()
     assert s.info().linear_solver == 2 and all(r["pcg_iters"] == 0 for r in s.iter_records()) or s.info().direct_fallbacks > 0
+    recs = s.iter_records()
+    DIRECT_TALLY["direct"] += 1
+    if recs:
+        first = restated_first_system(oracle, oracle_graph(oracle, g), np.asarray(poses, np.float64), fixed, method)
+        if recs[0]["pcg_iters"] > 0:      # LM iteration 1 was redone by PCG
+            DIRECT_TALLY["fell_back_in_iteration_1"] += 1
+            assert first is None or not first[1] > 0.0, ("the direct solve fell back in LM iteration 1 although the restatement solves that system", first)
+        else:
+            assert first is not None, "the restatement fails on a system the direct solve took"
+            note("LM iteration 1: direct solve residual %.2e, restatement %.2e" % (recs[0]["pcg_rel_residual"], first[0]))
+            assert recs[0]["pcg_rel_residual"] <= 10.0 * max(first[0], 1e-14), (recs[0]["pcg_rel_residual"], first[0])
+            DIRECT_TALLY["fell_back_later"] += int(s.info().direct_fallbacks > 0)
+    print("direct solve on random graphs so far:", DIRECT_TALLY)
     assert [a["step_ok"] for a in s.iter_records()] == [b["step_ok"] for b in ref.iter_records()]
     assert sm.final_cost == pytest.approx(sr.final_cost, rel=1e-7, abs=1e-12)
     assert np.abs(s.poses() - ref.poses()).max() < 1e-6 * max(1.0, np.abs(ref.poses()).max())

@@ -42,7 +42,7 @@ EXPORTS = [
     "pgo_batch_num_iter_records", "pgo_batch_get_iter_records", "pgo_lm_begin", "pgo_lm_step",
     "pgo_num_iter_records", "pgo_get_iter_records", "pgo_get_info", "pgo_get_poses", "pgo_set_poses", "pgo_get_switches",
     "pgo_write_switches",
-    "pgo_bench_eval", "pgo_bench_assemble", "pgo_bench_spmv", "pgo_bench_precond", "pgo_debug_precond", "pgo_debug_spmv", "pgo_debug_system_spmv", "pgo_debug_normal_eq",
+    "pgo_bench_eval", "pgo_bench_assemble", "pgo_bench_spmv", "pgo_bench_precond", "pgo_debug_precond", "pgo_debug_spmv", "pgo_debug_system_spmv", "pgo_debug_direct_solve", "pgo_debug_normal_eq",
     "pgo_debug_set_knob",
     "pgo_shard_plan", "pgo_shard_halo", "pgo_pose_order",
     "pgo_covariance_options_default", "pgo_pose_covariance",
@@ -109,7 +109,8 @@ class HandleInfo(C.Structure):
                 ("halo_overlap", C.c_int32), ("halo_send_rows", C.c_int64), ("halo_recv_rows", C.c_int64),
                 ("device_bytes", C.c_int64), ("host_enqueue_us_per_pcg_iter", C.c_double), ("pcg_graph_replay", C.c_int32),
                 ("linear_solver", C.c_int32), ("direct_rank", C.c_int32), ("direct_fallbacks", C.c_int32), ("direct_switched_at", C.c_int32), ("pcg_coarse_poses", C.c_int32), ("pcg_coarse_rank", C.c_int32),
-                ("pcg_single_reduction", C.c_int32), ("pcg_coarse_off_iters", C.c_int32)]
+                ("pcg_single_reduction", C.c_int32), ("pcg_coarse_off_iters", C.c_int32),
+                ("direct_separators", C.c_int32), ("direct_segments", C.c_int32), ("direct_refine_kernel", C.c_int32)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -269,6 +270,7 @@ def lib():
     L.pgo_debug_precond.argtypes = [vp, dp, dp]
     L.pgo_debug_spmv.argtypes = [vp, dp, dp]
     L.pgo_debug_system_spmv.argtypes = [vp, dp, dp, dp]
+    L.pgo_debug_direct_solve.argtypes = [vp, dp, C.c_int32, dp]
     L.pgo_debug_normal_eq.argtypes = [vp, dp, dp]
     L.pgo_shard_plan.argtypes = [C.c_int32, C.c_int32, ip, ip, C.c_int, C.c_int, C.c_int, ip, ip, ip, ip]
     L.pgo_shard_halo.argtypes = [C.c_int32, C.c_int32, ip, ip, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64),
@@ -694,6 +696,14 @@ class Solver:
         d2 = np.zeros_like(x) if want_d2 else None
         _check(lib().pgo_debug_system_spmv(self._h, _dp(x), _dp(y), _dp(d2)))
         return (y, d2) if want_d2 else y
+
+    def direct_solve(self, b, refine=-1):
+        """y = (H + D'D)^-1 b by the direct chain + low-rank solve at the current LM state (pgo_debug_direct_solve): refine
+        = -1 the handle's own refinement steps, 0 the raw Woodbury result, 1..3 that many"""
+        b = np.ascontiguousarray(b, np.float64)
+        y = np.zeros_like(b)
+        _check(lib().pgo_debug_direct_solve(self._h, _dp(b), int(refine), _dp(y)))
+        return y
 
     def precond(self, r):
         """z = M^-1 r with the preconditioner the next LM iteration applies (debug / restatement tests)"""

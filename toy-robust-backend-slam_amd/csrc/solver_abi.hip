@@ -413,6 +413,9 @@ int pgo_get_info(const pgo_t* h, pgo_handle_info* out) {
   out->pcg_coarse_poses = h->use_coarse ? h->co_agg : 0;
   out->pcg_coarse_rank = h->use_coarse ? h->co_K : 0;
   out->pcg_coarse_off_iters = h->co_off_iters;
+  out->direct_separators = h->direct ? h->dl_nsep : 0;
+  out->direct_segments = h->direct ? h->dl_nseg : 0;
+  out->direct_refine_kernel = h->direct ? (h->dl_pre2 ? 1 : 2) : 0;
   return PGO_OK;
 }
 
@@ -581,6 +584,46 @@ int pgo_debug_precond(pgo_t* h, const double* r_in, double* z_out) {
   if (h->perm.empty()) memcpy(z_out, ztmp.data(), ztmp.size() * sizeof(double));
   else h->to_caller(ztmp, z_out, 3);
   return PGO_OK;
+}
+
+// y = (H + D'D)^-1 b through direct_enqueue(), the launch sequence an LM iteration on the direct solve runs (eagerly: a
+// graph captured for LM keeps its own arguments and is neither used nor touched).  direct_enqueue() writes y, r, ap, the
+// gather vector and scal[8..9]; they are saved and put back, so that the LM loop finds what it left.
+int pgo_debug_direct_solve(pgo_t* h, const double* b_in, int32_t refine_steps, double* y_out) {
+  if (!h || !b_in || !y_out) return fail(PGO_ERR_INVALID_ARG, "pgo_debug_direct_solve: null");
+  if (refine_steps < -1 || refine_steps > 3) return fail(PGO_ERR_INVALID_ARG, "pgo_debug_direct_solve: refine_steps is -1 (the handle's own) or 0 .. 3");
+  if (!h->direct || !h->dl_ready) return fail(PGO_ERR_UNSUPPORTED, "pgo_debug_direct_solve: the handle is not on the direct solve");
+  if (!h->lin_valid) return fail(PGO_ERR_INVALID_ARG, "pgo_debug_direct_solve: call pgo_lm_begin first");
+  HIPC(hipSetDevice(h->device));
+  const size_t n3 = (size_t)3 * h->S.n_loc, npf = (size_t)dev::PS * h->n_full;   // (one rank, identity ordering: n_loc = N)
+  const size_t off_r = n3, off_ap = 2 * n3, off_pf = 3 * n3, off_scal = off_pf + npf, off_b = off_scal + N_SCAL;
+  double* save = nullptr;
+  if (hipMalloc((void**)&save, (off_b + n3) * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(PGO_ERR_NOMEM, "pgo_debug_direct_solve: hipMalloc");
+  }
+  auto run = [&]() -> int {
+    const hipMemcpyKind d2d = hipMemcpyDeviceToDevice;
+    HIPC(hipMemcpyAsync(save, h->y, n3 * sizeof(double), d2d, h->stream));
+    HIPC(hipMemcpyAsync(save + off_r, h->r, n3 * sizeof(double), d2d, h->stream));
+    HIPC(hipMemcpyAsync(save + off_ap, h->ap, n3 * sizeof(double), d2d, h->stream));
+    HIPC(hipMemcpyAsync(save + off_pf, h->p_full, npf * sizeof(double), d2d, h->stream));
+    HIPC(hipMemcpyAsync(save + off_scal, h->scal, N_SCAL * sizeof(double), d2d, h->stream));
+    HIPC(hipMemcpyAsync(save + off_b, b_in, n3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    PGOC(h->prepare_system());
+    PGOC(h->direct_enqueue(save + off_b, refine_steps < 0 ? h->dl_refine : refine_steps));
+    HIPC(hipMemcpyAsync(y_out, h->y, n3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPC(hipMemcpyAsync(h->y, save, n3 * sizeof(double), d2d, h->stream));
+    HIPC(hipMemcpyAsync(h->r, save + off_r, n3 * sizeof(double), d2d, h->stream));
+    HIPC(hipMemcpyAsync(h->ap, save + off_ap, n3 * sizeof(double), d2d, h->stream));
+    HIPC(hipMemcpyAsync(h->p_full, save + off_pf, npf * sizeof(double), d2d, h->stream));
+    HIPC(hipMemcpyAsync(h->scal, save + off_scal, N_SCAL * sizeof(double), d2d, h->stream));
+    return h->sync();
+  };
+  const int st = run();
+  if (st != PGO_OK) (void)hipStreamSynchronize(h->stream);
+  (void)hipFree(save);
+  return st;
 }
 
 static int time_launches(pgo_handle* h, int reps, const std::function<void()>& launch, double* ms_avg) {

@@ -1,9 +1,10 @@
 // The direct linear solve for small chain-like graphs (kernels: direct.hip.h; choice and buffers: solver_create.hip).
 #include "solver_handle.hip.h"
 
-// (H + D'D) y = gs by Woodbury on chain + low rank, then iterative refinement against the assembled matrix; leaves the
-// true residual in r (the model-decrease identity of lm_iteration_tail reads it) and |r|^2, |gs|^2 in scal[8..9].
-int pgo_handle::direct_enqueue() {
+// (H + D'D) y = rhs by Woodbury on chain + low rank, then refine steps of iterative refinement against the assembled
+// matrix; leaves the true residual in r (the model-decrease identity of lm_iteration_tail reads it) and |r|^2, |rhs|^2 in
+// scal[8..9].  LM passes gs and dl_refine; pgo_debug_direct_solve any right-hand side and 0..3 steps.
+int pgo_handle::direct_enqueue(const double* rhs, int refine) {
   const int n = S.n_loc, K = dl_K, Kp = dl_Kp, nb = dl_Kp / 32;
   dev::DlrArgs A;
   A.n = n;
@@ -40,7 +41,7 @@ int pgo_handle::direct_enqueue() {
   PGOC(check_launch("k_dlr_factor"));
   hipLaunchKernelGGL(dev::k_dlr_prefix<>, dim3(1), dim3(128), 0, stream, (const double*)dl_fac, n, dl_nseg, dl_seglen, dl_pre);
   PGOC(check_launch("k_dlr_prefix"));
-  const bool one_launch = dl_refine > 0 && dl_pre2 != nullptr;   // the refinement's single column: k_dlr_solve1
+  const bool one_launch = refine > 0 && dl_pre2 != nullptr;   // the refinement's single column: k_dlr_solve1
   if (one_launch) {
     hipLaunchKernelGGL(dev::k_dlr_prefix<>, dim3(1), dim3(512), 0, stream, (const double*)dl_fac, n, dl_nseg2, dl_seglen2, dl_pre2);
     PGOC(check_launch("k_dlr_prefix (fine segments)"));
@@ -62,7 +63,7 @@ int pgo_handle::direct_enqueue() {
   C.vrec = dl_vrec;
   C.va = dl_va;
   C.vb = dl_vb;
-  C.rhs_b = gs;
+  C.rhs_b = rhs;
   C.rhs_sub = nullptr;
   C.X = dl_Z;
   C.E = dl_E;
@@ -125,7 +126,7 @@ int pgo_handle::direct_enqueue() {
     PGOC(check_launch("k_scatter_owned"));
     return spmv_enqueue(p_full, ap, part[0], 1, nullptr);
   };
-  for (int it = 0; it < dl_refine; ++it) {
+  for (int it = 0; it < refine; ++it) {
     PGOC(residual_product());
     int xld = 64;   // layout of the single column in dl_x1: [3n][64] (batched kernels) or a plain vector (k_dlr_solve1)
     if (one_launch) {
@@ -135,7 +136,7 @@ int pgo_handle::direct_enqueue() {
       Q.n = n;
       Q.nseg = dl_nseg2;
       Q.seglen = dl_seglen2;
-      Q.rhs_b = gs;
+      Q.rhs_b = rhs;
       Q.rhs_sub = ap;
       Q.x = dl_x1;
       Q.nsep = dl_nsep;
@@ -169,10 +170,10 @@ int pgo_handle::direct_enqueue() {
     PGOC(check_launch("k_dlr_combine"));
   }
   PGOC(residual_product());
-  hipLaunchKernelGGL(dev::k_dlr_resid<>, dim3((3 * n + 255) / 256), dim3(256), 0, stream, (int64_t)3 * n, (const double*)gs, (const double*)ap, r);
+  hipLaunchKernelGGL(dev::k_dlr_resid<>, dim3((3 * n + 255) / 256), dim3(256), 0, stream, (int64_t)3 * n, rhs, (const double*)ap, r);
   PGOC(check_launch("k_dlr_resid"));
   hipLaunchKernelGGL(dev::k_dot<>, dim3(g_flat), dim3(dev::WG), 0, stream, (int64_t)3 * n, (const double*)r, (const double*)r, part[2]);
-  hipLaunchKernelGGL(dev::k_dot<>, dim3(g_flat), dim3(dev::WG), 0, stream, (int64_t)3 * n, (const double*)gs, (const double*)gs, part[4]);
+  hipLaunchKernelGGL(dev::k_dot<>, dim3(g_flat), dim3(dev::WG), 0, stream, (int64_t)3 * n, rhs, rhs, part[4]);
   PGOC(check_launch("k_dot"));
   return reduce_to_scal({{part[2], g_flat, 0}, {part[4], g_flat, 0}}, 8);
 }
@@ -186,7 +187,7 @@ int pgo_handle::direct_solve() {
     if (!dl_graph_exec) {
       hipGraph_t gr = nullptr;
       HIPC(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-      const int st_cap = direct_enqueue();
+      const int st_cap = direct_enqueue(gs, dl_refine);
       const hipError_t e_end = hipStreamEndCapture(stream, &gr);
       hipError_t e_inst = hipSuccess;
       if (st_cap == PGO_OK && e_end == hipSuccess) {
@@ -201,7 +202,7 @@ int pgo_handle::direct_solve() {
     }
     if (dl_graph_exec) HIPC(hipGraphLaunch(dl_graph_exec, stream));
   }
-  if (!dl_graph_exec) PGOC(direct_enqueue());
+  if (!dl_graph_exec) PGOC(direct_enqueue(gs, dl_refine));
   if (dl_fail_at > 0 && iter == dl_fail_at)   // test hook ("direct_fail_at"): a direct solve that returns NaNs
     HIPC(hipMemsetAsync(y, 0xFF, (size_t)3 * S.n_loc * sizeof(double), stream));
   return PGO_OK;

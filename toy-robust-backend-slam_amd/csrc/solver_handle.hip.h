@@ -506,7 +506,7 @@ struct pgo_handle {
   int pcg(int* iters, double* rel);
   int direct_setup(int32_t N, bool switch_now = false);
   int direct_solve();
-  int direct_enqueue();
+  int direct_enqueue(const double* rhs, int refine);
   int factor_chain();
   int prepare_preconditioner();
   void fill_summary(pgo_summary* s) const;
