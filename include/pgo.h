@@ -381,6 +381,38 @@ int pgo_batch_set_losses(pgo_batch_t* b, int32_t n_classes, const pgo_loss* loss
 int32_t pgo_batch_num_iter_records(const pgo_batch_t* b, int32_t problem);
 int pgo_batch_get_iter_records(const pgo_batch_t* b, int32_t problem, pgo_iter_record* out, int32_t cap);
 
+/* ------------------------------------------------------------ active sets
+ * Which residual blocks (edges) and which parameter blocks (poses) the handle's problem has, from now on -- the layer
+ * managers' many ceres::Solve calls over subsets of the loop edges and over windows of poses of the SAME graph
+ * (src/simple_layer_manager.cpp:457-622, src/layer_manager.cpp:104-179,602-654) without a new handle per call.
+ *   edge_active   E bytes in the caller's edge order, non-zero = the edge is a residual block; NULL = all.
+ *   pose_constant N bytes in the caller's pose order, non-zero = SetParameterBlockConstant; NULL = none.
+ * Batch: the arrays are the problems' edges / poses concatenated in problem order, like pgo_batch_set_losses.
+ * - An inactive edge is not in the problem: it adds nothing to the cost, the gradient, J'J, the Jacobi scale or the DCS /
+ *   loss bookkeeping; its rows in pgo_eval's r / J outputs are exactly 0; a non-finite residual or Jacobian of it is NOT an
+ *   evaluation failure (a candidate loop at |sin delta| = 1 does not poison a solve that does not use it).  pgo_edge_chi2
+ *   ignores the mask: it is the gate that decides what to activate.
+ * - Resolved constant set = {opt.fixed_pose if >= 0} + pose_constant + every pose with no active edge (a parameter block Ceres
+ *   would not have in the problem: it neither makes the system singular nor counts as "a pose without edges").  Constant
+ *   poses never move (bitwise).  An active edge between two constant poses still counts in the cost (Ceres' fixed_cost).
+ * - Gauge: pose_constant alone may anchor a window that does not contain opt.fixed_pose; a problem left without an anchor is
+ *   the caller's business, exactly as fixed_pose = -1 is.
+ * - A solve begun with pgo_lm_begin becomes stale, as after pgo_set_losses: pgo_lm_step returns PGO_ERR_INVALID_ARG until
+ *   pgo_lm_begin runs again.  The poses are kept.
+ * - pgo_set_losses / pgo_batch_set_losses leave the active set as it is, in either order of the calls.
+ * - pgo_set_active(h, NULL, NULL) restores the handle completely: a pgo_solve after it gives bitwise what a fresh handle gives.
+ * - The direct solve (linear_solver 2) stays in force while every edge of its odometry chain is active (inactive loop edges
+ *   are zero columns of the low-rank term); while a chain edge is inactive the handle solves by PCG and pgo_handle_info says
+ *   linear_solver 1.  pgo_pose_covariance works on the active problem: resolved-constant poses have zero blocks.
+ * - Errors: PGO_ERR_UNSUPPORTED for METHOD 2, a communicator or PGO_FORCE_COLLECTIVES=1; PGO_ERR_INVALID_ARG for a null
+ *   handle.  Nothing changes on error.                                                                              */
+int pgo_set_active(pgo_t* h, const uint8_t* edge_active_or_null, const uint8_t* pose_constant_or_null);             /* [gpu] */
+int pgo_batch_set_active(pgo_batch_t* b, const uint8_t* edge_active_or_null, const uint8_t* pose_constant_or_null); /* [gpu] */
+/* the resolved sets, pure logic (what the two calls above apply): constant_out[i] != 0 for the resolved constant poses */
+int pgo_active_plan(int32_t n_poses, int32_t n_edges, const int32_t* ia, const int32_t* ib,
+                    const uint8_t* edge_active_or_null, const uint8_t* pose_constant_or_null, int32_t fixed_pose,
+                    uint8_t* constant_out /* N */, int32_t* n_active_edges, int32_t* n_free_poses);             /* [host] */
+
 /* the same minimiser, resumable: (re)start with pgo_lm_begin, then run LM
  * iterations in slices (bench.py times slices); returns *done != 0 once a
  * termination test fired.                                                        */
@@ -424,6 +456,8 @@ typedef struct pgo_handle_info {
   int32_t direct_segments;           /* direct solve: segments of the chain sweeps (32, fewer on chains shorter than that)   */
   int32_t direct_refine_kernel;      /* direct solve: the refinement's column is solved by 1 = k_dlr_solve1 (one launch, up to
                                         4096 poses), 2 = the batched sweep kernels; 0 = not on the direct solve             */
+  int32_t n_active_edges;            /* resolved (pgo_set_active): residual blocks of the handle's problem                   */
+  int32_t n_constant_poses;          /* resolved: constant poses -- opt.fixed_pose, pose_constant, poses without an active edge */
 } pgo_handle_info;
 int pgo_get_info(const pgo_t* h, pgo_handle_info* out);                           /* [host] */
 
@@ -445,7 +479,7 @@ int pgo_set_poses(pgo_t* h, const double* poses_xyt);                           
  * while that lowers it; a true residual that stops falling above rtol is accepted up to 1e-5 (the double-precision floor
  * of an ill-conditioned system, reported in max_rel_residual), above that it is PGO_ERR_NUMERIC.  The LM state is left as
  * it was: pgo_lm_step afterwards gives bitwise the records and poses it gives without the call.
- * Errors: PGO_ERR_UNSUPPORTED for world > 1, fixed_pose = -1, info_weighting = 1 (not accurate enough yet) and batched
+ * Errors: PGO_ERR_UNSUPPORTED for world > 1, no constant pose (fixed_pose = -1 and none set by pgo_set_active), info_weighting = 1 and batched
  * handles; PGO_ERR_INVALID_ARG for a bad index or a null pointer (duplicate indices are allowed); PGO_ERR_NUMERIC for a
  * non-finite pose or Jacobian, a pose without edges, a PCG breakdown, a stalled true residual or max_iters reached
  * (pgo_last_error names the pose).                                                                                       */

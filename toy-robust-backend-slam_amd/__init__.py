@@ -22,7 +22,7 @@ from . import _build
 
 __all__ = ["PgoError", "Options", "Summary", "IterRecord", "ReadG2O", "Graph", "Solver", "Batch", "Comm", "lib", "build",
            "HandleInfo", "synth_manhattan", "solve_batch", "shard_plan", "shard_halo", "pose_order", "set_knob", "KernelStats", "EXPORTS", "TERMINATION",
-           "CovarianceOptions", "CovarianceReport", "Loss", "LOSS_TYPES"]
+           "CovarianceOptions", "CovarianceReport", "Loss", "LOSS_TYPES", "active_plan"]
 
 EDGE_ODOMETRY, EDGE_CLOSURE, EDGE_BOGUS = 0, 1, 2
 TERMINATION = {1: "CONVERGENCE_FTOL", 2: "CONVERGENCE_GTOL", 3: "CONVERGENCE_PTOL", 4: "NO_CONVERGENCE",
@@ -47,6 +47,7 @@ EXPORTS = [
     "pgo_shard_plan", "pgo_shard_halo", "pgo_pose_order",
     "pgo_covariance_options_default", "pgo_pose_covariance",
     "pgo_loss_evaluate", "pgo_set_losses", "pgo_batch_set_losses",
+    "pgo_set_active", "pgo_batch_set_active", "pgo_active_plan",
 ]
 LOSS_TYPES = {"trivial": 0, "huber": 1, "softlone": 2, "cauchy": 3, "arctan": 4, "tukey": 5}   # pgo_loss_type
 
@@ -110,7 +111,8 @@ class HandleInfo(C.Structure):
                 ("device_bytes", C.c_int64), ("host_enqueue_us_per_pcg_iter", C.c_double), ("pcg_graph_replay", C.c_int32),
                 ("linear_solver", C.c_int32), ("direct_rank", C.c_int32), ("direct_fallbacks", C.c_int32), ("direct_switched_at", C.c_int32), ("pcg_coarse_poses", C.c_int32), ("pcg_coarse_rank", C.c_int32),
                 ("pcg_single_reduction", C.c_int32), ("pcg_coarse_off_iters", C.c_int32),
-                ("direct_separators", C.c_int32), ("direct_segments", C.c_int32), ("direct_refine_kernel", C.c_int32)]
+                ("direct_separators", C.c_int32), ("direct_segments", C.c_int32), ("direct_refine_kernel", C.c_int32),
+                ("n_active_edges", C.c_int32), ("n_constant_poses", C.c_int32)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -283,6 +285,9 @@ def lib():
     L.pgo_loss_evaluate.argtypes = [C.POINTER(Loss), C.c_double, dp]
     L.pgo_set_losses.argtypes = [vp, C.c_int32, C.POINTER(Loss), bp]
     L.pgo_batch_set_losses.argtypes = [vp, C.c_int32, C.POINTER(Loss), bp]
+    L.pgo_set_active.argtypes = [vp, bp, bp]
+    L.pgo_batch_set_active.argtypes = [vp, bp, bp]
+    L.pgo_active_plan.argtypes = [C.c_int32, C.c_int32, ip, ip, bp, bp, C.c_int32, bp, ip, ip]
     _LIB = L
     return L
 
@@ -441,6 +446,30 @@ def shard_plan(n_poses, ia, ib, world, rank, row_align=1):
     return lo.value, hi.value, nl.value, nc.value
 
 
+def _mask(a, n, what):
+    """a byte mask of n entries (any array-like of truth values), or None"""
+    if a is None:
+        return None
+    m = np.ascontiguousarray(np.asarray(a).reshape(-1) != 0, np.uint8)
+    if m.size != n:
+        raise ValueError(f"{what}: {m.size} entries, expected {n}")
+    return m
+
+
+def active_plan(n_poses, ia, ib, edge_active=None, pose_constant=None, fixed_pose=0):
+    """pgo_active_plan (host only): what Solver.set_active / Batch.set_active resolve their masks to.
+    Returns (constant[n_poses] uint8, n_active_edges, n_free_poses)."""
+    ia = np.ascontiguousarray(ia, np.int32)
+    ib = np.ascontiguousarray(ib, np.int32)
+    ea = _mask(edge_active, len(ia), "edge_active")
+    pc = _mask(pose_constant, n_poses, "pose_constant")
+    const = np.zeros(max(n_poses, 0), np.uint8)
+    na, nf = C.c_int32(), C.c_int32()
+    _check(lib().pgo_active_plan(n_poses, len(ia), _ip(ia), _ip(ib), _bp(ea) if ea is not None else None,
+                                 _bp(pc) if pc is not None else None, fixed_pose, _bp(const), C.byref(na), C.byref(nf)))
+    return const, na.value, nf.value
+
+
 def set_knob(name: str, value: int = -1):
     """test hook (pgo_debug_set_knob): process-wide, read when a handle is created; value < 0 = library default"""
     _check(lib().pgo_debug_set_knob(name.encode(), int(value)))
@@ -527,6 +556,20 @@ class Batch:
         n, arr, cls, keep = _loss_args(losses, edge_class, sum(g.n_edges for g in self.graphs))
         _check(lib().pgo_batch_set_losses(self._h, n, arr, cls))
 
+    def set_active(self, edge_active=None, pose_constant=None):
+        """pgo_batch_set_active: which edges / constant poses every problem has from now on.  Each argument: None, the
+        concatenated mask over all problems, or a list with one mask (or None = all edges / no pose) per problem."""
+        def cat(m, sizes, what):
+            if m is None:
+                return None
+            if isinstance(m, (list, tuple)) and len(m) == self.n and any(x is None or np.ndim(x) > 0 for x in m):
+                fill = 1 if what == "edge_active" else 0
+                m = np.concatenate([np.full(k, fill, np.uint8) if x is None else _mask(x, k, what) for x, k in zip(m, sizes)])
+            return _mask(m, sum(sizes), what)
+        ea = cat(edge_active, [g.n_edges for g in self.graphs], "edge_active")
+        pc = cat(pose_constant, [g.n_poses for g in self.graphs], "pose_constant")
+        _check(lib().pgo_batch_set_active(self._h, _bp(ea) if ea is not None else None, _bp(pc) if pc is not None else None))
+
     def close(self):
         if getattr(self, "_h", None):
             lib().pgo_batch_destroy(self._h)
@@ -580,6 +623,14 @@ class Solver:
         lm_begin is stale afterwards."""
         n, arr, cls, keep = _loss_args(losses, edge_class, self.n_edges)
         _check(lib().pgo_set_losses(self._h, n, arr, cls))
+
+    def set_active(self, edge_active=None, pose_constant=None):
+        """pgo_set_active: edge_active = a mask over the edges (truthy = a residual block; None = all), pose_constant = a
+        mask over the poses (truthy = SetParameterBlockConstant; None = none).  Poses without an active edge are constant
+        too.  set_active() restores the handle.  A solve begun with lm_begin is stale afterwards."""
+        ea = _mask(edge_active, self.n_edges, "edge_active")
+        pc = _mask(pose_constant, self.n_poses, "pose_constant")
+        _check(lib().pgo_set_active(self._h, _bp(ea) if ea is not None else None, _bp(pc) if pc is not None else None))
 
     def close(self):
         if getattr(self, "_h", None):

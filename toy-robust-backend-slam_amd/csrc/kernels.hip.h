@@ -204,6 +204,7 @@ __device__ __forceinline__ double sum_partials_bcast(const double* __restrict__ 
 }
 
 // ------------------------------------------------------------------- K1
+constexpr unsigned EDGE_INACTIVE = 16u;   // flags bit 4: the edge is not a residual block of the handle's problem (pgo_set_active)
 struct EdgeArgs {
   const double* poses;    // [.. x 3] global pose positions
   const int32_t* ia;
@@ -212,7 +213,7 @@ struct EdgeArgs {
   const double* my;
   const double* mt;
   const uint8_t* flags;   // bit0 robust edge (DCS for METHOD 1, switchable for METHOD 2), bit1 cost counted on this rank,
-                          // bits 2-3 loss class (read by k_edge_eval<*, *, true> only)
+                          // bits 2-3 loss class, bit 4 inactive (pgo_set_active) -- both read by k_edge_eval<*, *, true> only
   int32_t n_edges;
   int32_t apply_loss;
   double phi;
@@ -279,7 +280,21 @@ __global__ __launch_bounds__(WG) void k_edge_eval(EdgeArgs A, double* __restrict
   const int64_t e0 = (int64_t)blk * WG;
   const int64_t e = live ? e0 + tid : (int64_t)A.n_edges;
   double cost = 0.0;
-  if (e < A.n_edges) {
+  // pgo_set_active (handles with an edge mask run the LOSSES instantiations): an inactive edge is not in the problem -- no pose
+  // gathers, no trigonometry, an all-zero record (K2 sums it in its fixed order), cost 0, and no part in the `bad` flag
+  bool in_problem = true;
+  if constexpr (LOSSES) {
+    if (e < A.n_edges && (A.flags[e] & EDGE_INACTIVE)) {
+      in_problem = false;
+      if (WITH_JAC) {
+        double* st = stage + tid * RL;
+#pragma unroll
+        for (int i = 0; i < RN; ++i) st[i] = 0.0;
+      }
+      if (A.cost_out) A.cost_out[e] = 0.0;
+    }
+  }
+  if (e < A.n_edges && in_problem) {
     const int a = A.ia[e], b = A.ib[e];
     const double dx = A.mx[e], dy = A.my[e], dth = A.mt[e];
     const unsigned fl = A.flags[e];

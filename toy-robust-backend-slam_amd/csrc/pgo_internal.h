@@ -48,7 +48,8 @@ struct ShardStructure {
   std::vector<int32_t> orig_edge;       // local -> caller's edge index
   std::vector<int32_t> ia, ib;          // global pose positions
   std::vector<double> mx, my, mt;       // measurement planes
-  std::vector<uint8_t> flags;           // bit0: DCS applies, bit1: cost counted on this rank
+  std::vector<uint8_t> flags;           // bit0: DCS applies, bit1: cost counted on this rank, bits 2-3: loss class (pgo_set_losses),
+                                        // bit4: inactive (pgo_set_active)
 
   // incidences of the owned rows (row-major):  row i -> [inc_ptr[i-lo], inc_ptr[i-lo+1])
   // each incidence = (local edge, side) ; side 0: row is Edge::a, 1: row is Edge::b

@@ -25,7 +25,7 @@ int pgo_handle::set_losses(int32_t n_classes, const pgo_loss* losses, const uint
   const int64_t EL = S.n_edges_local;
   for (int64_t k = 0; k < EL; ++k) {
     const int c = edge_class ? edge_class[S.orig_edge[k]] : std::min<int>(kind_local[k], n_classes - 1);
-    S.flags[k] = (uint8_t)((S.flags[k] & 3u) | ((unsigned)c << 2));
+    S.flags[k] = (uint8_t)((S.flags[k] & (3u | dev::EDGE_INACTIVE)) | ((unsigned)c << 2));   // (bit 4: pgo_set_active's mask stays)
   }
   lin_valid = false;
   lm_active = false;
@@ -33,6 +33,108 @@ int pgo_handle::set_losses(int32_t n_classes, const pgo_loss* losses, const uint
   HIPC(hipSetDevice(device));
   PGOC(upload(e_flags, S.flags));
   return sync();
+}
+
+// pgo_set_active / pgo_batch_set_active.  edge_active: the caller's edge order (a batch: the union's, which is the problems'
+// edges concatenated); pose_constant: the caller's pose order (a batch: the union's rows).  Everything is resolved on the host
+// before anything changes; then bit 4 of the local edges' flags and the constant-row mask are rewritten, the list of dead
+// coarse aggregates follows the resolved constant set, the direct solve steps aside while an edge of its chain is inactive,
+// and the running solve (if any) is stale.  Both NULL: the handle is as it was created.
+int pgo_handle::set_active(const uint8_t* edge_active, const uint8_t* pose_constant) {
+  if (opt.method == 2) return fail(PGO_ERR_UNSUPPORTED, "pgo_set_active: METHOD 0 and 1 only");
+  if (comm || force_collectives) return fail(PGO_ERR_UNSUPPORTED, "pgo_set_active: one rank without a communicator only");
+  HIPC(hipSetDevice(device));
+  const int64_t EL = S.n_edges_local, N = S.n_poses;   // (one rank: every edge is local, every row owned)
+  const bool restore = !edge_active && !pose_constant;
+  // resolved sets
+  std::vector<uint8_t> cst;
+  int32_t n_act = 0, n_cst = 0;
+  bool anchor = false, chain_cut = false;
+  {
+    std::vector<uint8_t> used((size_t)N, 0);
+    for (int64_t k = 0; k < EL; ++k)
+      if (!edge_active || edge_active[S.orig_edge[k]]) {
+        used[S.ia[k]] = used[S.ib[k]] = 1;
+        ++n_act;
+      }
+    cst.assign((size_t)N, 0);
+    if (!fixed_mask_h.empty()) cst = fixed_mask_h;   // a batch: every problem's anchor and the padding rows
+    if (fixed_internal >= 0) cst[fixed_internal] = 1;
+    for (int64_t i = 0; i < N; ++i) {
+      const int64_t r = perm.empty() ? i : (int64_t)perm[i];
+      if (pose_constant && pose_constant[i]) {
+        cst[r] = 1;
+        anchor = true;
+      }
+      if (!used[r]) cst[r] = 1;
+    }
+    for (int64_t i = 0; i < N; ++i) n_cst += cst[i];
+  }
+  if (edge_active && (direct || dl_possible || dl_ready || act_chain_cut)) {
+    // the direct solve's chain: the first local edge between every pair of consecutive poses (direct_setup)
+    std::vector<uint8_t> seen((size_t)N, 0);
+    for (int64_t k = 0; k < EL && !chain_cut; ++k) {
+      const int32_t lo_p = std::min(S.ia[k], S.ib[k]), hi_p = std::max(S.ia[k], S.ib[k]);
+      if (hi_p == lo_p + 1 && !seen[lo_p]) {
+        seen[lo_p] = 1;
+        chain_cut = !edge_active[S.orig_edge[k]];
+      }
+    }
+  }
+  std::vector<int32_t> dead;
+  int32_t* dead_buf = nullptr;
+  const bool coarse_built = (use_coarse || co_cov_ready) && !co_multi;
+  // device buffers this call may need, before anything changes
+  if (!restore && !batch_mode && !act_mask) PGOC(dalloc(&act_mask, N));
+  if (coarse_built) {
+    std::vector<uint8_t> keep;
+    keep.swap(act_const_h);
+    if (!restore) act_const_h = cst;
+    coarse_dead_list(&dead);
+    act_const_h.swap(keep);
+    if ((int)dead.size() > co_dead_cap) PGOC(dalloc(&dead_buf, co_nagg));   // (once per handle: every later list fits)
+  }
+  // apply
+  if (dead_buf) {
+    co_dead = dead_buf;
+    co_dead_cap = co_nagg;
+  }
+  for (int64_t k = 0; k < EL; ++k) {
+    const bool on = !edge_active || edge_active[S.orig_edge[k]];
+    S.flags[k] = (uint8_t)((S.flags[k] & ~dev::EDGE_INACTIVE) | (on ? 0u : dev::EDGE_INACTIVE));
+  }
+  act_edges = edge_active != nullptr && n_act < EL;
+  act_anchor = anchor;
+  n_active_edges = n_act;
+  n_constant_poses = n_cst;
+  if (restore) {
+    act_const_h.clear();
+    if (!batch_mode) fixed_mask = nullptr;
+  } else {
+    act_const_h = cst;
+    if (!batch_mode) fixed_mask = act_mask;
+  }
+  if (chain_cut != act_chain_cut) {
+    if (chain_cut) {
+      act_saved_direct = direct;
+      act_saved_possible = dl_possible;
+      direct = false;
+      dl_possible = false;
+    } else {
+      direct = act_saved_direct;
+      dl_possible = act_saved_possible;
+    }
+    act_chain_cut = chain_cut;
+  }
+  lin_valid = false;
+  lm_active = false;
+  if (EL > 0) PGOC(upload(e_flags, S.flags));
+  if (fixed_mask) PGOC(upload(fixed_mask, restore ? fixed_mask_h : act_const_h));
+  if (coarse_built) {
+    co_ndead = (int)dead.size();
+    PGOC(upload(co_dead, dead));
+  }
+  return sync();   // (`dead` dies with this scope)
 }
 
 // ====================================================================== C-ABI
@@ -255,6 +357,11 @@ int pgo_set_losses(pgo_t* h, int32_t n_classes, const pgo_loss* losses, const ui
   return h->set_losses(n_classes, losses, edge_class);
 }
 
+int pgo_set_active(pgo_t* h, const uint8_t* edge_active, const uint8_t* pose_constant) {
+  if (!h) return fail(PGO_ERR_INVALID_ARG, "pgo_set_active: null handle");
+  return h->set_active(edge_active, pose_constant);
+}
+
 int pgo_edge_chi2(pgo_t* h, const double* poses_or_null, double* chi2_out) {
   if (!h || !chi2_out) return fail(PGO_ERR_INVALID_ARG, "pgo_edge_chi2: null");
   if (!h->e_info) return fail(PGO_ERR_INVALID_ARG, "pgo_edge_chi2: the handle was created without information matrices");
@@ -416,6 +523,8 @@ int pgo_get_info(const pgo_t* h, pgo_handle_info* out) {
   out->direct_separators = h->direct ? h->dl_nsep : 0;
   out->direct_segments = h->direct ? h->dl_nseg : 0;
   out->direct_refine_kernel = h->direct ? (h->dl_pre2 ? 1 : 2) : 0;
+  out->n_active_edges = h->n_active_edges;
+  out->n_constant_poses = h->n_constant_poses;
   return PGO_OK;
 }
 

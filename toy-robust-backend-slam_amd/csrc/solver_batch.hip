@@ -392,6 +392,25 @@ int pgo_batch_set_losses(pgo_batch_t* b, int32_t n_classes, const pgo_loss* loss
   return b->U->set_losses(n_classes, losses, edge_class);   // (the union's edges are the problems' edges concatenated)
 }
 
+// pgo_set_active for the whole batch: the masks of problem k cover its own edges / poses; its pose mask ORs into the rows of
+// that problem (anchors and padding rows stay constant)
+int pgo_batch_set_active(pgo_batch_t* b, const uint8_t* edge_active, const uint8_t* pose_constant) {
+  if (!b) return fail(PGO_ERR_INVALID_ARG, "pgo_batch_set_active: null");
+  pgo_handle& H = *b->U;
+  std::vector<uint8_t> rows;
+  if (pose_constant) {
+    rows.assign((size_t)H.S.n_poses, 0);
+    int64_t off = 0;
+    for (int32_t k = 0; k < b->n; ++k) {
+      memcpy(&rows[(size_t)b->row0[k]], pose_constant + off, (size_t)b->npos[k]);
+      off += b->npos[k];
+    }
+  }
+  PGOC(H.set_active(edge_active, pose_constant ? rows.data() : nullptr));
+  b->begun = false;
+  return PGO_OK;
+}
+
 int32_t pgo_batch_num_iter_records(const pgo_batch_t* b, int32_t k) {
   return (b && k >= 0 && k < b->n) ? (int32_t)b->st[k].recs.size() : 0;
 }

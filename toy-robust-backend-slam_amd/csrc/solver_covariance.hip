@@ -179,7 +179,7 @@ int pgo_pose_covariance(pgo_t* h, int32_t n, const int32_t* poses, const pgo_cov
   // information weighting: even the columns whose true residual reaches 1e-5 differ from a sparse direct inverse by ~1e-3 on
   // INTEL (others stall at 2e-5) -- refused rather than returning blocks of that quality
   if (h->info_mode) return fail(PGO_ERR_UNSUPPORTED, "pgo_pose_covariance: not available with info_weighting = 1");
-  if (h->fixed_internal < 0)
+  if (!h->has_anchor())   // (opt.fixed_pose, or a pose made constant by pgo_set_active)
     return fail(PGO_ERR_UNSUPPORTED, "pgo_pose_covariance: fixed_pose = -1 leaves the gauge free (J'J is singular)");
   const int64_t N = h->S.n_poses;
   for (int32_t k = 0; k < n; ++k)

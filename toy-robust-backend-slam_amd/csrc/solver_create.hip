@@ -398,6 +398,16 @@ int pgo_handle::create(int32_t N, const double* poses_h, int32_t E, const int32_
     PGOC(upload(fixed_mask, fixed_mask_h));
   }
   if (batch_mode) PGOC(dalloc(&edge_cost, std::max<int64_t>(EL, 1)));
+  {  // what pgo_handle_info reports while no active set is in force: every edge, opt.fixed_pose + the poses without an edge
+     // (one numbering throughout: with the pose ordering on, ia / ib were replaced by their renumbered copies above, so they
+     // index poses as fixed_internal and fixed_mask_h do)
+    std::vector<uint8_t> used((size_t)N, 0);
+    for (int32_t e = 0; e < E; ++e) used[ia[e]] = used[ib[e]] = 1;
+    n_active_edges = E;
+    n_constant_poses = 0;
+    for (int32_t i = 0; i < N; ++i)
+      n_constant_poses += (i == fixed_internal || (!fixed_mask_h.empty() && fixed_mask_h[i]) || !used[i]) ? 1 : 0;
+  }
   PGOC(direct_setup(N));
   PGOC(coarse_setup(E, ia, ib));   // (after the direct solver's decision: auto adds the coarse level only to solves that stay on PCG)
   return sync();
@@ -492,18 +502,12 @@ int pgo_handle::coarse_setup(int32_t E, const int32_t* ia, const int32_t* ib) {
   // aggregates with no pose in the coarse space: every pose edge-less (no real incidence; k_coarse_basis tests the same through
   // H_ii = 0) or the constant pose.  Their block (I, I) is zero; k_coarse_dead puts identity there, as on the padding.
   std::vector<int32_t> dead;
-  for (int Il = 0; Il < co_nown; ++Il) {
-    bool any = false;
-    for (int32_t r = Il * co_agg; r < std::min<int64_t>(NL, (int64_t)(Il + 1) * co_agg) && !any; ++r) {
-      if (S.lo + r == fixed_internal) continue;
-      for (int32_t q = S.inc_ptr[r]; q < S.inc_ptr[r + 1] && !any; ++q) any = S.inc_edge[q] >= 0;
-    }
-    if (!any) dead.push_back(co_aoff + Il);
-  }
+  coarse_dead_list(&dead);
   if (multi) PGOC(coarse_setup_multi(E, ia, ib, world, rank, cbi, cbj, dead, &dead));   // (dead: every rank's, afterwards)
   co_ndead = (int)dead.size();
   if (co_ndead) {
     PGOC(dalloc(&co_dead, co_ndead));
+    co_dead_cap = co_ndead;
     PGOC(upload(co_dead, dead));
   }
   PGOC(dalloc(&co_pb, 5 * (multi ? N : NL)));
@@ -543,6 +547,25 @@ int pgo_handle::coarse_setup(int32_t E, const int32_t* ia, const int32_t* ib) {
   fused_p = false;
   use_sr = false;
   return PGO_OK;
+}
+
+// The own aggregates with no pose in the coarse space.  With an active set in force (pgo_set_active) those are the aggregates
+// whose poses are all resolved-constant: every other pose has an active edge.
+void pgo_handle::coarse_dead_list(std::vector<int32_t>* dead) const {
+  const int64_t NL = S.n_loc;
+  dead->clear();
+  for (int Il = 0; Il < co_nown; ++Il) {
+    bool any = false;
+    for (int32_t r = Il * co_agg; r < std::min<int64_t>(NL, (int64_t)(Il + 1) * co_agg) && !any; ++r) {
+      if (!act_const_h.empty()) {
+        any = !act_const_h[(size_t)S.lo + r];
+        continue;
+      }
+      if (S.lo + r == fixed_internal) continue;
+      for (int32_t q = S.inc_ptr[r]; q < S.inc_ptr[r + 1] && !any; ++q) any = S.inc_edge[q] >= 0;
+    }
+    if (!any) dead->push_back(co_aoff + Il);
+  }
 }
 
 // Several ranks: the edge mask of the basis planes, and the coarse coordinates of every rank's blocks and dead aggregates --

@@ -383,6 +383,18 @@ struct pgo_handle {
     for (auto& L : loss_cls) L = pgo::make_loss_class(opt.huber_delta > 0.0 ? PGO_LOSS_HUBER : PGO_LOSS_TRIVIAL, opt.huber_delta);
   }
   int set_losses(int32_t n_classes, const pgo_loss* losses, const uint8_t* edge_class);
+  // active sets (pgo_set_active): an edge mask in bit 4 of the flags bytes, the resolved constant poses in fixed_mask
+  bool act_edges = false;             // some edge is inactive: K1 runs its LOSSES instantiations, which test the bit
+  bool act_anchor = false;            // pose_constant names at least one pose (a gauge without opt.fixed_pose)
+  std::vector<uint8_t> act_const_h;   // the resolved constant rows, internal numbering; empty = no active set in force
+  uint8_t* act_mask = nullptr;        // solo handles: device copy, allocated at the first pgo_set_active and kept
+  int32_t n_active_edges = 0, n_constant_poses = 0;   // resolved (pgo_handle_info)
+  bool act_chain_cut = false;         // an edge of the direct solve's chain is inactive: PCG until it is active again
+  bool act_saved_direct = false, act_saved_possible = false;
+  int co_dead_cap = 0;                // entries co_dead can hold
+  bool has_anchor() const { return fixed_internal >= 0 || act_anchor; }
+  void coarse_dead_list(std::vector<int32_t>* dead) const;
+  int set_active(const uint8_t* edge_active, const uint8_t* pose_constant);
   dev::SwitchArrays switch_arrays() const {
     dev::SwitchArrays W;
     W.flags = e_flags;

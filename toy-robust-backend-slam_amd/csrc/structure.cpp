@@ -523,3 +523,31 @@ extern "C" int pgo_pose_order(int32_t n_poses, int32_t n_edges, const int32_t* i
   std::copy(p.begin(), p.end(), perm);
   return PGO_OK;
 }
+
+// The resolved sets of pgo_set_active / pgo_batch_set_active: a pose is constant when it is opt.fixed_pose, when the caller
+// says so, or when no active edge touches it (Ceres would not have that parameter block in the problem).
+extern "C" int pgo_active_plan(int32_t n_poses, int32_t n_edges, const int32_t* ia, const int32_t* ib, const uint8_t* edge_active,
+                               const uint8_t* pose_constant, int32_t fixed_pose, uint8_t* constant_out, int32_t* n_active_edges,
+                               int32_t* n_free_poses) {
+  if (n_poses <= 0 || n_edges < 0 || fixed_pose >= n_poses || (n_edges && (!ia || !ib)))
+    return pgo::fail(PGO_ERR_INVALID_ARG, "pgo_active_plan: bad argument");
+  for (int32_t e = 0; e < n_edges; ++e)
+    if (ia[e] < 0 || ia[e] >= n_poses || ib[e] < 0 || ib[e] >= n_poses)
+      return pgo::fail(PGO_ERR_INVALID_ARG, "pgo_active_plan: endpoint out of range");
+  std::vector<uint8_t> used((size_t)n_poses, 0);
+  int32_t n_act = 0;
+  for (int32_t e = 0; e < n_edges; ++e)
+    if (!edge_active || edge_active[e]) {
+      used[ia[e]] = used[ib[e]] = 1;
+      ++n_act;
+    }
+  int32_t n_free = 0;
+  for (int32_t i = 0; i < n_poses; ++i) {
+    const bool c = i == fixed_pose || (pose_constant && pose_constant[i]) || !used[i];
+    if (constant_out) constant_out[i] = c ? 1 : 0;
+    n_free += c ? 0 : 1;
+  }
+  if (n_active_edges) *n_active_edges = n_act;
+  if (n_free_poses) *n_free_poses = n_free;
+  return PGO_OK;
+}

@@ -84,7 +84,22 @@ class Problem {
     if (cost->kind != CostFunction::SWITCH_PRIOR || loss) throw std::invalid_argument("one parameter block: SwitchPriorResidue without loss only");
     prior_lambda_[s] = cost->dx;
   }
-  void SetParameterBlockConstant(double* p) { fixed_ = block(p); }
+  // Any number of blocks may be made constant.  The first one is the handle's fixed pose (one block, called once: exactly
+  // the path of a problem with a single anchor); the others, and the blocks that appear in no residual block, are applied
+  // through pgo_set_active when the problem is solved.
+  void SetParameterBlockConstant(double* p) {
+    const int32_t k = block(p);
+    for (int32_t c : constant_)
+      if (c == k) return;
+    constant_.push_back(k);
+    fixed_ = constant_[0];
+  }
+  // Problem::AddParameterBlock: a pose block of its own; one that no residual block uses is constant, as it would not be
+  // part of Ceres' reduced program
+  void AddParameterBlock(double* p, int size = 3) {
+    if (size != 3) throw std::invalid_argument("pose blocks have 3 parameters");
+    block(p);
+  }
   int NumResidualBlocks() const { return (int)ia_.size(); }
   int NumParameterBlocks() const { return (int)ptr_.size(); }
 
@@ -113,6 +128,7 @@ class Problem {
   std::vector<double> meas_;
   std::vector<uint8_t> kind_;
   int32_t fixed_ = -1;
+  std::vector<int32_t> constant_;                  // every constant block, in the order they were set (fixed_ = the first)
   std::vector<pgo_loss> losses_;                   // the distinct losses (pgo_set_losses' classes)
   std::vector<uint8_t> class_;                     // per residual block: its loss class
   std::vector<double*> switch_;                    // per residual block: its switch variable or nullptr
@@ -172,6 +188,19 @@ struct SolverAccess {
       if (x[k].type != y[k].type || x[k].a != y[k].a) return false;
     return true;
   }
+  // pose_constant of pgo_set_active for a problem that needs it -- more than one constant block, or a block without a
+  // residual block -- else empty: the handle then runs exactly as it does for a problem with one anchor
+  static std::vector<uint8_t> ConstantMask(const Problem* pr) {
+    const size_t N = pr->ptr_.size();
+    std::vector<uint8_t> used(N, 0), mask;
+    for (size_t e = 0; e < pr->ia_.size(); ++e) used[pr->ia_[e]] = used[pr->ib_[e]] = 1;
+    bool need = pr->constant_.size() > 1;
+    for (size_t i = 0; i < N && !need; ++i) need = !used[i];
+    if (!need) return mask;
+    mask.assign(N, 0);
+    for (int32_t c : pr->constant_) mask[c] = 1;
+    return mask;
+  }
   static pgo_t* Prepare(const Solver::Options& opt, Problem* pr) {
     const int32_t N = (int32_t)pr->ptr_.size(), E = (int32_t)pr->ia_.size();
     std::vector<double> poses((size_t)3 * N);
@@ -206,7 +235,9 @@ struct SolverAccess {
     pgo_t* h = nullptr;
     check(pgo_create(&h, N, poses.data(), E, pr->ia_.data(), pr->ib_.data(), pr->meas_.data(), pr->kind_.data(), &o, nullptr, opt.device));
     const std::vector<pgo_loss> L = LossTable(pr);
-    const int st = pgo_set_losses(h, (int32_t)L.size(), L.data(), E ? pr->class_.data() : nullptr);
+    int st = pgo_set_losses(h, (int32_t)L.size(), L.data(), E ? pr->class_.data() : nullptr);
+    const std::vector<uint8_t> mask = ConstantMask(pr);
+    if (st == PGO_OK && !mask.empty()) st = pgo_set_active(h, nullptr, mask.data());
     if (st != PGO_OK) {
       const std::string msg = pgo_last_error();
       pgo_destroy(h);
@@ -246,7 +277,7 @@ struct SolverAccess {
     if (prs.empty()) return false;
     for (Problem* pr : prs)
       if (pr->any_sc_ || pr->any_dcs_ != prs[0]->any_dcs_ || !SameLosses(pr, prs[0]) || pr->fixed_ != prs[0]->fixed_ ||
-          pr->ptr_.empty())
+          pr->ptr_.empty() || !ConstantMask(pr).empty())   // (several constant blocks: ordinary handles, pgo_set_active)
         return false;
     return true;
   }
