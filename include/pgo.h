@@ -432,7 +432,7 @@ typedef struct pgo_handle_info {
   int64_t n_incidences;              /* off-diagonal blocks of the owned rows                                       */
   int32_t pcg_block_poses;           /* resolved: poses per dense preconditioner block (1 when the chain form is on) */
   int32_t pcg_chain_len;             /* resolved: segment length of the chain preconditioner, 0 = off               */
-  int32_t chain_kernel;              /* 0 = scan form, 2 / 4 = lean form with that many poses per lane              */
+  int32_t chain_kernel;              /* 2 / 4 = poses per lane of the chain apply kernels (0 without the chain form)*/
   int32_t pose_ordering;             /* resolved: 1 = internal locality ordering in use                             */
   int32_t halo_exchange;             /* resolved: 1 = point-to-point halo exchange, 0 = all-gather / single rank    */
   int32_t halo_overlap;              /* resolved                                                                    */

@@ -759,7 +759,7 @@ def test_lm_inexact_matches_port_on_synthetic_10k(pgo, oracle):
 
 @pytest.mark.parametrize("n_poses,seed,chain", [(10000, 20260410, 64), (30011, 3, 64), (30011, 3, 256), (9001, 4, 8), (150, 7, 64)])
 def test_chain_preconditioner_matches_port(pgo, oracle, n_poses, seed, chain):
-    """pcg_chain_len: block-tridiagonal segments, factor (k_chain_factor) + chunked wave-scan apply (k_cg_update1_c)
+    """pcg_chain_len: block-tridiagonal segments, factor (k_chain_factor) + chunked wave apply (k_cg_update1_cl)
     against the sequential block LDL' sweep of the C port: same LM history, PCG iteration counts within 1, and fewer PCG
     iterations than the dense 4-pose blocks.  30011 / 9001 poses: the last segment, chunk and 256-row tile are ragged."""
     g = pgo.synth_manhattan(n_poses, 4.0, 0.10, seed)
@@ -1388,7 +1388,7 @@ def test_chain_preconditioner_other_modes(pgo, kw):
 @pytest.mark.parametrize("n_poses,kw", [(1000000, dict(pcg_chain_len=64)), (30011, dict(pcg_chain_len=256)),
                                         (30011, dict(pcg_block_poses=4, pcg_chain_len=0)), (30011, dict(pcg_block_poses=1, pcg_chain_len=0))])
 def test_preconditioner_is_symmetric_positive_definite(pgo, n_poses, kw):
-    """what CG needs from M^-1, checked through the apply kernels themselves (k_cg_init_c: chunked wave scans over the
+    """what CG needs from M^-1, checked through the apply kernels themselves (k_cg_init_cl: chunked wave sweeps over the
     block LDL' factors; k_cg_init_g: dense group inverses) at the bench size and on a ragged graph:
     u'(M^-1 v) == v'(M^-1 u), r'(M^-1 r) > 0, linearity, and the constant pose's rows stay decoupled"""
     g = pgo.synth_manhattan(n_poses, 4.0, 0.10, 20260410)

@@ -311,3 +311,20 @@ def test_product_never_touches_the_oracle():
             if f.endswith((".py", ".cpp", ".h", ".hip", ".c")):
                 txt = open(os.path.join(dirpath, f), errors="ignore").read()
                 assert "pgo_oracle" not in txt and "import oracle" not in txt and "oracle/" not in txt, os.path.join(dirpath, f)
+
+
+def test_library_reads_two_environment_variables_only():
+    """the library reads PGO_FORCE_COLLECTIVES and PGO_GRAPH_COLLECTIVES and nothing else from the environment --
+    every getenv( in csrc/ names one of the two, and no other way in (secure_getenv, environ, a macro standing for getenv)"""
+    import re
+    allowed = {"PGO_FORCE_COLLECTIVES", "PGO_GRAPH_COLLECTIVES"}
+    csrc = os.path.join(ROOT, "toy-robust-backend-slam_amd", "csrc")
+    seen = set()
+    for f in sorted(os.listdir(csrc)):
+        txt = open(os.path.join(csrc, f), errors="ignore").read()
+        for m in re.finditer(r"getenv\s*\(", txt):
+            arg = re.match(r'\s*"([A-Za-z0-9_]+)"\s*\)', txt[m.end():])
+            assert arg and arg.group(1) in allowed, (f, txt[m.start():m.start() + 60])
+            seen.add(arg.group(1))
+        assert not re.search(r"PGO_EXP_ENV|secure_getenv|\benviron\b|\benvp\b", txt), f
+    assert seen == allowed, seen

@@ -191,8 +191,8 @@ def lib():
     global _LIB
     if _LIB is not None:
         return _LIB
-    path = os.environ.get("PGO_LIB") or _build.LIB   # PGO_LIB: an experiment build (scripts/exp_*.sh), never the default
-    if path == _build.LIB and _build.needs_build():
+    path = _build.LIB
+    if _build.needs_build():
         try:
             path = _build.build_lib()
         except RuntimeError as e:  # no hipcc on this box: a present library is still usable, but say that it is stale

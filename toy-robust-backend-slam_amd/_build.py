@@ -31,15 +31,14 @@ def needs_build() -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build_lib(force: bool = False, verbose: bool = False, defines=(), out: str = LIB) -> str:
-    """`defines` / `out`: experiment builds (scripts/exp_*.sh) next to the product library, selected with PGO_LIB"""
-    if not force and not needs_build() and out == LIB:
+def build_lib(force: bool = False, verbose: bool = False) -> str:
+    if not force and not needs_build():
         return LIB
     # one object per translation unit, compiled side by side (the device code of a unit = the kernels it launches), then linked
     import tempfile
     from concurrent.futures import ThreadPoolExecutor
     flags = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wno-unused-function",
-             "-I" + os.path.join(ROOT, "include"), "-I" + CSRC] + ["-D" + d for d in defines]
+             "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
     with tempfile.TemporaryDirectory(prefix="pgo_build_") as tmp:
         def compile_one(src):
             obj = os.path.join(tmp, os.path.splitext(src)[0] + ".o")
@@ -50,12 +49,12 @@ def build_lib(force: bool = False, verbose: bool = False, defines=(), out: str =
             return obj
         with ThreadPoolExecutor(max_workers=min(len(SOURCES), max(1, (os.cpu_count() or 2) // 2))) as pool:
             objs = list(pool.map(compile_one, SOURCES))
-        cmd = [_hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared"] + objs + ["-o", out + ".tmp", "-lrccl", "-pthread"]
+        cmd = [_hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared"] + objs + ["-o", LIB + ".tmp", "-lrccl", "-pthread"]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
-    os.replace(out + ".tmp", out)
-    return out
+    os.replace(LIB + ".tmp", LIB)
+    return LIB
 
 
 def build_cli(force: bool = False) -> str:

@@ -43,24 +43,13 @@ constexpr int PS = 3;            // doubles per pose in the GATHERED vector p.  
 // ------------------------------------------------- streaming accesses
 // Data that a kernel touches exactly once (matrix / factor streams, CG vectors) is moved with the non-temporal hint so
 // that it does not displace what IS re-used (the gathered search direction) from the XCD's L2.
-#ifndef PGO_NT_STREAMS
-#define PGO_NT_STREAMS 1
-#endif
 template <class T>
 __device__ __forceinline__ T ld_stream(const T* p) {
-#if PGO_NT_STREAMS
   return __builtin_nontemporal_load(p);
-#else
-  return *p;
-#endif
 }
 template <class T>
 __device__ __forceinline__ void st_stream(T* p, T v) {
-#if PGO_NT_STREAMS
   __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
 }
 
 // the same under a template switch: kernels whose phases hand data to each other through global memory INSIDE one
@@ -126,9 +115,8 @@ __device__ __forceinline__ void hoff_store(double* __restrict__ hoff, int64_t q,
 }
 // a pose's three doubles of the gathered vector: one 16-byte + one 8-byte load (the vector is 8-byte aligned only)
 typedef double double2_a8 __attribute__((ext_vector_type(2), aligned(8)));
-template <int STRIDE = PS>
 __device__ __forceinline__ void gather3(const double* __restrict__ p, int64_t col, double& p0, double& p1, double& p2) {
-  const double* q = p + STRIDE * col;
+  const double* q = p + PS * col;
   const double2_a8 t = *reinterpret_cast<const double2_a8*>(q);
   p0 = t.x;
   p1 = t.y;
@@ -762,8 +750,7 @@ struct SpmvArgs {
 
 // Algorithmic bytes: 76 per off-diagonal block (72 value + 4 column index) + per row
 // 48 (diagonal planes) + 24 (D'D) + 4 (row pointer) + 24 (y) + 24 (p, counted once).
-// MODE 0 = the product kernel.  MODE 1..3 are timing-only ablations used by pgo_bench_spmv under
-// PGO_SPMV_ABLATE (1: no p[col] gather, 2: no H-plane loads, 3: neither): wrong results, same structure.
+// MODE 0 = the product kernel.
 // MODE 4 = the part of the product that needs OWNED columns only (blocks whose column lies on another rank contribute
 // 0 and are not loaded): it runs while the halo exchange is in flight, k_spmv_remote adds the rest afterwards.
 template <int MODE>
@@ -849,28 +836,16 @@ __global__ __launch_bounds__(WG) void k_spmv_t(SpmvArgs A) {
       const bool skip = MODE == 4 && (col < A.lo || col >= (int64_t)A.lo + A.n_loc);
       double p0 = 0.0, p1 = 0.0, p2 = 0.0, h[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
       if (lane_on && !skip) {
-        if (MODE == 1 || MODE == 3) {
-          p0 = (double)col; p1 = p0 + 1.0; p2 = p0 + 2.0;
-        } else {
-          load_p(col, p0, p1, p2);
-        }
-        if (MODE != 2 && MODE != 3) {
-          if (A.nt) hoff_load_nt(A.hoff, q, h);
-          else hoff_load(A.hoff, q, h);
-        }
+        load_p(col, p0, p1, p2);
+        if (A.nt) hoff_load_nt(A.hoff, q, h);
+        else hoff_load(A.hoff, q, h);
       }
       // the next tile's column indices (its descriptor has arrived: it was the first load of this iteration)
       if (tn < xr.end && dn.w <= WG && tid < dn.w) col_n = ld_stream(A.inc_col + dn.z + tid);
       if (lane_on) {
-        if (MODE == 2 || MODE == 3) {
-          scr[buf][0][tid] = p0 + 2.0 * p1 + 3.0 * p2;
-          scr[buf][1][tid] = p0 - p1;
-          scr[buf][2][tid] = p2 * p1;
-        } else {
-          scr[buf][0][tid] = h[0] * p0 + h[1] * p1 + h[2] * p2;   // skipped (remote-column) blocks: h = 0
-          scr[buf][1][tid] = h[3] * p0 + h[4] * p1 + h[5] * p2;
-          scr[buf][2][tid] = h[6] * p0 + h[7] * p1 + h[8] * p2;
-        }
+        scr[buf][0][tid] = h[0] * p0 + h[1] * p1 + h[2] * p2;   // skipped (remote-column) blocks: h = 0
+        scr[buf][1][tid] = h[3] * p0 + h[4] * p1 + h[5] * p2;
+        scr[buf][2][tid] = h[6] * p0 + h[7] * p1 + h[8] * p2;
       }
       __syncthreads();
       if (pv) {
@@ -956,10 +931,7 @@ __global__ __launch_bounds__(WG) void k_spmv_t(SpmvArgs A) {
 // tile t + 1 -- block stream, gathers, row operands -- issued BEFORE the barrier and the row phase of tile t, so that a
 // workgroup always has a tile's worth of memory requests in flight instead of waiting out one round trip per tile.
 // Costs registers (two tiles' operands live: ~110 VGPRs, 4 workgroups per CU instead of 8) -- the same bytes in flight.
-// PSTR: doubles per pose of the gathered vector.  PS in the product; experiment builds (scripts/exp_mall.sh) time the kernel
-// on a copy of p spread over 96 / 288 bytes per pose -- a table of 96 / 288 MB at 1M poses, i.e. inside / beyond the
-// 256 MiB Infinity Cache -- to tell gathers served by that cache from gathers served by HBM.
-template <int PSTR = PS>
+template <int PGO_UNIT_ = 0>   // (a template so that only the translation units that launch it carry it)
 __global__ __launch_bounds__(WG) void k_spmv_p(SpmvArgs A) {
   __shared__ double scr[2][3][WG];
   __shared__ double red[8];
@@ -996,14 +968,14 @@ __global__ __launch_bounds__(WG) void k_spmv_p(SpmvArgs A) {
       L.h0 = (a == 0) ? dg : o0;
       L.h1 = (a == 1) ? dg : o1;
       L.h2 = (a == 2) ? dg : o2;
-      gather3<PSTR>(A.p, (int64_t)A.lo + L.row, L.pr0, L.pr1, L.pr2);
+      gather3(A.p, (int64_t)A.lo + L.row, L.pr0, L.pr1, L.pr2);
     }
     L.on = tid < nq;
     L.p0 = L.p1 = L.p2 = 0.0;
 #pragma unroll
     for (int c = 0; c < 9; ++c) L.h[c] = 0.0;
     if (L.on) {
-      gather3<PSTR>(A.p, (int64_t)col_, L.p0, L.p1, L.p2);
+      gather3(A.p, (int64_t)col_, L.p0, L.p1, L.p2);
       if (A.nt) hoff_load_nt(A.hoff, q0 + tid, L.h);
       else hoff_load(A.hoff, q0 + tid, L.h);
     }
@@ -1684,19 +1656,18 @@ __global__ __launch_bounds__(WG) void k_cg_update1_g(CgVec V, GroupPre G, int pa
 //     S_i = M_ii - W_i C_i',   W_i = C_i S_{i-1}^-1,   C_i = H_{i,i-1}      (W_i = 0 at a segment start)
 // (k_chain_factor, one thread per segment) and applied as  t_i = r_i - W_i t_{i-1};  z_i = S_i^-1 t_i - W_{i+1}' z_{i+1}.
 //
-// Apply (chain_apply, fused into the CG update kernels): one wavefront per tile of 256 rows, one lane per CHUNK of 4
-// consecutive poses.  Each recurrence is a composition of affine maps x -> a + F x, so a lane (1) sweeps its chunk from
-// a zero input, accumulating the chunk's map (a, F = product of its 4 matrices), (2) the 64 chunk maps are combined by
-// a Hillis-Steele scan over the wave (6 levels of (3-vector, 3x3) pairs), (3) the lane sweeps its chunk again from its
-// true input.  Because W = 0 at every segment start, the chunk maps of different segments do not interact: the scan needs
-// no segment masks and the kernel is independent of L.  Work per pose ~150 fp64 FMA and 4.5 64-bit shuffles (the
-// lane-per-pose scan this replaces: 380 FMA and 126 shuffles per pose, 76 us per apply at 1M poses, shuffle-bound).
-// Factor planes are stored TRANSPOSED inside each 256-row tile (chain_tidx) so that step k of all 64 lanes is one
-// coalesced 512-byte access; the vectors go through a wave-private LDS tile (coalesced global access, strided LDS access
-// with one pad per chunk: conflict-free).  120 B/pose of factors per PCG iteration (dense 4-pose blocks: 288 B/pose).
-constexpr int CHAIN_CHUNK = 4;
-constexpr int CHAIN_TILE = 256;                       // rows per wavefront = 64 lanes x CHAIN_CHUNK
-constexpr int CHAIN_LDS = CHAIN_TILE * 3 + 64;        // doubles of LDS per wavefront (one pad per chunk)
+// Apply (chain_apply_lean below, fused into the CG update kernels): one wavefront per tile of 64 * CH rows, one lane per
+// chunk of CH (2 or 4) consecutive poses.  Each recurrence is a composition of affine maps x -> a + F x, so a lane (1)
+// sweeps its chunk from a zero input, accumulating the chunk's map (a, F = product of its CH matrices), (2) the chunk maps
+// are combined over the lanes of a segment, (3) the lane sweeps its chunk again from its true input.  Because W = 0 at
+// every segment start, the chunk maps of different segments do not interact: no segment masks are needed.  (A lane-per-
+// pose scan was the first form: 380 FMA and 126 shuffles per pose, 76 us per apply at 1M poses, shuffle-bound.)
+// Factor planes are stored TRANSPOSED inside each tile (chain_tidx_g; chain_tidx for the 256-row tiles of CH = 4) so that
+// step k of all 64 lanes is one coalesced 512-byte access; the vectors go through a wave-private LDS tile (coalesced global
+// access, strided LDS access with one pad per chunk: conflict-free).  120 B/pose of factors per PCG iteration (dense 4-pose
+// blocks: 288 B/pose).
+constexpr int CHAIN_CHUNK = 4;                        // the segment length is a multiple of this
+constexpr int CHAIN_TILE = 256;                       // rows of the largest tile = 64 lanes x CHAIN_CHUNK: n_pad is a multiple
 
 __host__ __device__ __forceinline__ int64_t chain_tidx(int64_t i) {
   return (i & ~(int64_t)(CHAIN_TILE - 1)) + ((i & (CHAIN_CHUNK - 1)) << 6) + ((i & (CHAIN_TILE - 1)) / CHAIN_CHUNK);
@@ -1869,269 +1840,10 @@ __device__ __forceinline__ void affine_compose(double a[3], double M[9], const d
   }
 }
 
-// In place on the wave-private LDS tile `buf` (CHAIN_LDS doubles): on entry r of the 256 rows starting at `wbase`
-// (pose q, component c at q*3 + c + (q >> 2); rows >= n_loc hold 0), on exit z = M^-1 r.  All 64 lanes call it; the
-// caller separates it from its own accesses to `buf` with barriers.
-__device__ __forceinline__ void chain_apply(const ChainPre& C, int64_t wbase, double* __restrict__ buf) {
-  const int lane = threadIdx.x & 63;
-  const int64_t np = C.n_pad;
-  const double* cwl = C.cw + wbase + lane;  // + c * np + k * 64 : W of this lane's pose k, entry c
-  const double* csl = C.cs + wbase + lane;
-  double* ch = buf + lane * (3 * CHAIN_CHUNK + 1);  // this lane's chunk: pose k at 3 k
-  // The lane's factors are (re)loaded as one batch at the start of each sweep (coalesced; L2 hits after the first):
-  // one memory latency per sweep, and only one sweep's factors are live at a time.
-  double W[CHAIN_CHUNK][9];
-  auto load_w = [&](int shift) {  // shift 0: W_k of the chunk's poses; 1: W_{k+1} (the backward sweeps)
-#pragma unroll
-    for (int k = 0; k < CHAIN_CHUNK; ++k) {
-      if (shift && k == CHAIN_CHUNK - 1) {
-        // the pose after the chunk = the next lane's first one (0 for lane 63: the next tile starts a segment)
-#pragma unroll
-        for (int c = 0; c < 9; ++c) W[k][c] = lane < 63 ? cwl[(int64_t)c * np + 1] : 0.0;
-      } else {
-#pragma unroll
-        for (int c = 0; c < 9; ++c) W[k][c] = cwl[(int64_t)c * np + (k + shift) * 64];
-      }
-    }
-  };
-  load_w(0);
-
-  double t[3] = {0.0, 0.0, 0.0}, F[9];
-  // ---- forward, pass 1: chunk map from a zero input:  t <- r_k - W_k t ;  F <- (-W_k) F
-#pragma unroll
-  for (int k = 0; k < CHAIN_CHUNK; ++k) {
-    const double* w = W[k];
-    const double t0 = ch[3 * k] - (w[0] * t[0] + w[1] * t[1] + w[2] * t[2]);
-    const double t1 = ch[3 * k + 1] - (w[3] * t[0] + w[4] * t[1] + w[5] * t[2]);
-    const double t2 = ch[3 * k + 2] - (w[6] * t[0] + w[7] * t[1] + w[8] * t[2]);
-    t[0] = t0; t[1] = t1; t[2] = t2;
-    if (k == 0) {
-#pragma unroll
-      for (int c = 0; c < 9; ++c) F[c] = -w[c];
-    } else {
-      double R[9];
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) R[3 * i + j] = -(w[3 * i] * F[j] + w[3 * i + 1] * F[3 + j] + w[3 * i + 2] * F[6 + j]);
-#pragma unroll
-      for (int c = 0; c < 9; ++c) F[c] = R[c];
-    }
-  }
-  // ---- scan of the chunk maps (inclusive): t becomes the true value at the end of this lane's chunk
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    double b[3], N[9];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) b[k] = __shfl_up(t[k], off, 64);
-    if (off < 32) {
-#pragma unroll
-      for (int c = 0; c < 9; ++c) N[c] = __shfl_up(F[c], off, 64);
-    }
-    if (lane >= off) affine_compose(t, F, b, N, off < 32);
-  }
-  // ---- forward, pass 2 from the true input (end of the previous chunk), then u = S^-1 t, stored over r
-  {
-    double S[CHAIN_CHUNK][6];
-#pragma unroll
-    for (int k = 0; k < CHAIN_CHUNK; ++k)
-#pragma unroll
-      for (int c = 0; c < 6; ++c) S[k][c] = csl[(int64_t)c * np + k * 64];
-    double x0 = __shfl_up(t[0], 1, 64), x1 = __shfl_up(t[1], 1, 64), x2 = __shfl_up(t[2], 1, 64);
-    if (lane == 0) { x0 = 0.0; x1 = 0.0; x2 = 0.0; }
-#pragma unroll
-    for (int k = 0; k < CHAIN_CHUNK; ++k) {
-      const double* w = W[k];
-      const double* q = S[k];
-      const double t0 = ch[3 * k] - (w[0] * x0 + w[1] * x1 + w[2] * x2);
-      const double t1 = ch[3 * k + 1] - (w[3] * x0 + w[4] * x1 + w[5] * x2);
-      const double t2 = ch[3 * k + 2] - (w[6] * x0 + w[7] * x1 + w[8] * x2);
-      x0 = t0; x1 = t1; x2 = t2;
-      ch[3 * k] = q[0] * t0 + q[1] * t1 + q[2] * t2;
-      ch[3 * k + 1] = q[1] * t0 + q[3] * t1 + q[4] * t2;
-      ch[3 * k + 2] = q[2] * t0 + q[4] * t1 + q[5] * t2;
-    }
-  }
-  // ---- backward, pass 1 (k = 3..0) from a zero input:  z <- u_k - W_{k+1}' z ;  F <- (-W_{k+1}') F
-  load_w(1);
-  t[0] = 0.0; t[1] = 0.0; t[2] = 0.0;
-#pragma unroll
-  for (int k = CHAIN_CHUNK - 1; k >= 0; --k) {
-    const double* w = W[k];
-    const double z0 = ch[3 * k] - (w[0] * t[0] + w[3] * t[1] + w[6] * t[2]);
-    const double z1 = ch[3 * k + 1] - (w[1] * t[0] + w[4] * t[1] + w[7] * t[2]);
-    const double z2 = ch[3 * k + 2] - (w[2] * t[0] + w[5] * t[1] + w[8] * t[2]);
-    t[0] = z0; t[1] = z1; t[2] = z2;
-    if (k == CHAIN_CHUNK - 1) {
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) F[3 * i + j] = -w[3 * j + i];
-    } else {
-      double R[9];
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) R[3 * i + j] = -(w[i] * F[j] + w[3 + i] * F[3 + j] + w[6 + i] * F[6 + j]);
-#pragma unroll
-      for (int c = 0; c < 9; ++c) F[c] = R[c];
-    }
-  }
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    double b[3], N[9];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) b[k] = __shfl_down(t[k], off, 64);
-    if (off < 32) {
-#pragma unroll
-      for (int c = 0; c < 9; ++c) N[c] = __shfl_down(F[c], off, 64);
-    }
-    if (lane + off < 64) affine_compose(t, F, b, N, off < 32);
-  }
-  // ---- backward, pass 2 from the true input (start of the next chunk), z stored over u
-  {
-    double x0 = __shfl_down(t[0], 1, 64), x1 = __shfl_down(t[1], 1, 64), x2 = __shfl_down(t[2], 1, 64);
-    if (lane == 63) { x0 = 0.0; x1 = 0.0; x2 = 0.0; }
-#pragma unroll
-    for (int k = CHAIN_CHUNK - 1; k >= 0; --k) {
-      const double* w = W[k];
-      const double z0 = ch[3 * k] - (w[0] * x0 + w[3] * x1 + w[6] * x2);
-      const double z1 = ch[3 * k + 1] - (w[1] * x0 + w[4] * x1 + w[7] * x2);
-      const double z2 = ch[3 * k + 2] - (w[2] * x0 + w[5] * x1 + w[8] * x2);
-      x0 = z0; x1 = z1; x2 = z2;
-      ch[3 * k] = z0;
-      ch[3 * k + 1] = z1;
-      ch[3 * k + 2] = z2;
-    }
-  }
-}
-
-// LDS position of flat element e (= 3 * pose + component) of a wave tile
-__device__ __forceinline__ int chain_lds_pos(int e) { return e + e / (3 * CHAIN_CHUNK); }
-
-// PCG start-up with the chain preconditioner: r = b, z = M^-1 r, y = 0, p = z; partials of r.z and b.b.
-// One wavefront per 256-row tile; workgroup = 4 waves = 1024 rows.
-template <int PGO_UNIT_ = 0>   // (a template so that only the translation units that launch it carry it)
-__global__ __launch_bounds__(WG) void k_cg_init_c(CgVec V, ChainPre C, const double* __restrict__ b,
-                                                  double* __restrict__ part_rz, double* __restrict__ part_bb) {
-  __shared__ double tile[4][CHAIN_LDS];
-  __shared__ double red[8];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  double* buf = tile[wave];
-  const int64_t n3 = 3 * (int64_t)V.n_loc;
-  // distinct arrays: let the compiler batch the loads of an unrolled group ahead of its stores
-  double* __restrict__ vy = V.y;
-  double* __restrict__ vr = V.r;
-  double* __restrict__ vz = V.z;
-  double* __restrict__ vp = V.p + 3 * (int64_t)V.lo;
-  double rz = 0.0, bb = 0.0;
-  for (int64_t wg_base = (int64_t)blockIdx.x * (4 * CHAIN_TILE); wg_base < V.n_loc; wg_base += (int64_t)gridDim.x * (4 * CHAIN_TILE)) {
-    const int64_t wbase = wg_base + (int64_t)wave * CHAIN_TILE;
-    const bool active = wbase < V.n_loc;
-    const int64_t f0 = 3 * wbase;
-    if (active) {
-#pragma unroll 4
-      for (int e = lane; e < 3 * CHAIN_TILE; e += 64) {
-        const int64_t idx = f0 + e;
-        buf[chain_lds_pos(e)] = idx < n3 ? b[idx] : 0.0;
-      }
-    }
-    __syncthreads();
-    if (active) chain_apply(C, wbase, buf);
-    __syncthreads();
-    if (active) {
-#pragma unroll 4
-      for (int e = lane; e < 3 * CHAIN_TILE; e += 64) {
-        const int64_t idx = f0 + e;
-        if (idx < n3) {
-          const double z = buf[chain_lds_pos(e)], r = b[idx];
-          vy[idx] = 0.0;
-          vr[idx] = r;
-          vz[idx] = z;
-          vp[idx] = z;
-          rz += r * z;
-          bb += r * r;
-        }
-      }
-    }
-    __syncthreads();
-  }
-  rz = block_sum_bcast(rz, red);
-  bb = block_sum_bcast(bb, red);
-  if (tid == 0) {
-    part_rz[blockIdx.x] = rz;
-    part_bb[blockIdx.x] = bb;
-  }
-}
-
-// x += alpha p ; r -= alpha A p ; z = M^-1 r (chain) ; partials of r.z and r.r
-template <int PGO_UNIT_ = 0>   // (a template so that only the translation units that launch it carry it)
-__global__ __launch_bounds__(WG) void k_cg_update1_c(CgVec V, ChainPre C, int parity, const double* __restrict__ part_pap,
-                                                     int n_pap, double* __restrict__ part_rz, double* __restrict__ part_rr) {
-  __shared__ double tile[4][CHAIN_LDS];
-  __shared__ double red[8];
-  if (V.st->done) return;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const double pap = sum_partials_bcast(part_pap, n_pap, red);
-  const double alpha = V.st->rz[parity] / pap;
-  double* buf = tile[wave];
-  const int64_t n3 = 3 * (int64_t)V.n_loc;
-  double* __restrict__ vy = V.y;
-  double* __restrict__ vr = V.r;
-  double* __restrict__ vz = V.z;
-  const double* __restrict__ vap = V.ap;
-  const double* __restrict__ pown = V.p + 3 * (int64_t)V.lo;
-  double rz = 0.0, rr = 0.0;
-  for (int64_t wg_base = (int64_t)blockIdx.x * (4 * CHAIN_TILE); wg_base < V.n_loc; wg_base += (int64_t)gridDim.x * (4 * CHAIN_TILE)) {
-    const int64_t wbase = wg_base + (int64_t)wave * CHAIN_TILE;
-    const bool active = wbase < V.n_loc;
-    const int64_t f0 = 3 * wbase;
-    if (active) {
-#pragma unroll 4
-      for (int e = lane; e < 3 * CHAIN_TILE; e += 64) {
-        const int64_t idx = f0 + e;
-        double r = 0.0;
-        if (idx < n3) {
-          vy[idx] += alpha * pown[idx];
-          r = vr[idx] - alpha * vap[idx];
-          vr[idx] = r;
-        }
-        buf[chain_lds_pos(e)] = r;
-      }
-    }
-    __syncthreads();
-    if (active) chain_apply(C, wbase, buf);
-    __syncthreads();
-    if (active) {
-#pragma unroll 4
-      for (int e = lane; e < 3 * CHAIN_TILE; e += 64) {
-        const int64_t idx = f0 + e;
-        if (idx < n3) {
-          const double z = buf[chain_lds_pos(e)], r = vr[idx];
-          vz[idx] = z;
-          rz += r * z;
-          rr += r * r;
-        }
-      }
-    }
-    __syncthreads();
-  }
-  rz = block_sum_bcast(rz, red);
-  rr = block_sum_bcast(rr, red);
-  if (tid == 0) {
-    part_rz[blockIdx.x] = rz;
-    part_rr[blockIdx.x] = rr;
-  }
-  if (V.fused && blockIdx.x == 0 && threadIdx.x == 0) {
-    V.st->pending = 1;
-    V.st->started = 1;
-  }
-}
-
 // ------------------------------------------------- chain preconditioner, lean apply (segments of <= 64 * CH rows)
-// Second form of the same apply, built for occupancy: the scan-based kernel above keeps ~244 VGPRs live (2 waves/SIMD)
-// and couples its four waves with workgroup barriers, so in the PCG loop -- where its 288 B/row arrive from HBM, the
-// SpMV stream having flushed every cache -- it is latency-bound (81 us at 1M poses, 0.44 of the HBM roofline).  Here
+// Built for occupancy: an earlier form that scanned (vector, matrix) pairs over whole 256-row tiles kept ~244 VGPRs live
+// (2 waves/SIMD) and coupled its four waves with workgroup barriers, so in the PCG loop -- where its 288 B/row arrive from
+// HBM, the SpMV stream having flushed every cache -- it was latency-bound (81 us at 1M poses, 0.44 of the HBM roofline).  Here
 //   * a wavefront owns a tile of 64 * CH rows (CH = 2: 128 rows, 30 doubles of factors per lane instead of 60);
 //   * the chunk maps are NOT scanned as (vector, matrix) pairs: the chunk's matrix F = (-W_{CH-1}) ... (-W_0) depends on
 //     the factors only, so the values at the chunk ends follow from the first-order recurrence x_l = a_l + F_l x_{l-1}
@@ -2388,12 +2100,6 @@ __global__ __launch_bounds__(64 * NW) void k_cg_init_cl(CgVec V, ChainPre C, int
 }
 
 // x += alpha p ; r -= alpha A p ; z = M^-1 r (lean chain apply) ; partials of r.z and r.r
-#ifdef PGO_PHASE_TIMING
-static __device__ unsigned long long g_phase_t[16];
-#define PGO_T(k) do { if (blockIdx.x == 0 && threadIdx.x == 0) g_phase_t[k] = wall_clock64(); } while (0)
-#else
-#define PGO_T(k) do { } while (0)
-#endif
 template <int CH, int NW>
 __global__ __launch_bounds__(64 * NW) void k_cg_update1_cl(CgVec V, ChainPre C, int n_steps, int scan_levels, int parity,
                                                       const double* __restrict__ part_pap, int n_pap,
@@ -2401,7 +2107,6 @@ __global__ __launch_bounds__(64 * NW) void k_cg_update1_cl(CgVec V, ChainPre C, 
   constexpr int TILE = 64 * CH, STRIDE = 3 * CH + 1, NV = 3 * CH;
   __shared__ double tile[NW][64 * STRIDE];
   __shared__ double red[8];
-  PGO_T(0);
   const unsigned tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   double alpha = 0.0, pap_part = 0.0;
   if constexpr (NW == 4) {
@@ -2416,8 +2121,6 @@ __global__ __launch_bounds__(64 * NW) void k_cg_update1_cl(CgVec V, ChainPre C, 
     for (int i = threadIdx.x; i < n_pap; i += 64) pap_part += part_pap[i];
     if (dn) return;
   }
-  PGO_T(1);
-  PGO_T(2);
   double* buf = tile[wave];
   double* ch = buf + lane * STRIDE;
   const int64_t n3 = 3 * (int64_t)V.n_loc, np = C.n_pad;
@@ -2502,10 +2205,8 @@ __global__ __launch_bounds__(64 * NW) void k_cg_update1_cl(CgVec V, ChainPre C, 
       buf[e + e / (3 * CH)] = rv[j];
     }
     wave_lds_sync();
-    PGO_T(3);
     chain_apply_lean<CH>(W, C.cs + wbase, np, lane, ch, n_steps, scan_levels);
     wave_lds_sync();
-    PGO_T(4);
     double* zt = vz + f0;
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
@@ -2516,7 +2217,6 @@ __global__ __launch_bounds__(64 * NW) void k_cg_update1_cl(CgVec V, ChainPre C, 
     }
     wave_lds_sync();
   }
-  PGO_T(5);
   rz = block_sum_nw<NW>(rz, red);
   rr = block_sum_nw<NW>(rr, red);
   if (tid == 0) {
@@ -2527,7 +2227,6 @@ __global__ __launch_bounds__(64 * NW) void k_cg_update1_cl(CgVec V, ChainPre C, 
     V.st->pending = 1;
     V.st->started = 1;
   }
-  PGO_T(6);
 }
 
 // ------------------------------------------------- single-reduction PCG (Chronopoulos & Gear), chain preconditioner

@@ -87,8 +87,6 @@ int build_shard_structure(int32_t n_poses, int32_t n_edges, const int32_t* ia, c
                           const double* meas, const uint8_t* kind, int method, int world, int rank, int row_align,
                           ShardStructure* out, const std::vector<int32_t>* tile_breaks = nullptr);
 
-// processing order of the row tiles for K3 (structure.cpp): order[k] = tile that takes the k-th turn
-void compute_tile_order(const ShardStructure& S, std::vector<int32_t>* order);
 bool pad_tiles_to_slots(ShardStructure* S);
 
 // locality ordering (structure.cpp): perm[i] = new position of pose i

@@ -470,15 +470,6 @@ int pgo_solve_batch(pgo_t* const* handles, int32_t n, pgo_summary* summaries, in
   return PGO_OK;
 }
 
-#ifdef PGO_PHASE_TIMING
-// experiment builds only (scripts/exp_phase.sh): wall_clock64 stamps of the last k_cg_update1_cl launch
-int pgo_debug_phase_times(pgo_t* h, unsigned long long* out16) {
-  HIPC(hipStreamSynchronize(h->stream));
-  HIPC(hipMemcpyFromSymbol(out16, HIP_SYMBOL(dev::g_phase_t), 16 * sizeof(unsigned long long)));
-  return PGO_OK;
-}
-#endif
-
 int pgo_debug_set_knob(const char* name, long long value) {
   if (!name) return fail(PGO_ERR_INVALID_ARG, "pgo_debug_set_knob: null name");
   for (Knob& k : g_knobs)
@@ -784,33 +775,7 @@ int pgo_bench_spmv(pgo_t* h, int reps, pgo_kernel_stats* out) {
   if (!h->lin_valid) return fail(PGO_ERR_INVALID_ARG, "pgo_bench_spmv: call pgo_lm_begin first");
   HIPC(hipSetDevice(h->device));
   double ms = 0;
-  const char* ab = PGO_EXP_ENV("PGO_SPMV_ABLATE");
-  h->spmv_ablate = ab ? atoi(ab) : 0;
-  int st_ab = PGO_OK;
-#ifdef PGO_EXPERIMENTS
-  // PGO_SPMV_PSTRIDE = 12 | 36: the product kernel on a copy of p spread over 96 / 288 bytes per pose (timing only; the
-  // result is the same product) -- are the gathers served by the Infinity Cache or by HBM?
-  const char* pstr = getenv("PGO_SPMV_PSTRIDE");
-  const int stride = pstr ? atoi(pstr) : 0;
-  if ((stride == 12 || stride == 36) && h->spmv_pipe) {
-    double* big = nullptr;
-    const int64_t nf = h->n_full;
-    HIPC(hipMalloc((void**)&big, (size_t)nf * stride * sizeof(double)));
-    HIPC(hipMemsetAsync(big, 0, (size_t)nf * stride * sizeof(double), h->stream));
-    HIPC(hipMemcpy2DAsync(big, (size_t)stride * sizeof(double), h->p_full, 3 * sizeof(double), 3 * sizeof(double), (size_t)nf,
-                          hipMemcpyDeviceToDevice, h->stream));
-    dev::SpmvArgs A = h->spmv_args(big, h->ap, h->part[0], 1, nullptr);
-    st_ab = time_launches(h, reps, [&] {
-      if (stride == 12) hipLaunchKernelGGL(dev::k_spmv_p<12>, dim3(h->g_spmv), dim3(dev::WG), 0, h->stream, A);
-      else hipLaunchKernelGGL(dev::k_spmv_p<36>, dim3(h->g_spmv), dim3(dev::WG), 0, h->stream, A);
-    }, &ms);
-    (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(big);
-  } else
-#endif
-  st_ab = time_launches(h, reps, [&] { (void)h->spmv_enqueue(h->p_full, h->ap, h->part[0], 1, nullptr); }, &ms);
-  h->spmv_ablate = 0;
-  PGOC(st_ab);
+  PGOC(time_launches(h, reps, [&] { (void)h->spmv_enqueue(h->p_full, h->ap, h->part[0], 1, nullptr); }, &ms));
   out->ms_avg = ms;
   out->units = h->S.n_inc_real + h->S.n_loc;
   // 76 B per off-diagonal block (value + column) ; per row: 48 B diagonal planes + 24 B D'D + 4 B row

@@ -93,11 +93,10 @@ int coarse_for_covariance(pgo_handle* h) {
   int want = NL <= 8192 ? 16 : 64;
   while (3 * ((NL + want - 1) / want) + 1 > COARSE_MAX_RANK) want *= 2;
   const int saved_want = h->opt.pcg_coarse_poses;
-  const bool solo = h->solo, fused_p = h->fused_p, use_sr = h->use_sr, dl_possible = h->dl_possible;
+  const bool fused_p = h->fused_p, use_sr = h->use_sr, dl_possible = h->dl_possible;
   h->opt.pcg_coarse_poses = want;
   const int st = h->coarse_setup(0, nullptr, nullptr);   // (one rank: the edge lists are not read)
   h->opt.pcg_coarse_poses = saved_want;
-  h->solo = solo;
   h->fused_p = fused_p;
   h->use_sr = use_sr;
   h->dl_possible = dl_possible;

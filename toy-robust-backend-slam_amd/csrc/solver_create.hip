@@ -31,7 +31,6 @@ int pgo_handle::create(int32_t N, const double* poses_h, int32_t E, const int32_
   }
   const char* fc = getenv("PGO_FORCE_COLLECTIVES");
   force_collectives = fc && fc[0] == '1';
-  if (const char* nt = PGO_EXP_ENV("PGO_SPMV_NT")) spmv_nt = atoi(nt);
   if (const char* gc = getenv("PGO_GRAPH_COLLECTIVES")) graph_collectives = atoi(gc);
   grp_B = pgo::resolve_block_poses(opt.pcg_block_poses, N);
   chain_len = pgo::resolve_chain_len(opt.pcg_chain_len, opt.pcg_block_poses, N, E, ia, ib);
@@ -102,9 +101,7 @@ int pgo_handle::create(int32_t N, const double* poses_h, int32_t E, const int32_
   for (int32_t k = 0; k < S.n_edges_local; ++k) kind_local[k] = kind[S.orig_edge[k]];
   // Graphs large enough for the one-tile-per-workgroup product kernel (k_spmv_1, below) get the padded-slot layout: every
   // tile's incidences at TILE_INC t (structure.cpp, pad_tiles_to_slots).  Test hook "pad_tiles" = 0 keeps the dense layout.
-  int one_tile_min = 4096;
-  if (const char* om = PGO_EXP_ENV("PGO_ONE_TILE_MIN")) one_tile_min = atoi(om);
-  if (knob("pad_tiles") == 1) one_tile_min = 0;   // (test hook: the large-graph layout and product kernel on a graph of any size)
+  const int one_tile_min = knob("pad_tiles") == 1 ? 0 : 4096;   // (test hook: the large-graph layout and product kernel on a graph of any size)
   if (!batch_mode && S.n_tiles() > one_tile_min && knob("pad_tiles") != 0) (void)pgo::pad_tiles_to_slots(&S);
   n_full = (int64_t)world * S.rows_per_rank;
   const int64_t EL = S.n_edges_local, NL = S.n_loc;
@@ -157,7 +154,6 @@ int pgo_handle::create(int32_t N, const double* poses_h, int32_t E, const int32_
   g_rows = std::max(1, cdiv(NL, dev::WG));
   g_vec = std::min(std::max(1, cdiv(NL, dev::WG)), 1024);
   g_flat = std::min(std::max(1, cdiv(3 * NL, dev::WG)), 1024);
-  if (const char* fe = PGO_EXP_ENV("PGO_FLAT_GRID")) g_flat = std::min(g_flat, std::max(8, atoi(fe)));
   g_spmv = up8(std::min(std::max(1, S.n_tiles()), 2048));
   g_asm = up8(std::min(std::max(1, S.n_tiles()), 1 << 20));
   part_cap = std::max(std::max(g_edge, 2048), up8(std::max(1, S.n_tiles()))) + 8 + 512;   // (k_spmv_1: one dot partial per tile)   // (+ the coarse level's dot partials behind the one-level r.z partials)
@@ -185,30 +181,23 @@ int pgo_handle::create(int32_t N, const double* poses_h, int32_t E, const int32_
   PGOC(upload(tile_row, S.tile_row));
   PGOC(upload(inc_rowoff, S.inc_rowoff));
   {  // one 16-byte descriptor per tile for K3: {first local row, rows, first incidence, incidences}
-    // in breadth-first order of the tile graph (compute_tile_order): tiles running together gather the same lines
+    // in row order: a breadth-first order of the tile graph cuts the gather traffic (FETCH_SIZE 992 -> 920-937 MB at 1M
+    // poses) but the scattered 18-KB H chunks cost more than that saves (184 vs 179 us)
     std::vector<int4> desc((size_t)std::max(1, S.n_tiles()));
-    std::vector<int32_t> order;
-    const char* to = PGO_EXP_ENV("PGO_TILE_ORDER");
-    // OFF by default: it cuts the gather traffic (FETCH_SIZE 992 -> 920-937 MB at 1M poses) but the scattered 18-KB
-    // H chunks cost more than that saves (184 vs 179 us); PGO_TILE_ORDER=1 turns it on (never in a batch, which keeps
-    // each problem's tiles together)
-    if (to && to[0] == '1' && S.n_tiles() >= 4096 && !batch_mode) pgo::compute_tile_order(S, &order);
-    for (int k = 0; k < S.n_tiles(); ++k) {
-      const int t = order.empty() ? k : order[k];
+    for (int t = 0; t < S.n_tiles(); ++t) {
       const int32_t r0 = S.tile_row[t], r1 = S.tile_row[t + 1];
-      desc[k] = make_int4(r0, r1 - r0, S.inc_ptr[r0], S.inc_ptr[r1] - S.inc_ptr[r0]);
+      desc[t] = make_int4(r0, r1 - r0, S.inc_ptr[r0], S.inc_ptr[r1] - S.inc_ptr[r0]);
     }
     {
       // the software-pipelined product kernel (k_spmv_p) needs plain tiles: no chunked heavy row, at most 85 rows
-      // (one row-phase pass); PGO_SPMV_PIPE=0 keeps k_spmv_t.  Measured on one box at 1M poses: k_spmv_t 185.7 us (8
-      // workgroups per CU), k_spmv_p 172.4 / 175.5 / 168.8 / 165.1 us at 8 / 6 / 5 / 4 workgroups per CU.
+      // (one row-phase pass).  Measured on one box at 1M poses: k_spmv_t 185.7 us (8 workgroups per CU), k_spmv_p
+      // 172.4 / 175.5 / 168.8 / 165.1 us at 8 / 6 / 5 / 4 workgroups per CU -- hence 4.
       bool ok = knob("spmv_pipe") != 0;   // (test hook: 0 keeps k_spmv_t so that the two product kernels can be compared)
       for (int t = 0; ok && t < S.n_tiles(); ++t)
         ok = desc[t].w <= dev::WG && desc[t].y * 3 <= dev::WG;
       spmv_pipe = ok;
       if (ok) {
-        int per_cu = 4;
-        if (const char* ge = PGO_EXP_ENV("PGO_SPMV_PIPE_WGS")) per_cu = std::max(1, atoi(ge));
+        const int per_cu = 4;
         g_spmv = ((std::min(std::max(1, S.n_tiles()), 256 * per_cu) + 7) / 8) * 8;
         // Large graphs: one tile per workgroup (k_spmv_1) -- 151 us against the pipelined form's 164-166 us at 1M poses; test
         // hook "spmv_pipe" = 2 keeps k_spmv_p there.  Up to 4096 tiles the persistent forms stay: fewer partials, no
@@ -311,49 +300,31 @@ int pgo_handle::create(int32_t N, const double* poses_h, int32_t E, const int32_
     // the padding rows of the factor planes are never written: they must read as 0
     HIPC(hipMemsetAsync(chain_w, 0, (size_t)9 * chain_pad * sizeof(double), stream));
     HIPC(hipMemsetAsync(chain_s, 0, (size_t)6 * chain_pad * sizeof(double), stream));
-    g_chain = (int)std::max<int64_t>(1, std::min<int64_t>((NL + 4 * dev::CHAIN_TILE - 1) / (4 * dev::CHAIN_TILE), 2048));
     // apply kernel: the lean form (one DPP-shift recurrence step per lane of a segment), 2 poses per lane for segments of
-    // <= 64 poses, 4 for longer ones (INTEL, chain-256: 20 us per apply in the scan form -- five 256-row tiles, latency-
-    // bound -- of a 30 us PCG iteration); PGO_CHAIN_KERNEL = scan | lean2 | lean4 overrides (experiments)
+    // <= 64 poses, 4 for longer ones (INTEL, chain-256: the earlier scan form over whole 256-row tiles took 20 us per apply
+    // -- five tiles, latency-bound -- of a 30 us PCG iteration)
     chain_chunk = chain_len <= 64 ? 2 : 4;   // 4: segments of up to 256 poses (the small chain-like graphs)
-    if (const char* ck = PGO_EXP_ENV("PGO_CHAIN_KERNEL")) {
-      if (!strcmp(ck, "scan")) chain_chunk = 0;
-      else if (!strcmp(ck, "lean2") && (128 % chain_len) == 0) chain_chunk = 2;
-      else if (!strcmp(ck, "lean4")) chain_chunk = 4;
-    }
-    if (chain_chunk) {
-      chain_steps = chain_len / chain_chunk - 1;
-      const int64_t n_wt = (NL + 64 * chain_chunk - 1) / (64 * chain_chunk);
-      // Small graphs (few tiles, nothing to overlap with): one wavefront per workgroup, so that every tile loads through
-      // its own CU's L1, and -- for segments of more than 16 lanes -- the recurrence as a log-depth scan (INTEL, 256-pose
-      // segments: 7.4 -> 4.8 us per apply); large graphs keep the 4-wave workgroups and the serial DPP recurrence,
-      // which needs fewer registers and no LDS-crossbar shuffles.
-      int64_t small_max = 512;
-      if (const char* sm = PGO_EXP_ENV("PGO_CHAIN_SMALL_TILES")) small_max = atoll(sm);
-      const bool small = n_wt <= small_max;
-      chain_nw = small ? 1 : 4;
-      chain_scan = 0;
-      if (small && chain_len / chain_chunk > 16)
-        for (int l = 1; l < chain_len / chain_chunk; l <<= 1) ++chain_scan;
-      if (const char* cs = PGO_EXP_ENV("PGO_CHAIN_SCAN")) {  // experiments: 0 = always serial
-        if (atoi(cs) == 0) chain_scan = 0;
-      }
-      // every workgroup of the NEXT kernel re-sums this kernel's per-workgroup partials, so fewer, longer-running
-      // workgroups are cheaper all round: 2048 -> 512 (and 1024 for the flat vector kernels) 25.43 -> 24.65 ms per LM
-      // iteration at 1M poses (same box, 3 interleaved repetitions)
-      int cap = 512;
-      if (const char* ce = PGO_EXP_ENV("PGO_CHAIN_GRID")) cap = std::max(8, atoi(ce));
-      g_chain = (int)std::max<int64_t>(1, std::min<int64_t>((n_wt + chain_nw - 1) / chain_nw, chain_nw == 1 ? 2048 : cap));
-    }
+    chain_steps = chain_len / chain_chunk - 1;
+    const int64_t n_wt = (NL + 64 * chain_chunk - 1) / (64 * chain_chunk);
+    // Small graphs (few tiles, nothing to overlap with): one wavefront per workgroup, so that every tile loads through
+    // its own CU's L1, and -- for segments of more than 16 lanes -- the recurrence as a log-depth scan (INTEL, 256-pose
+    // segments: 7.4 -> 4.8 us per apply); large graphs keep the 4-wave workgroups and the serial DPP recurrence,
+    // which needs fewer registers and no LDS-crossbar shuffles.
+    const bool small = n_wt <= 512;
+    chain_nw = small ? 1 : 4;
+    chain_scan = 0;
+    if (small && chain_len / chain_chunk > 16)
+      for (int l = 1; l < chain_len / chain_chunk; l <<= 1) ++chain_scan;
+    // every workgroup of the NEXT kernel re-sums this kernel's per-workgroup partials, so fewer, longer-running
+    // workgroups are cheaper all round: 2048 -> 512 (and 1024 for the flat vector kernels) 25.43 -> 24.65 ms per LM
+    // iteration at 1M poses (same box, 3 interleaved repetitions)
+    g_chain = (int)std::max<int64_t>(1, std::min<int64_t>((n_wt + chain_nw - 1) / chain_nw, chain_nw == 1 ? 2048 : 512));
   }
   // One-workgroup PCG (solo.hip.h): a single rank, a chain or 3x3 block-Jacobi preconditioner, no chunked heavy row.
-  {
-    const char* se = PGO_EXP_ENV("PGO_SOLO");
-    // a single graph takes this path only on request (PGO_SOLO=1): one CU's L1 paces the solve -- INTEL 36 us per PCG
-    // iteration against 27 us for the three-kernel loop on 256 CUs, MIT / FR079 8 % faster -- the win is the BATCH, where
-    // every problem has a CU of its own
-    bool ok = world == 1 && !force_collectives && grp_B == 1 && NL > 0 &&
-              (batch_mode || ((se && se[0] == '1') && S.n_tiles() <= 64));
+  // Batched handles only: on a single graph one CU's L1 paces the solve -- INTEL 36 us per PCG iteration against 27 us for
+  // the three-kernel loop on 256 CUs, MIT / FR079 8 % faster -- the win is the BATCH, where every problem has a CU of its own
+  if (batch_mode) {
+    bool ok = world == 1 && !force_collectives && grp_B == 1 && NL > 0;
     for (int t = 0; ok && t < S.n_tiles(); ++t)
       ok = S.inc_ptr[S.tile_row[t + 1]] - S.inc_ptr[S.tile_row[t]] <= dev::WG;
     if (ok && chain_len) {
@@ -369,17 +340,10 @@ int pgo_handle::create(int32_t N, const double* poses_h, int32_t E, const int32_
       if (lanes > 16)
         for (int l = 1; l < lanes; l <<= 1) ++solo_scan;
     }
-    if (batch_mode && !ok) return fail(PGO_ERR_UNSUPPORTED, "pgo_batch: a problem has a row with more than 256 incidences");
-    if (ok && !batch_mode) {
-      PGOC(dalloc(&solo_prob, 1));
-      PGOC(dalloc(&solo_out, 1));
-      HIPC(hipHostMalloc((void**)&h_solo, sizeof(dev::SoloOut)));
-    }
-    solo = ok;
+    if (!ok) return fail(PGO_ERR_UNSUPPORTED, "pgo_batch: a problem has a row with more than 256 incidences");
   }
   {
-    int64_t fused_max = 16384;
-    if (const char* fm = PGO_EXP_ENV("PGO_FUSED_MAX_ROWS")) fused_max = atoll(fm);
+    const int64_t fused_max = 16384;
     fused_p = knob("fused_p") != 0 && world == 1 && !force_collectives && !batch_mode && NL > 0 && NL <= fused_max;
     if (fused_p) PGOC(dalloc(&p_full2, dev::PS * n_full));
   }
@@ -388,7 +352,7 @@ int pgo_handle::create(int32_t N, const double* poses_h, int32_t E, const int32_
     // and only in the inexact mode (pcg_rtol >= 1e-6: the recurrence for A p drifts over the thousands of iterations of
     // the exact mode); needs the lean chain apply.  Test hook "single_reduction": 1 = also on one rank, 0 = never.
     const long long kn = knob("single_reduction");
-    use_sr = chain_len > 0 && chain_chunk > 0 && !solo && !fused_p && !batch_mode && opt.pcg_rtol >= 1e-6 &&
+    use_sr = chain_len > 0 && !fused_p && !batch_mode && opt.pcg_rtol >= 1e-6 &&
              (kn == 1 || (kn != 0 && (world > 1 || force_collectives)));
     if (use_sr) PGOC(dalloc(&sr_s, 3 * NL));
     verify_residual = knob("verify_residual") == 1;
@@ -543,7 +507,6 @@ int pgo_handle::coarse_setup(int32_t E, const int32_t* ia, const int32_t* ib) {
   if (opt.linear_solver == 0) dl_possible = false;   // (ranks above the direct solve's cheap range: two-level PCG instead of the PCG / direct alternation)
   // the loops that fold launches together assume the one-level preconditioner: two-level solves take the plain three-kernel loop
   // (several ranks: the two-reduction loop on every rank)
-  solo = false;
   fused_p = false;
   use_sr = false;
   return PGO_OK;
@@ -639,8 +602,7 @@ int pgo_handle::coarse_setup_multi(int32_t E, const int32_t* ia, const int32_t* 
 
 int pgo_handle::direct_setup(int32_t N, bool switch_now) {
   const int world = comm ? comm->world : 1;
-  int want = switch_now ? 2 : opt.linear_solver;
-  if (const char* de = PGO_EXP_ENV("PGO_DIRECT")) want = atoi(de) ? 2 : 1;  // experiment builds only: force on / off
+  const int want = switch_now ? 2 : opt.linear_solver;
   if (want == 1) return PGO_OK;
   if (want != 0 && want != 2) return fail(PGO_ERR_INVALID_ARG, "linear_solver: 0 = auto, 1 = PCG, 2 = direct (chain + low rank)");
   auto no = [&](const std::string& why) -> int {
@@ -690,24 +652,18 @@ int pgo_handle::direct_setup(int32_t N, bool switch_now) {
   if (dl_K + 1 > DIRECT_MAX_RANK) return no(std::to_string(dl_m) + " edges outside the odometry chain (at most " + std::to_string((DIRECT_MAX_RANK - 1) / 3) + ")");
   dl_Kp = std::max(dev::CHOL_NB, ((dl_K + dev::CHOL_NB - 1) / dev::CHOL_NB) * dev::CHOL_NB);
   // separators: the chain is factorised in nsep + 1 pieces side by side (k_dlr_factor is one wavefront's dependent chain:
-  // 0.3 us per pose); PGO_DIRECT_SEP=0 keeps one piece
+  // 0.3 us per pose)
   dl_nsep = 0;
-  {
-    const char* se = PGO_EXP_ENV("PGO_DIRECT_SEP");
-    if (N >= 256 && !(se && se[0] == '0')) {
-      // 3 separators up to ~5000 poses (INTEL / MIT: 3 -> 826 / 2392 GN it/s, 5 -> 813 / 2294, 7 -> 788 / 2116, 15 -> 606 / 1209:
-      // every separator adds 3 columns and a row of the Schur system), then one per ~1200 poses (40k poses: 3 -> 156, 15 -> 205)
-      dl_nsep = std::min(dev::DLR_MAX_SEP, std::max(3, (int)(N / 1200)));
-      if (const char* ne = PGO_EXP_ENV("PGO_DIRECT_NSEP")) dl_nsep = std::min(dev::DLR_MAX_SEP, std::max(1, atoi(ne)));   // experiments
-      for (int j = 0; j < dl_nsep; ++j) dl_sep[j] = (int)(((int64_t)(j + 1) * N) / (dl_nsep + 1));
-    }
+  if (N >= 256) {
+    // 3 separators up to ~5000 poses (INTEL / MIT: 3 -> 826 / 2392 GN it/s, 5 -> 813 / 2294, 7 -> 788 / 2116, 15 -> 606 / 1209:
+    // every separator adds 3 columns and a row of the Schur system), then one per ~1200 poses (40k poses: 3 -> 156, 15 -> 205)
+    dl_nsep = std::min(dev::DLR_MAX_SEP, std::max(3, (int)(N / 1200)));
+    for (int j = 0; j < dl_nsep; ++j) dl_sep[j] = (int)(((int64_t)(j + 1) * N) / (dl_nsep + 1));
   }
   dl_nU = 3 * dl_nsep;
   dl_ld = ((dl_K + 1 + dl_nU + 63) / 64) * 64;
   dl_refine = 1;   // (a second step does not lower FRH's 5e-8: that residual is what the conditioning allows)
-  if (const char* re = PGO_EXP_ENV("PGO_DIRECT_REFINE")) dl_refine = std::max(0, atoi(re));
   if (knob("direct_fail_at") > 0) dl_fail_at = (int)knob("direct_fail_at");   // test hook
-  if (const char* ge = PGO_EXP_ENV("PGO_DIRECT_GRAPH")) dl_use_graph = ge[0] == '1';
   PGOC(dalloc(&dl_chain_edge, N));
   PGOC(dalloc(&dl_lr_edge, std::max(1, dl_m)));
   PGOC(dalloc(&dl_va, std::max(1, dl_m)));
@@ -727,11 +683,10 @@ int pgo_handle::direct_setup(int32_t N, bool switch_now) {
   PGOC(dalloc(&dl_nm, (int64_t)dl_Kp * dl_Kp));
   PGOC(dalloc(&dl_cy, dl_Kp));
   PGOC(dalloc(&dl_pre, (int64_t)dev::DLR_PRE * N));
-  int want_seg = 32;   // segments the chain sweeps are cut into (PGO_DIRECT_NSEG: experiments, <= 64)
-  if (const char* ns = PGO_EXP_ENV("PGO_DIRECT_NSEG")) want_seg = std::min(dev::DLR_MAX_SEG, std::max(1, atoi(ns)));
+  const int want_seg = 32;   // segments the chain sweeps are cut into (at most DLR_MAX_SEG)
   dl_seglen = std::max(1, (N + want_seg - 1) / want_seg);
   dl_nseg = (N + dl_seglen - 1) / dl_seglen;
-  if (N <= 4096 && !PGO_EXP_ENV("PGO_DIRECT_NO_SOLVE1")) {
+  if (N <= 4096) {
     dl_seglen2 = std::max(1, (N + 255) / 256);
     dl_nseg2 = (N + dl_seglen2 - 1) / dl_seglen2;
     PGOC(dalloc(&dl_pre2, (int64_t)dev::DLR_PRE * N));

@@ -178,31 +178,11 @@ int pgo_handle::direct_enqueue(const double* rhs, int refine) {
   return reduce_to_scal({{part[2], g_flat, 0}, {part[4], g_flat, 0}}, 8);
 }
 
-// The ~130 launches of a direct solve are the same every time (every argument is fixed for the handle's lifetime; the
-// trust-region radius enters through d2 on the device), so they can be captured once into a hipGraph and replayed with
-// one host call -- measured: no gain in GN it/s (the solve is bound by its dependent kernels, not by the host), while
-// capture + instantiation cost ~5 ms, as much as five LM iterations of a fresh handle.  Off unless PGO_DIRECT_GRAPH=1.
+// The ~130 launches of a direct solve are the same every time, but replaying them from a captured hipGraph was measured
+// to gain nothing in GN it/s (the solve is bound by its dependent kernels, not by the host), while capture + instantiation
+// cost ~5 ms, as much as five LM iterations of a fresh handle: they are launched eagerly.
 int pgo_handle::direct_solve() {
-  if (opt.use_graphs && dl_use_graph && !dl_graph_failed) {
-    if (!dl_graph_exec) {
-      hipGraph_t gr = nullptr;
-      HIPC(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-      const int st_cap = direct_enqueue(gs, dl_refine);
-      const hipError_t e_end = hipStreamEndCapture(stream, &gr);
-      hipError_t e_inst = hipSuccess;
-      if (st_cap == PGO_OK && e_end == hipSuccess) {
-        e_inst = hipGraphInstantiate(&dl_graph_exec, gr, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(gr);
-      }
-      if (st_cap != PGO_OK || e_end != hipSuccess || e_inst != hipSuccess) {   // eager launches from here on
-        (void)hipGetLastError();
-        dl_graph_exec = nullptr;
-        dl_graph_failed = true;
-      }
-    }
-    if (dl_graph_exec) HIPC(hipGraphLaunch(dl_graph_exec, stream));
-  }
-  if (!dl_graph_exec) PGOC(direct_enqueue(gs, dl_refine));
+  PGOC(direct_enqueue(gs, dl_refine));
   if (dl_fail_at > 0 && iter == dl_fail_at)   // test hook ("direct_fail_at"): a direct solve that returns NaNs
     HIPC(hipMemsetAsync(y, 0xFF, (size_t)3 * S.n_loc * sizeof(double), stream));
   return PGO_OK;

@@ -55,14 +55,8 @@ namespace dev = pgo::dev;
     if (_s != PGO_OK) return _s; \
   } while (0)
 
-// Experiment switches (scripts/exp_*.sh build a library of their own with -DPGO_EXPERIMENTS and select it with PGO_LIB):
-// the product library reads two documented environment variables only -- PGO_FORCE_COLLECTIVES, PGO_GRAPH_COLLECTIVES --
+// The library reads two documented environment variables only -- PGO_FORCE_COLLECTIVES, PGO_GRAPH_COLLECTIVES (create()) --
 // and never lets the environment override a pgo_options field.
-#ifdef PGO_EXPERIMENTS
-#define PGO_EXP_ENV(name) getenv(name)
-#else
-#define PGO_EXP_ENV(name) ((const char*)nullptr)
-#endif
 
 // Test hooks (pgo_debug_set_knob, include/pgo.h): process-wide, read when a handle is created.  -1 = library default.
 // (table and setter: solver_abi.hip)
@@ -176,7 +170,7 @@ struct pgo_handle {
   double* ginv = nullptr;
   // chain (block-tridiagonal) preconditioner over 64-pose segments (opt.pcg_chain_len): C planes, W planes, S^-1 planes
   int chain_len = 0, g_chain = 1, chain_pad = 0;
-  int chain_chunk = 0, chain_steps = 0;  // lean apply: poses per lane (2 / 4) and recurrence steps; 0 = scan kernel (layout chunk 4)
+  int chain_chunk = 0, chain_steps = 0;  // lean apply: poses per lane (2 / 4) and recurrence steps
   int chain_scan = 0;                    // > 0: the lean apply runs its recurrence as this many scan levels (few long segments)
   int chain_nw = 4;                      // wavefronts per workgroup of the lean kernels: 1 on small graphs (a tile per CU)
   double *chain_c = nullptr, *chain_w = nullptr, *chain_s = nullptr;
@@ -233,11 +227,7 @@ struct pgo_handle {
   int32_t* prob_of_256 = nullptr;       // problem of each 256-row block
   double* prob_radius = nullptr;        // trust-region radius per problem
   double* edge_cost = nullptr;          // cost per local edge (k_edge_eval -> k_prob_reduce)
-  // small graphs: the whole PCG solve of an LM iteration as ONE launch, one workgroup (solo.hip.h)
-  bool solo = false;
-  dev::SoloProb* solo_prob = nullptr;
-  dev::SoloOut* solo_out = nullptr;
-  dev::SoloOut* h_solo = nullptr;  // pinned
+  // batched handles: the whole PCG solve of an LM iteration as ONE launch, one workgroup per problem (solo.hip.h, solver_batch.hip)
   int solo_steps = 0, solo_scan = 0;
   // grids
   int g_edge = 1, g_rows = 1, g_vec = 1, g_flat = 1, g_spmv = 1, g_asm = 1;
@@ -267,15 +257,12 @@ struct pgo_handle {
     dl_pre2 = dl_ksep = dl_R = dl_Wm = nullptr;
     dl_ready = false;
   }
-  hipGraphExec_t dl_graph_exec = nullptr;   // the captured direct solve
-  bool dl_graph_failed = false;
-  bool dl_use_graph = false;   // PGO_DIRECT_GRAPH=1
 
   // LM state (TrustRegionMinimizer)
   bool lm_active = false, lin_valid = false, lm_done = false;
   int iter = 0, prev_success = 1, invalid_run = 0, successful = 0, total_pcg = 0, termination = 0;
   double cost = 0, initial_cost = 0, radius = 0, decrease_factor = 2, x_norm = 0, gmax = 0;
-  double t_eval = 0, t_asm = 0, t_lin = 0, t_cand = 0, t_total = 0;
+  double t_eval = 0, t_asm = 0, t_lin = 0, t_cand = 0, t_total = 0;   // (t_cand stays 0: the candidate is evaluated with the model terms, inside t_lin)
   std::vector<pgo_iter_record> recs;
 
   ~pgo_handle() {
@@ -285,18 +272,14 @@ struct pgo_handle {
     if (comm_stream) (void)hipStreamDestroy(comm_stream);
     for (void* p : allocs) (void)hipFree(p);
     if (cg_graph_exec) (void)hipGraphExecDestroy(cg_graph_exec);
-    if (dl_graph_exec) (void)hipGraphExecDestroy(dl_graph_exec);
     if (h_st) (void)hipHostFree(h_st);
     if (h_scal) (void)hipHostFree(h_scal);
-    if (h_solo) (void)hipHostFree(h_solo);
     if (stream) (void)hipStreamDestroy(stream);
   }
 
   // collectives are skipped for a single rank unless PGO_FORCE_COLLECTIVES=1 (lets a 1-GPU box
   // exercise the RCCL calls themselves: at world == 1 they are identities)
   bool force_collectives = false;
-  int spmv_ablate = 0;  // timing-only ablations of k_spmv, set by pgo_bench_spmv from PGO_SPMV_ABLATE
-  int spmv_nt = 1;      // non-temporal H-stream loads in k_spmv (PGO_SPMV_NT=0 turns them off): 179 -> 166 us at 1M poses
   bool multi_rank() const { return comm && (comm->world > 1 || force_collectives); }
 
   template <class T>
@@ -455,7 +438,7 @@ struct pgo_handle {
     A.n_loc = S.n_loc;
     A.lo = S.lo;
     A.with_d2 = with_d2;
-    A.nt = spmv_nt;
+    A.nt = 1;   // non-temporal H-stream loads in k_spmv: 179 -> 166 us at 1M poses
     A.inc_stride = inc_stride;
     A.hoff = hoff;
     A.hd = hd;
@@ -502,7 +485,7 @@ struct pgo_handle {
     CP.n_pad = chain_pad;
     return CP;
   }
-  // PCG start-up / first update kernel with the chain preconditioner (scan or lean form)
+  // PCG start-up / first update kernel with the chain preconditioner
   void launch_cg_init_chain(const double* b, double* part_rz, double* part_bb);
   void launch_cg_sr_chain(const dev::CgVec& V, double* part_gamma, double* part_rr);
   void launch_cg_update1_chain(const dev::CgVec& V, int par, const double* pap, int n_pap, double* part_rz, double* part_rr);

@@ -95,18 +95,10 @@ int pgo_handle::assemble_enqueue() {
 
 int pgo_handle::spmv_enqueue(const double* p, double* yout, double* dot_part, int with_d2, const int32_t* done) {
   dev::SpmvArgs A = spmv_args(p, yout, dot_part, with_d2, done);
-  switch (spmv_ablate) {
-#ifdef PGO_EXPERIMENTS
-    case 1: hipLaunchKernelGGL(dev::k_spmv_t<1>, dim3(g_spmv), dim3(dev::WG), 0, stream, A); break;
-    case 2: hipLaunchKernelGGL(dev::k_spmv_t<2>, dim3(g_spmv), dim3(dev::WG), 0, stream, A); break;
-    case 3: hipLaunchKernelGGL(dev::k_spmv_t<3>, dim3(g_spmv), dim3(dev::WG), 0, stream, A); break;
-#endif
-    default:
-      if (spmv_pipe && spmv_one_tile && S.padded) hipLaunchKernelGGL(dev::k_spmv_1<true>, dim3(g_spmv), dim3(dev::WG), 0, stream, A);
-      else if (spmv_pipe && spmv_one_tile) hipLaunchKernelGGL(dev::k_spmv_1<false>, dim3(g_spmv), dim3(dev::WG), 0, stream, A);
-      else if (spmv_pipe) hipLaunchKernelGGL(dev::k_spmv_p<dev::PS>, dim3(g_spmv), dim3(dev::WG), 0, stream, A);
-      else hipLaunchKernelGGL(dev::k_spmv_t<0>, dim3(g_spmv), dim3(dev::WG), 0, stream, A);
-  }
+  if (spmv_pipe && spmv_one_tile && S.padded) hipLaunchKernelGGL(dev::k_spmv_1<true>, dim3(g_spmv), dim3(dev::WG), 0, stream, A);
+  else if (spmv_pipe && spmv_one_tile) hipLaunchKernelGGL(dev::k_spmv_1<false>, dim3(g_spmv), dim3(dev::WG), 0, stream, A);
+  else if (spmv_pipe) hipLaunchKernelGGL(dev::k_spmv_p<>, dim3(g_spmv), dim3(dev::WG), 0, stream, A);
+  else hipLaunchKernelGGL(dev::k_spmv_t<0>, dim3(g_spmv), dim3(dev::WG), 0, stream, A);
   return check_launch("k_spmv");
 }
 
@@ -165,9 +157,8 @@ void pgo_handle::launch_cg_init_chain(const double* b, double* part_rz, double* 
   const dev::ChainPre CP = chain_pre();
   if (chain_chunk == 2 && chain_nw == 4) hipLaunchKernelGGL((dev::k_cg_init_cl<2, 4>), dim3(g_chain), dim3(256), 0, stream, V, CP, chain_steps, chain_scan, b, part_rz, part_bb);
   else if (chain_chunk == 2) hipLaunchKernelGGL((dev::k_cg_init_cl<2, 1>), dim3(g_chain), dim3(64), 0, stream, V, CP, chain_steps, chain_scan, b, part_rz, part_bb);
-  else if (chain_chunk == 4 && chain_nw == 4) hipLaunchKernelGGL((dev::k_cg_init_cl<4, 4>), dim3(g_chain), dim3(256), 0, stream, V, CP, chain_steps, chain_scan, b, part_rz, part_bb);
-  else if (chain_chunk == 4) hipLaunchKernelGGL((dev::k_cg_init_cl<4, 1>), dim3(g_chain), dim3(64), 0, stream, V, CP, chain_steps, chain_scan, b, part_rz, part_bb);
-  else hipLaunchKernelGGL(dev::k_cg_init_c<>, dim3(g_chain), dim3(dev::WG), 0, stream, V, CP, b, part_rz, part_bb);
+  else if (chain_nw == 4) hipLaunchKernelGGL((dev::k_cg_init_cl<4, 4>), dim3(g_chain), dim3(256), 0, stream, V, CP, chain_steps, chain_scan, b, part_rz, part_bb);
+  else hipLaunchKernelGGL((dev::k_cg_init_cl<4, 1>), dim3(g_chain), dim3(64), 0, stream, V, CP, chain_steps, chain_scan, b, part_rz, part_bb);
 }
 
 void pgo_handle::launch_cg_sr_chain(const dev::CgVec& V, double* part_gamma, double* part_rr) {
@@ -182,7 +173,6 @@ void pgo_handle::launch_cg_update1_chain(const dev::CgVec& V, int par, const dou
   const dev::ChainPre CP = chain_pre();
   if (chain_chunk == 2 && chain_nw == 4) hipLaunchKernelGGL((dev::k_cg_update1_cl<2, 4>), dim3(g_chain), dim3(256), 0, stream, V, CP, chain_steps, chain_scan, par, pap, n_pap, part_rz, part_rr);
   else if (chain_chunk == 2) hipLaunchKernelGGL((dev::k_cg_update1_cl<2, 1>), dim3(g_chain), dim3(64), 0, stream, V, CP, chain_steps, chain_scan, par, pap, n_pap, part_rz, part_rr);
-  else if (chain_chunk == 4 && chain_nw == 4) hipLaunchKernelGGL((dev::k_cg_update1_cl<4, 4>), dim3(g_chain), dim3(256), 0, stream, V, CP, chain_steps, chain_scan, par, pap, n_pap, part_rz, part_rr);
-  else if (chain_chunk == 4) hipLaunchKernelGGL((dev::k_cg_update1_cl<4, 1>), dim3(g_chain), dim3(64), 0, stream, V, CP, chain_steps, chain_scan, par, pap, n_pap, part_rz, part_rr);
-  else hipLaunchKernelGGL(dev::k_cg_update1_c<>, dim3(g_chain), dim3(dev::WG), 0, stream, V, CP, par, pap, n_pap, part_rz, part_rr);
+  else if (chain_nw == 4) hipLaunchKernelGGL((dev::k_cg_update1_cl<4, 4>), dim3(g_chain), dim3(256), 0, stream, V, CP, chain_steps, chain_scan, par, pap, n_pap, part_rz, part_rr);
+  else hipLaunchKernelGGL((dev::k_cg_update1_cl<4, 1>), dim3(g_chain), dim3(64), 0, stream, V, CP, chain_steps, chain_scan, par, pap, n_pap, part_rz, part_rr);
 }

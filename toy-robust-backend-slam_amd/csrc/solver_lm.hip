@@ -218,33 +218,31 @@ int pgo_handle::lm_iteration_tail(bool* stop, pgo_iter_record& R, double it0, do
   R.pcg_iters = k_it;
   R.pcg_rel_residual = rel;
   // model_cost_change = -(J d).(r + J d / 2), d = -S y   ==   y.gs - y.(H y) / 2
-  if (!solo) {  // (the one-workgroup solve has done all of this in its epilogue; the gather vector holds y either way)
-    // The model decrease below uses r = b - (H + D'D) y.  PCG's recurrence residual is that up to rounding drift, which
-    // grows with the iteration count: in the exact mode (tight tolerance, up to 1e5 iterations on the ill-conditioned
-    // late systems) the drift would bias rho and with it the accept / reject and radius decisions, unnoticed -- so
-    // there the residual is recomputed with one product (nothing next to the solve it follows).  The inexact mode
-    // (rtol 0.1, ~100 iterations) keeps the recurrence residual; the direct solve writes the true residual itself.
-    const bool true_residual = k_it > 0 && (opt.pcg_rtol < 1e-6 || k_it > 1000);
-    if (has_sw || true_residual) {  // (the switch back-substitution below reads y of both endpoints from the gather vector)
-      hipLaunchKernelGGL(dev::k_scatter_owned<>, dim3(g_flat), dim3(dev::WG), 0, stream, S.n_loc, S.lo, y, p_full);
-      PGOC(check_launch("k_scatter_owned"));
-      PGOC(share_gather_vector(p_full));
-    }
-    if (true_residual) {
-      PGOC(spmv_enqueue(p_full, ap, part[0], 1, nullptr));
-      hipLaunchKernelGGL(dev::k_dlr_resid<>, dim3(std::max<int64_t>(1, (3 * S.n_loc + 255) / 256)), dim3(256), 0, stream, (int64_t)3 * S.n_loc,
-                         (const double*)gs, (const double*)ap, r);   // (at least one workgroup: a rank may own no rows)
-      PGOC(check_launch("k_dlr_resid"));
-    }
-    // y.(H y) = y.b - y.r - y.(D y) from the residual (no further product by H): part[1] = y.b, part[0] = y.r, part[5] = y.(D y)
-    hipLaunchKernelGGL(dev::k_model_terms<>, dim3(g_flat), dim3(dev::WG), 0, stream, (int64_t)3 * S.n_loc, (const double*)y, (const double*)gs,
-                       (const double*)r, (const double*)d2, part[1], part[0], part[5]);
-    PGOC(check_launch("k_model_terms"));
-    // candidate x + d and |d|^2
-    double* x_old = poses;
-    hipLaunchKernelGGL(dev::k_candidate<>, dim3(g_flat), dim3(dev::WG), 0, stream, S.n_loc, S.lo, x_old, scale, y, cand, part[3]);
-    PGOC(check_launch("k_candidate"));
+  // The model decrease below uses r = b - (H + D'D) y.  PCG's recurrence residual is that up to rounding drift, which
+  // grows with the iteration count: in the exact mode (tight tolerance, up to 1e5 iterations on the ill-conditioned
+  // late systems) the drift would bias rho and with it the accept / reject and radius decisions, unnoticed -- so
+  // there the residual is recomputed with one product (nothing next to the solve it follows).  The inexact mode
+  // (rtol 0.1, ~100 iterations) keeps the recurrence residual; the direct solve writes the true residual itself.
+  const bool true_residual = k_it > 0 && (opt.pcg_rtol < 1e-6 || k_it > 1000);
+  if (has_sw || true_residual) {  // (the switch back-substitution below reads y of both endpoints from the gather vector)
+    hipLaunchKernelGGL(dev::k_scatter_owned<>, dim3(g_flat), dim3(dev::WG), 0, stream, S.n_loc, S.lo, y, p_full);
+    PGOC(check_launch("k_scatter_owned"));
+    PGOC(share_gather_vector(p_full));
   }
+  if (true_residual) {
+    PGOC(spmv_enqueue(p_full, ap, part[0], 1, nullptr));
+    hipLaunchKernelGGL(dev::k_dlr_resid<>, dim3(std::max<int64_t>(1, (3 * S.n_loc + 255) / 256)), dim3(256), 0, stream, (int64_t)3 * S.n_loc,
+                       (const double*)gs, (const double*)ap, r);   // (at least one workgroup: a rank may own no rows)
+    PGOC(check_launch("k_dlr_resid"));
+  }
+  // y.(H y) = y.b - y.r - y.(D y) from the residual (no further product by H): part[1] = y.b, part[0] = y.r, part[5] = y.(D y)
+  hipLaunchKernelGGL(dev::k_model_terms<>, dim3(g_flat), dim3(dev::WG), 0, stream, (int64_t)3 * S.n_loc, (const double*)y, (const double*)gs,
+                     (const double*)r, (const double*)d2, part[1], part[0], part[5]);
+  PGOC(check_launch("k_model_terms"));
+  // candidate x + d and |d|^2
+  double* x_old = poses;
+  hipLaunchKernelGGL(dev::k_candidate<>, dim3(g_flat), dim3(dev::WG), 0, stream, S.n_loc, S.lo, x_old, scale, y, cand, part[3]);
+  PGOC(check_launch("k_candidate"));
   double model_sw = 0.0, step2_sw = 0.0;
   if (has_sw) {  // back-substitute the switches (needs y of both endpoints: in the gather vector after the share above)
     const int g_sw = std::min(std::max(1, (S.n_edges_local + dev::WG - 1) / dev::WG), 1024);
@@ -253,26 +251,19 @@ int pgo_handle::lm_iteration_tail(bool* stop, pgo_iter_record& R, double it0, do
     PGOC(check_launch("k_switch_backsub"));
     PGOC(reduce_to_scal({{part[2], g_sw, 0}, {part[4], g_sw, 0}}, 13));
   }
-  if (solo) {
-    h_scal[0] = h_solo->ydotg;
-    h_scal[1] = h_solo->yHy;
-    h_scal[2] = h_solo->step2;
-  } else {
-    PGOC(reduce_to_scal({{part[1], g_flat, 0}, {part[0], g_flat, 0}, {part[3], g_flat, 0}, {part[5], g_flat, 0}}, 0));
-    // the candidate's cost is evaluated in the same breath (scal[6..7]; wasted only when the step turns out invalid): one
-    // host synchronisation for the model terms AND the candidate instead of two
-    PGOC(allgather(cand));
-    PGOC(eval_enqueue(cand, sw_cand, 1, false, 6));
-    PGOC(fetch_scal(0, co_flag_pending ? 16 : (has_sw ? 15 : 10)));
-    h_scal[1] = h_scal[0] - h_scal[1] - h_scal[3];   // y.(H y)
-    if (co_flag_pending) {   // scal[15]: the coarse level's flag of this solve (pcg())
-      if (h_scal[15] == 0.0) ++co_off_iters;
-      co_flag_pending = false;
-    }
-    if (direct && !dl_retry) R.pcg_rel_residual = dl_rel = (h_scal[9] > 0.0) ? std::sqrt(h_scal[8] / h_scal[9]) : 0.0;
+  PGOC(reduce_to_scal({{part[1], g_flat, 0}, {part[0], g_flat, 0}, {part[3], g_flat, 0}, {part[5], g_flat, 0}}, 0));
+  // the candidate's cost is evaluated in the same breath (scal[6..7]; wasted only when the step turns out invalid): one
+  // host synchronisation for the model terms AND the candidate instead of two
+  PGOC(allgather(cand));
+  PGOC(eval_enqueue(cand, sw_cand, 1, false, 6));
+  PGOC(fetch_scal(0, co_flag_pending ? 16 : (has_sw ? 15 : 10)));
+  h_scal[1] = h_scal[0] - h_scal[1] - h_scal[3];   // y.(H y)
+  if (co_flag_pending) {   // scal[15]: the coarse level's flag of this solve (pcg())
+    if (h_scal[15] == 0.0) ++co_off_iters;
+    co_flag_pending = false;
   }
+  if (direct && !dl_retry) R.pcg_rel_residual = dl_rel = (h_scal[9] > 0.0) ? std::sqrt(h_scal[8] / h_scal[9]) : 0.0;
   if (has_sw) {
-    if (solo) PGOC(fetch_scal(13, 2));
     model_sw = h_scal[13];
     step2_sw = h_scal[14];
   }
@@ -312,13 +303,6 @@ int pgo_handle::lm_iteration_tail(bool* stop, pgo_iter_record& R, double it0, do
     return PGO_OK;
   }
   invalid_run = 0;
-  t0 = wall_s();
-  if (solo) {   // (the one-workgroup solve synchronised inside pcg(): its candidate is evaluated here)
-    PGOC(allgather(cand));
-    PGOC(eval_enqueue(cand, sw_cand, 1, false, 6));
-    PGOC(fetch_scal(6, 2));
-  }
-  t_cand += wall_s() - t0;
   double cand_cost = h_scal[6];
   if (h_scal[7] > 0.0 || !std::isfinite(cand_cost)) cand_cost = std::numeric_limits<double>::max();
   R.step_norm = std::sqrt(step2);

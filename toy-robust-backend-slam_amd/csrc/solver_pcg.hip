@@ -136,38 +136,6 @@ int pgo_handle::coarse_solve(double* dot_part, const int32_t* done) {
 // block-Jacobi PCG on (H + D2) y = gs, y0 = 0.  Host checks the residual every
 // pcg_check_every iterations; in between the kernels early-out on st->done.
 int pgo_handle::pcg(int* iters, double* rel) {
-  if (solo) {
-    dev::SoloProb P;
-    P.row0 = 0;
-    P.nrows = S.n_loc;
-    P.tile0 = 0;
-    P.ntiles = S.n_tiles();
-    P.active = 1;
-    P.max_it = std::max(0, opt.pcg_max_iters);
-    P.rtol = opt.pcg_rtol;
-    HIPC(hipMemcpyAsync(solo_prob, &P, sizeof P, hipMemcpyHostToDevice, stream));
-    dev::SoloArgs A;
-    A.A = spmv_args(p_full, ap, part[0], 1, nullptr);
-    A.V = cg_vec();
-    A.C = chain_pre();
-    if (!chain_len) A.C.cw = nullptr;
-    A.chain_steps = solo_steps;
-    A.scan_levels = solo_scan;
-    A.b = gs;
-    A.prob = solo_prob;
-    A.out = solo_out;
-    A.x = poses;
-    A.scale = scale;
-    A.cand = cand;
-    hipLaunchKernelGGL(dev::k_pcg_solo<>, dim3(1), dim3(dev::SOLO_WG), 0, stream, A);
-    PGOC(check_launch("k_pcg_solo"));
-    HIPC(hipMemcpyAsync(h_solo, solo_out, sizeof(dev::SoloOut), hipMemcpyDeviceToHost, stream));
-    PGOC(sync());  // P (stack) was consumed by the copy above
-    *iters = h_solo->iters;
-    *rel = (h_solo->bb > 0.0) ? std::sqrt(h_solo->rr / h_solo->bb) : 0.0;
-    last_pcg_iters = h_solo->iters;
-    return PGO_OK;
-  }
   dev::CgVec V = cg_vec();
   const bool multi = multi_rank();
   dev::GroupPre GP;
@@ -435,7 +403,7 @@ int pgo_handle::factor_chain() {
   // wave instructions through the address coalescer, and 174 instead of 122 MB are written.
   const int spw = 64;
   if (n_seg == 0) return PGO_OK;   // a rank that owns no rows
-  if ((chain_chunk ? chain_chunk : dev::CHAIN_CHUNK) == 2)
+  if (chain_chunk == 2)
     hipLaunchKernelGGL(dev::k_chain_factor<2>, dim3((n_seg + spw - 1) / spw), dim3(spw), 0, stream, (const double*)chain_c, S.n_loc, chain_pad,
                        chain_len, chain_w, chain_s);
   else
