@@ -500,6 +500,47 @@ int  pgo_pose_covariance(pgo_t* h, int32_t n, const int32_t* poses /* caller's n
                          const pgo_covariance_options* opt_or_null, double* out,
                          pgo_covariance_report* report_or_null);                           /* [gpu]  */
 
+/* ------------------------------------------------------------- edge gate
+ * Is a candidate loop edge consistent with the current estimate, and what would it add?  For candidate k = (a, b, meas, Omega)
+ * in the caller's pose numbering -- it need NOT be an edge of the graph -- at the handle's CURRENT poses:
+ *   r             the plain residual (ex, ey, asin(clamp(sin delta))) of pgo_edge_chi2
+ *   J             3x6 row-major [d r/d Pa | d r/d Pb] of the plain (METHOD 0) functor, with g = cos delta / sqrt(1 - sin^2 delta);
+ *                 no loss and no DCS on the candidate
+ *   P             J Sigma_[ab] J' (3x3 row-major, stored symmetric as 1/2 (P + P')), Sigma what pgo_pose_covariance defines on the
+ *                 active problem: the covariance of the predicted residual
+ *   chi2          r' Omega r, clamped at 0 (the point gate, pgo_edge_chi2)
+ *   chi2_marginal r' (P + Omega^-1)^-1 r, computed as (L'r)' M^-1 (L'r) with Omega = L L', M = I + L' P L (the innovation gate)
+ *   info_gain     1/2 logdet M = 1/2 logdet(I + Omega P) = 1/2 [logdet(Lambda + J' Omega J) - logdet Lambda], Lambda = J'J of the
+ *                 problem.  The layer managers' 1/2 logdet(I + Omega) (src/layer_manager.cpp:284-298) is its P = I case.
+ * info6 = n x 6 (I11 I12 I13 I22 I23 I33) or NULL = the identity, the weight the handle's default objective
+ * (info_weighting = 0) gives every block.  The numbers are meant for edges that are NOT residual blocks of the active problem; for
+ * an edge that is one they are still the quantities defined above.
+ * Solved as A X = S J' on the system of pgo_pose_covariance: THREE columns per candidate (six non-zeros each), `poses_per_pass`
+ * candidates per pass (1..16; the "cov_poses_per_pass" knob applies), `cross` ignored; P, the 3x3 algebra and the result
+ * records are formed on the device in fixed order: two calls are bitwise equal.  Tolerance, residual replacement,
+ * PGO_ERR_NUMERIC and "the LM state is left as it was" are those of pgo_pose_covariance.  report.columns counts the columns
+ * solved: 3 x (candidates with status 0 and a non-zero right-hand side).
+ * - A candidate whose r or J is not finite at the current poses (|sin delta| = 1) is not a call failure: status = 1, every
+ *   double of its record NaN, no columns.
+ * - A resolved-constant endpoint (opt.fixed_pose, pose_constant, a pose without an active edge) contributes nothing.  Both
+ *   endpoints constant: P = 0 and info_gain = 0 exactly, chi2_marginal = chi2 up to rounding (the same code path), no columns.
+ * Errors: PGO_ERR_UNSUPPORTED as pgo_pose_covariance (world > 1, batched handles, info_weighting = 1, no constant pose);
+ * PGO_ERR_INVALID_ARG for a == b, an index out of range, an Omega that is not finite and positive definite (checked on the
+ * host before any launch), a null pointer with n > 0, METHOD 2 before pgo_lm_begin.  n == 0 is PGO_OK.                   */
+typedef struct pgo_edge_gate_result {
+  double r[3], J[18], P[9];
+  double chi2, chi2_marginal, info_gain;
+  int32_t status;   /* 0 ok; 1 = non-finite r or J at the current poses: every double above is NaN */
+  int32_t _pad;
+} pgo_edge_gate_result;
+/* the 3x3 algebra alone (csrc/gate.h, what the device runs): out = {chi2, chi2_marginal, info_gain} from r, P (row-major,
+ * symmetric) and Omega.  PGO_ERR_INVALID_ARG: a null pointer, an Omega that is not finite and positive definite;
+ * PGO_ERR_NUMERIC: M = I + L' P L is not positive definite (an indefinite P).                                          */
+int pgo_gate_evaluate(const double r[3], const double P[9], const double* info6_or_null, double out[3]);   /* [host] */
+int pgo_edge_gate(pgo_t* h, int32_t n, const int32_t* ia, const int32_t* ib, const double* meas_xyt /* n x 3 */,
+                  const double* info6_or_null /* n x 6 */, const pgo_covariance_options* opt_or_null,
+                  pgo_edge_gate_result* out /* n */, pgo_covariance_report* report_or_null);                /* [gpu]  */
+
 /* ------------------------------------------------ kernel-level entry points
  * Used by the parity tests and by bench.py's roofline leg: each launches exactly
  * one kind of kernel `reps` times on the handle's stream, brackets the launches
@@ -555,7 +596,7 @@ int pgo_debug_normal_eq(pgo_t* h, double* g_or_null, double* hdiag_or_null);    
  *   "pad_tiles"          0 = large graphs keep the dense incidence layout (default: every row tile padded to 256 incidence
  *                        slots of its own, so that K3 finds a tile's blocks from its number alone; same results);
  *                        1 = that layout and its product kernel (k_spmv_1) on a graph of any size
- *   "cov_poses_per_pass" 1..16 = overrides pgo_covariance_options.poses_per_pass of every pgo_pose_covariance call (read per call;
+ *   "cov_poses_per_pass" 1..16 = overrides pgo_covariance_options.poses_per_pass of every pgo_pose_covariance / pgo_edge_gate call (read per call;
  *                        the results agree with every value up to the solver tolerance)
  * Unknown name: PGO_ERR_INVALID_ARG.                                                                              */
 int pgo_debug_set_knob(const char* name, long long value);                        /* [host] */

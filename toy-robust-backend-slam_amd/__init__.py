@@ -22,7 +22,7 @@ from . import _build
 
 __all__ = ["PgoError", "Options", "Summary", "IterRecord", "ReadG2O", "Graph", "Solver", "Batch", "Comm", "lib", "build",
            "HandleInfo", "synth_manhattan", "solve_batch", "shard_plan", "shard_halo", "pose_order", "set_knob", "KernelStats", "EXPORTS", "TERMINATION",
-           "CovarianceOptions", "CovarianceReport", "Loss", "LOSS_TYPES", "active_plan"]
+           "CovarianceOptions", "CovarianceReport", "Loss", "LOSS_TYPES", "active_plan", "EdgeGateResult", "gate_evaluate"]
 
 EDGE_ODOMETRY, EDGE_CLOSURE, EDGE_BOGUS = 0, 1, 2
 TERMINATION = {1: "CONVERGENCE_FTOL", 2: "CONVERGENCE_GTOL", 3: "CONVERGENCE_PTOL", 4: "NO_CONVERGENCE",
@@ -48,6 +48,7 @@ EXPORTS = [
     "pgo_covariance_options_default", "pgo_pose_covariance",
     "pgo_loss_evaluate", "pgo_set_losses", "pgo_batch_set_losses",
     "pgo_set_active", "pgo_batch_set_active", "pgo_active_plan",
+    "pgo_gate_evaluate", "pgo_edge_gate",
 ]
 LOSS_TYPES = {"trivial": 0, "huber": 1, "softlone": 2, "cauchy": 3, "arctan": 4, "tukey": 5}   # pgo_loss_type
 
@@ -179,6 +180,12 @@ class CovarianceReport(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class EdgeGateResult(C.Structure):
+    """mirror of pgo_edge_gate_result: one candidate of Solver.gate"""
+    _fields_ = [("r", C.c_double * 3), ("J", C.c_double * 18), ("P", C.c_double * 9), ("chi2", C.c_double),
+                ("chi2_marginal", C.c_double), ("info_gain", C.c_double), ("status", C.c_int32), ("_pad", C.c_int32)]
+
+
 _LIB = None
 
 
@@ -288,6 +295,9 @@ def lib():
     L.pgo_set_active.argtypes = [vp, bp, bp]
     L.pgo_batch_set_active.argtypes = [vp, bp, bp]
     L.pgo_active_plan.argtypes = [C.c_int32, C.c_int32, ip, ip, bp, bp, C.c_int32, bp, ip, ip]
+    L.pgo_gate_evaluate.argtypes = [dp, dp, dp, dp]
+    L.pgo_edge_gate.argtypes = [vp, C.c_int32, ip, ip, dp, dp, C.POINTER(CovarianceOptions), C.POINTER(EdgeGateResult),
+                                C.POINTER(CovarianceReport)]
     _LIB = L
     return L
 
@@ -468,6 +478,17 @@ def active_plan(n_poses, ia, ib, edge_active=None, pose_constant=None, fixed_pos
     _check(lib().pgo_active_plan(n_poses, len(ia), _ip(ia), _ip(ib), _bp(ea) if ea is not None else None,
                                  _bp(pc) if pc is not None else None, fixed_pose, _bp(const), C.byref(na), C.byref(nf)))
     return const, na.value, nf.value
+
+
+def gate_evaluate(r, P, info=None):
+    """pgo_gate_evaluate (host only), the 3x3 algebra of Solver.gate: (chi2, chi2_marginal, info_gain) from the residual r,
+    the covariance P (3x3) of the predicted residual and the information (I11 I12 I13 I22 I23 I33), None = the identity"""
+    r = np.ascontiguousarray(r, np.float64).reshape(3)
+    P = np.ascontiguousarray(P, np.float64).reshape(9)
+    w = np.ascontiguousarray(info, np.float64).reshape(6) if info is not None else None
+    out = np.zeros(3)
+    _check(lib().pgo_gate_evaluate(_dp(r), _dp(P), _dp(w), _dp(out)))
+    return float(out[0]), float(out[1]), float(out[2])
 
 
 def set_knob(name: str, value: int = -1):
@@ -707,6 +728,28 @@ class Solver:
         out = np.zeros((3 * n, 3 * n) if cross else (n, 3, 3))
         rep = CovarianceReport()
         _check(lib().pgo_pose_covariance(self._h, n, _ip(idx), C.byref(o), _dp(out), C.byref(rep)))
+        return out, rep.as_dict()
+
+    def gate(self, ia, ib, meas, info=None, **opts):
+        """pgo_edge_gate: candidate loop edges (ia[k], ib[k], meas[k], info[k]) against the current estimate -- they need
+        not be edges of the graph.  info = (n, 6) information entries or None (the identity).  Returns (dict of arrays
+        r (n, 3), J (n, 3, 6), P (n, 3, 3), chi2, chi2_marginal, info_gain, status (n), report dict); opts: the
+        CovarianceOptions fields (poses_per_pass = candidates per pass)."""
+        ia = np.ascontiguousarray(np.asarray(ia, np.int64).reshape(-1), np.int32)
+        ib = np.ascontiguousarray(np.asarray(ib, np.int64).reshape(-1), np.int32)
+        n = ia.size
+        meas = np.ascontiguousarray(meas, np.float64).reshape(-1, 3)
+        w = np.ascontiguousarray(info, np.float64).reshape(-1, 6) if info is not None else None
+        if ib.size != n or meas.shape[0] != n or (w is not None and w.shape[0] != n):
+            raise ValueError("gate: ia, ib, meas and info must have one entry per candidate")
+        o = CovarianceOptions(**opts)
+        res = (EdgeGateResult * max(n, 1))()
+        rep = CovarianceReport()
+        _check(lib().pgo_edge_gate(self._h, n, _ip(ia), _ip(ib), _dp(meas), _dp(w), C.byref(o), res, C.byref(rep)))
+        a = np.ctypeslib.as_array(res)[:n]
+        out = {"r": a["r"].copy(), "J": a["J"].reshape(n, 3, 6).copy(), "P": a["P"].reshape(n, 3, 3).copy(),
+               "chi2": a["chi2"].copy(), "chi2_marginal": a["chi2_marginal"].copy(), "info_gain": a["info_gain"].copy(),
+               "status": a["status"].copy()}
         return out, rep.as_dict()
 
     def write_back(self):

@@ -1,8 +1,10 @@
 #pragma once
-// Kernels of pgo_pose_covariance (solver_covariance.hip): PCG on m right-hand sides at once for the undamped, Jacobi-scaled
-// normal equations A X = S E.  Vectors are column-major panels [m][3N] in the internal pose order (column c at c * ld).
+// Kernels of pgo_pose_covariance and pgo_edge_gate (solver_covariance.hip): PCG on m right-hand sides at once for the
+// undamped, Jacobi-scaled normal equations A X = B (B = S E: unit vectors; B = S J': the sparse columns of the gate).  Vectors are column-major panels [m][3N] in the internal pose order (column c at c * ld).
 // Every column has its own scalars (CovCol) and stops on its own; a stopped column is frozen by the `done` mask.  Every
 // reduction is a fixed-order sum of per-workgroup partials (no atomics): the results are bitwise reproducible.
+#include "pgo.h"
+#include "gate.h"
 #include "kernels.hip.h"
 
 namespace pgo {
@@ -99,17 +101,59 @@ __global__ __launch_bounds__(WG) void k_spmm(SpmmArgs A) {
   }
 }
 
-// Right-hand sides and start: column c is S e_k with k = rows[c] (the internal row of pose component c); X = 0, R = B, P = 0.
-// Grid (g, m).  part_bb[c * g + block].
-template <int PGO_UNIT_ = 0>
-__global__ __launch_bounds__(WG) void k_cov_rhs(int64_t n3, int64_t ld, const int32_t* __restrict__ rows, const double* __restrict__ scale,
-                                                double* __restrict__ x, double* __restrict__ r, double* __restrict__ p, double* __restrict__ part_bb) {
+// One candidate of pgo_edge_gate as k_gate_eval leaves it, a 64-byte-aligned record: the plain residual, its Jacobian
+// [d r/d Pa | d r/d Pb] (3x6 row-major), the internal rows 3 a, 3 b of its endpoints, status 1 = r or J not finite, and
+// nonzero = some entry of S J' is not 0 (an endpoint is not constant)
+struct alignas(64) GateRec {
+  double J[18];
+  double r[3];
+  int32_t ra, rb;
+  int32_t status, nonzero;
+};
+
+// The right-hand sides of a pass, as functors: column(c) = what column c needs, at(col, i) = its entry in row i.
+// RhsUnit: column c is S e_k with k = rows[c] (the internal row of pose component c) -- pgo_pose_covariance.
+struct RhsUnit {
+  const int32_t* __restrict__ rows;
+  const double* __restrict__ scale;
+  struct Col {
+    int64_t k;
+  };
+  __device__ __forceinline__ Col column(int c) const { return Col{rows[c]}; }
+  __device__ __forceinline__ double at(const Col& q, int64_t i) const { return (i == q.k) ? scale[i] : 0.0; }
+};
+// RhsSparse: column 3 j + c is S J_c' of the pass's j-th candidate (record cand[j]): scale[i] J[c][i - ra] on the rows
+// ra .. ra + 2, the b half on rb .. rb + 2 (a != b) -- pgo_edge_gate.
+struct RhsSparse {
+  const GateRec* __restrict__ rec;
+  const int32_t* __restrict__ cand;
+  const double* __restrict__ scale;
+  struct Col {
+    int64_t ra, rb;
+    const double* j;
+  };
+  __device__ __forceinline__ Col column(int c) const {
+    const GateRec& g = rec[cand[c / 3]];
+    return Col{g.ra, g.rb, g.J + 6 * (c % 3)};
+  }
+  __device__ __forceinline__ double at(const Col& q, int64_t i) const {
+    const int64_t da = i - q.ra, db = i - q.rb;
+    if (da >= 0 && da < 3) return scale[i] * q.j[da];
+    if (db >= 0 && db < 3) return scale[i] * q.j[3 + db];
+    return 0.0;
+  }
+};
+
+// Right-hand sides and start: X = 0, R = B, P = 0.  Grid (g, m).  part_bb[c * g + block].
+template <class RHS>
+__global__ __launch_bounds__(WG) void k_cov_rhs(int64_t n3, int64_t ld, RHS B, double* __restrict__ x, double* __restrict__ r, double* __restrict__ p,
+                                                double* __restrict__ part_bb) {
   __shared__ double red[8];
   const int c = blockIdx.y;
-  const int64_t k = rows[c];
+  const typename RHS::Col q = B.column(c);
   double bb = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * WG + threadIdx.x; i < n3; i += (int64_t)gridDim.x * WG) {
-    const double b = (i == k) ? scale[i] : 0.0;
+    const double b = B.at(q, i);
     x[c * ld + i] = 0.0;
     p[c * ld + i] = 0.0;
     r[c * ld + i] = b;
@@ -218,31 +262,29 @@ __global__ __launch_bounds__(WG) void k_cov_pupdate(int64_t n3, int64_t ld, cons
   for (int64_t i = (int64_t)blockIdx.x * WG + threadIdx.x; i < n3; i += (int64_t)gridDim.x * WG) p[c * ld + i] = z[c * ld + i] + beta * p[c * ld + i];
 }
 
-// true residual R = S E - A X of every column after the product A X (k_spmm into y): partials of |r|^2 (grid (g, m))
-template <int PGO_UNIT_ = 0>
-__global__ __launch_bounds__(WG) void k_cov_resid(int64_t n3, int64_t ld, const int32_t* __restrict__ rows, const double* __restrict__ scale,
-                                                  const double* __restrict__ ax, double* __restrict__ part) {
+// true residual R = B - A X of every column after the product A X (k_spmm into y): partials of |r|^2 (grid (g, m))
+template <class RHS>
+__global__ __launch_bounds__(WG) void k_cov_resid(int64_t n3, int64_t ld, RHS B, const double* __restrict__ ax, double* __restrict__ part) {
   __shared__ double red[8];
   const int c = blockIdx.y;
-  const int64_t k = rows[c];
+  const typename RHS::Col q = B.column(c);
   double s = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * WG + threadIdx.x; i < n3; i += (int64_t)gridDim.x * WG) {
-    const double d = ((i == k) ? scale[i] : 0.0) - ax[c * ld + i];
+    const double d = B.at(q, i) - ax[c * ld + i];
     s += d * d;
   }
   s = block_sum_bcast(s, red);
   if (threadIdx.x == 0) part[(int64_t)c * gridDim.x + blockIdx.x] = s;
 }
 
-// residual replacement for the columns of mask: r = S e - A X from the product A X in ax (grid (g, m))
-template <int PGO_UNIT_ = 0>
-__global__ __launch_bounds__(WG) void k_cov_replace(int64_t n3, int64_t ld, const int32_t* __restrict__ rows, const double* __restrict__ scale,
-                                                    const double* __restrict__ ax, double* __restrict__ r, const uint8_t* __restrict__ mask) {
+// residual replacement for the columns of mask: r = B - A X from the product A X in ax (grid (g, m))
+template <class RHS>
+__global__ __launch_bounds__(WG) void k_cov_replace(int64_t n3, int64_t ld, RHS B, const double* __restrict__ ax, double* __restrict__ r,
+                                                    const uint8_t* __restrict__ mask) {
   const int c = blockIdx.y;
   if (!mask[c]) return;
-  const int64_t k = rows[c];
-  for (int64_t i = (int64_t)blockIdx.x * WG + threadIdx.x; i < n3; i += (int64_t)gridDim.x * WG)
-    r[c * ld + i] = ((i == k) ? scale[i] : 0.0) - ax[c * ld + i];
+  const typename RHS::Col q = B.column(c);
+  for (int64_t i = (int64_t)blockIdx.x * WG + threadIdx.x; i < n3; i += (int64_t)gridDim.x * WG) r[c * ld + i] = B.at(q, i) - ax[c * ld + i];
 }
 
 // the columns of mask run again (one thread per column)
@@ -298,6 +340,114 @@ __global__ __launch_bounds__(WG) void k_cov_check_rows(int n, const double* __re
     __syncthreads();
   }
   if (threadIdx.x == 0) part[blockIdx.x] = sh[0];
+}
+
+// ---------------------------------------------------------------- pgo_edge_gate
+// One lane per candidate (a, b, meas) at the current poses: the plain residual of k_edge_chi2 (heading clamped), the
+// Jacobian of the plain functor in K1's form (g = cos delta / sqrt(1 - sin^2 delta), unclamped), both unscaled.  ia, ib:
+// internal pose indices.  flags[k] = status | nonzero << 1 for the host's pass plan.
+template <int PGO_UNIT_ = 0>
+__global__ __launch_bounds__(WG) void k_gate_eval(int n, const int32_t* __restrict__ ia, const int32_t* __restrict__ ib, const double* __restrict__ meas,
+                                                  const double* __restrict__ poses, const double* __restrict__ scale, GateRec* __restrict__ rec,
+                                                  int32_t* __restrict__ flags) {
+  const int k = blockIdx.x * WG + threadIdx.x;
+  if (k >= n) return;
+  const int a = ia[k], b = ib[k];
+  const double dx = meas[3 * (int64_t)k], dy = meas[3 * (int64_t)k + 1], dth = meas[3 * (int64_t)k + 2];
+  const double x1 = poses[3 * (int64_t)a], y1 = poses[3 * (int64_t)a + 1], t1 = poses[3 * (int64_t)a + 2];
+  const double x2 = poses[3 * (int64_t)b], y2 = poses[3 * (int64_t)b + 1], t2 = poses[3 * (int64_t)b + 2];
+  double s1, c1, s2, c2, sd, cd;
+  sincos(t1, &s1, &c1);
+  sincos(t2, &s2, &c2);
+  sincos(dth, &sd, &cd);
+  const double Dx = x2 - x1, Dy = y2 - y1;
+  const double pa = c1 * Dx + s1 * Dy, pb = -s1 * Dx + c1 * Dy;
+  const double ux = pa - dx, uy = pb - dy;
+  const double ex = cd * ux + sd * uy, ey = -sd * ux + cd * uy;
+  const double c21 = c1 * c2 + s1 * s2, s21 = c1 * s2 - s1 * c2;
+  const double sind = cd * s21 - sd * c21, cosd = cd * c21 + sd * s21;
+  const double et = asin(fmin(1.0, fmax(-1.0, sind)));
+  const double cm = c1 * cd - s1 * sd, sm = s1 * cd + c1 * sd;
+  const double g = cosd / sqrt(1.0 - sind * sind);
+  GateRec R;
+  double* J = R.J;
+  J[0] = -cm;  J[1] = -sm;  J[2] = cd * pb - sd * pa;   J[3] = cm;   J[4] = sm;   J[5] = 0.0;
+  J[6] = sm;   J[7] = -cm;  J[8] = -sd * pb - cd * pa;  J[9] = -sm;  J[10] = cm;  J[11] = 0.0;
+  J[12] = 0.0; J[13] = 0.0; J[14] = -g;                 J[15] = 0.0; J[16] = 0.0; J[17] = g;
+  R.r[0] = ex;
+  R.r[1] = ey;
+  R.r[2] = et;
+  R.ra = 3 * a;
+  R.rb = 3 * b;
+  bool finite = isfinite(ex) && isfinite(ey) && isfinite(et);
+  bool nz = false;
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int d = 0; d < 6; ++d) {
+      const double v = J[6 * c + d];
+      finite = finite && isfinite(v);
+      nz = nz || (scale[(d < 3 ? R.ra + d : R.rb + d - 3)] * v != 0.0);
+    }
+  R.status = finite ? 0 : 1;
+  R.nonzero = (finite && nz) ? 1 : 0;
+  rec[k] = R;
+  flags[k] = R.status | (R.nonzero << 1);
+}
+
+// One lane per candidate of a pass (record cand[j], columns 3 j .. 3 j + 2 of the panel x): the six rows of S X its
+// Jacobian touches, P = J (S X) symmetrised, the 3x3 algebra of gate.h, the result record out[cand[j]].  x == nullptr: the
+// candidates that took no columns (P = 0: both endpoints constant; status 1: every double NaN).  Fixed-order sums, no
+// atomics.  info6: n x 6 in the caller's candidate order, or nullptr = the identity.
+template <int PGO_UNIT_ = 0>
+__global__ void k_gate_reduce(int k, const int32_t* __restrict__ cand, const GateRec* __restrict__ rec, const double* __restrict__ x, int64_t ld,
+                              const double* __restrict__ scale, const double* __restrict__ info6, pgo_edge_gate_result* __restrict__ out) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= k) return;
+  const int q = cand[j];
+  const GateRec& g = rec[q];
+  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  pgo_edge_gate_result o;
+  o._pad = 0;
+  o.status = g.status;
+  if (g.status) {
+    for (int i = 0; i < 3; ++i) o.r[i] = nan;
+    for (int i = 0; i < 18; ++i) o.J[i] = nan;
+    for (int i = 0; i < 9; ++i) o.P[i] = nan;
+    o.chi2 = o.chi2_marginal = o.info_gain = nan;
+    out[q] = o;
+    return;
+  }
+  double P[9];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    double y[6];   // rows ra .. ra + 2, rb .. rb + 2 of column c of Sigma J'
+#pragma unroll
+    for (int d = 0; d < 6; ++d) {
+      const int64_t row = d < 3 ? g.ra + d : g.rb + d - 3;
+      y[d] = x ? scale[row] * x[(int64_t)(3 * j + c) * ld + row] : 0.0;
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      double s = 0.0;
+#pragma unroll
+      for (int d = 0; d < 6; ++d) s += g.J[6 * a + d] * y[d];
+      P[3 * a + c] = s;
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int c = a + 1; c < 3; ++c) P[3 * a + c] = P[3 * c + a] = 0.5 * (P[3 * a + c] + P[3 * c + a]);
+  double res[3] = {nan, nan, nan};
+  (void)gate_evaluate(g.r, P, info6 ? info6 + 6 * (int64_t)q : nullptr, res);   // (M not positive definite: NaNs, named by the host)
+  for (int i = 0; i < 3; ++i) o.r[i] = g.r[i];
+  for (int i = 0; i < 18; ++i) o.J[i] = g.J[i];
+  for (int i = 0; i < 9; ++i) o.P[i] = P[i];
+  o.chi2 = res[0];
+  o.chi2_marginal = res[1];
+  o.info_gain = res[2];
+  out[q] = o;
 }
 
 }  // namespace dev

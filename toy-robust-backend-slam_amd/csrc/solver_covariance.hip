@@ -1,7 +1,10 @@
 // Pose marginal covariances (ceres::Covariance with a constant parameter block): Sigma = (J'J)^-1 at the handle's current
-// poses, by PCG on 3 x (poses per pass) right-hand sides at once (covariance.hip.h).  The system is the undamped one of the LM
+// poses, by PCG on 3 x (poses per pass) right-hand sides at once (covariance.hip.h), and the loop-edge gate on the same
+// system (pgo_edge_gate: right-hand sides S J' of candidate edges, three columns each, P = J Sigma J' on the device).  The system is the undamped one of the LM
 // loop, A = S J'J S + I_fixed (k_prepare at radius = infinity), right-hand side S e_k, Sigma = S X.  The preconditioner is the
 // handle's own (one level + the coarse level where the handle has it), set up for D'D = 0 and applied column by column.
+#include <functional>
+
 #include "solver_handle.hip.h"
 #include "covariance.hip.h"
 
@@ -21,7 +24,7 @@ struct DevScratch {   // buffers of one call, freed on every return path
   int alloc(T** out, int64_t n) {
     void* q = nullptr;
     hipError_t e = hipMalloc(&q, (size_t)std::max<int64_t>(n, 1) * sizeof(T));
-    if (e != hipSuccess) return fail(PGO_ERR_NOMEM, std::string("pgo_pose_covariance: hipMalloc: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(PGO_ERR_NOMEM, std::string("covariance: hipMalloc: ") + hipGetErrorString(e));
     p.push_back(q);
     *out = (T*)q;
     return PGO_OK;
@@ -148,71 +151,85 @@ int setup_system(pgo_handle* h) {
   return st;
 }
 
-}  // namespace
+// the right-hand sides of one pass: unit vectors S e_rows[c] (pgo_pose_covariance), or with rec != nullptr the sparse
+// columns S J' of the candidates cand[0 .. m / 3) (pgo_edge_gate)
+struct PassRhs {
+  const int32_t* rows = nullptr;
+  const dev::GateRec* rec = nullptr;
+  const int32_t* cand = nullptr;
+};
 
-extern "C" {
-
-void pgo_covariance_options_default(pgo_covariance_options* o) {
-  if (!o) return;
-  memset(o, 0, sizeof *o);
-  o->rtol = 1e-10;
-  o->max_iters = 20000;
-  o->poses_per_pass = 8;
-  o->cross = 0;
-}
-
-int pgo_pose_covariance(pgo_t* h, int32_t n, const int32_t* poses, const pgo_covariance_options* opt_or_null, double* out,
-                        pgo_covariance_report* report) {
-  const double t0 = wall_s();
-  if (!h) return fail(PGO_ERR_INVALID_ARG, "pgo_pose_covariance: null handle");
-  if (n < 0 || (n > 0 && (!poses || !out))) return fail(PGO_ERR_INVALID_ARG, "pgo_pose_covariance: bad argument");
+// One call on the undamped system: the checks and the set-up both entry points share, the PCG panels, and the solve of a pass.
+struct Session {
+  pgo_handle* h;
+  std::string fn;             // the entry point, for messages
   pgo_covariance_options o;
-  if (opt_or_null) o = *opt_or_null;
-  else pgo_covariance_options_default(&o);
-  const long long kp = knob("cov_poses_per_pass");
-  if (kp >= 0) o.poses_per_pass = (int32_t)kp;
-  if (!(o.rtol > 0.0) || !std::isfinite(o.rtol) || o.max_iters < 1 || o.poses_per_pass < 1 || o.poses_per_pass > dev::COV_MAX_COLS / 3)
-    return fail(PGO_ERR_INVALID_ARG, "pgo_pose_covariance: rtol > 0, max_iters >= 1 and poses_per_pass in 1..16 required");
-  if ((h->comm && h->comm->world > 1) || h->co_multi) return fail(PGO_ERR_UNSUPPORTED, "pgo_pose_covariance: one rank only");
-  if (h->batch_mode) return fail(PGO_ERR_UNSUPPORTED, "pgo_pose_covariance: not on batched handles");
-  // information weighting: even the columns whose true residual reaches 1e-5 differ from a sparse direct inverse by ~1e-3 on
-  // INTEL (others stall at 2e-5) -- refused rather than returning blocks of that quality
-  if (h->info_mode) return fail(PGO_ERR_UNSUPPORTED, "pgo_pose_covariance: not available with info_weighting = 1");
-  if (!h->has_anchor())   // (opt.fixed_pose, or a pose made constant by pgo_set_active)
-    return fail(PGO_ERR_UNSUPPORTED, "pgo_pose_covariance: fixed_pose = -1 leaves the gauge free (J'J is singular)");
-  const int64_t N = h->S.n_poses;
-  for (int32_t k = 0; k < n; ++k)
-    if (poses[k] < 0 || poses[k] >= N)
-      return fail(PGO_ERR_INVALID_ARG, "pgo_pose_covariance: pose index " + std::to_string(poses[k]) + " (entry " + std::to_string(k) + ") out of range");
-  if (h->has_sw && !h->lin_valid)
-    return fail(PGO_ERR_INVALID_ARG, "pgo_pose_covariance: METHOD 2 needs the switches of a solve: call pgo_lm_begin or pgo_solve first");
-  if (report) memset(report, 0, sizeof *report);
-  if (n == 0) return PGO_OK;
-  HIPC(hipSetDevice(h->device));
-  auto internal = [&](int64_t i) -> int64_t { return h->perm.empty() ? i : (int64_t)h->perm[i]; };
-  auto caller = [&](int64_t k) -> int64_t {   // internal row -> caller's pose
+  int64_t N = 0, n3 = 0, ld = 0;
+  int g = 1, gs = 1, gp = 1;  // grids of the vector kernels, of k_spmm, and the larger of both
+  DevScratch buf;
+  double *X = nullptr, *R = nullptr, *Z = nullptr, *P = nullptr, *AP = nullptr, *part_a = nullptr, *part_b = nullptr;
+  dev::CovCol* cs = nullptr;
+  uint8_t* rmask = nullptr;
+  std::vector<dev::CovCol> hc;
+  std::vector<double> hpart;
+  std::unique_ptr<CoarseOn> coarse_on;
+  int passes = 0, it_max = 0;
+  int64_t it_total = 0;
+  double rel_max = 0.0;
+
+  Session(pgo_handle* hh, const char* name) : h(hh), fn(name) {}
+
+  // options and the cases that are refused
+  int check(const pgo_covariance_options* opt_or_null) {
+    if (opt_or_null) o = *opt_or_null;
+    else pgo_covariance_options_default(&o);
+    const long long kp = knob("cov_poses_per_pass");
+    if (kp >= 0) o.poses_per_pass = (int32_t)kp;
+    if (!(o.rtol > 0.0) || !std::isfinite(o.rtol) || o.max_iters < 1 || o.poses_per_pass < 1 || o.poses_per_pass > dev::COV_MAX_COLS / 3)
+      return fail(PGO_ERR_INVALID_ARG, fn + ": rtol > 0, max_iters >= 1 and poses_per_pass in 1..16 required");
+    if ((h->comm && h->comm->world > 1) || h->co_multi) return fail(PGO_ERR_UNSUPPORTED, fn + ": one rank only");
+    if (h->batch_mode) return fail(PGO_ERR_UNSUPPORTED, fn + ": not on batched handles");
+    // information weighting: even the columns whose true residual reaches 1e-5 differ from a sparse direct inverse by ~1e-3 on
+    // INTEL (others stall at 2e-5) -- refused rather than returning blocks of that quality
+    if (h->info_mode) return fail(PGO_ERR_UNSUPPORTED, fn + ": not available with info_weighting = 1");
+    if (!h->has_anchor())   // (opt.fixed_pose, or a pose made constant by pgo_set_active)
+      return fail(PGO_ERR_UNSUPPORTED, fn + ": fixed_pose = -1 leaves the gauge free (J'J is singular)");
+    N = h->S.n_poses;
+    return PGO_OK;
+  }
+  int need_switches() {
+    if (h->has_sw && !h->lin_valid)
+      return fail(PGO_ERR_INVALID_ARG, fn + ": METHOD 2 needs the switches of a solve: call pgo_lm_begin or pgo_solve first");
+    return PGO_OK;
+  }
+  int64_t internal(int64_t i) const { return h->perm.empty() ? i : (int64_t)h->perm[i]; }
+  int64_t caller(int64_t k) const {   // internal row -> caller's pose
     if (h->perm.empty()) return k;
     for (int64_t i = 0; i < N; ++i)
       if (h->perm[i] == k) return i;
     return k;
-  };
-  {   // a non-finite pose is named before anything is evaluated at it
-    std::vector<double> x((size_t)3 * N);
-    HIPC(hipMemcpyAsync(x.data(), h->poses, x.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    PGOC(h->sync());
-    for (int64_t k = 0; k < N; ++k)
-      if (!std::isfinite(x[3 * k]) || !std::isfinite(x[3 * k + 1]) || !std::isfinite(x[3 * k + 2]))
-        return fail(PGO_ERR_NUMERIC, "pgo_pose_covariance: pose " + std::to_string(caller(k)) + " is not finite");
   }
-  PGOC(coarse_for_covariance(h));
-  CoarseOn coarse_on(h);
-  PGOC(setup_system(h));
 
-  const int64_t n3 = 3 * N, ld = n3;
-  const int g = std::min(std::max(1, (int)((n3 + dev::WG - 1) / dev::WG)), 1024);     // vector kernels
-  const int gs = std::min(std::max(1, (int)((N + dev::WG - 1) / dev::WG)), 1024);     // k_spmm
-  const int gp = std::max(g, gs);
-  {   // every row of A needs a positive diagonal: a pose without edges has none
+  // finite poses, the coarse level, the undamped system and its preconditioner, a positive diagonal on every row
+  int open() {
+    HIPC(hipSetDevice(h->device));
+    {   // a non-finite pose is named before anything is evaluated at it
+      std::vector<double> x((size_t)3 * N);
+      HIPC(hipMemcpyAsync(x.data(), h->poses, x.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      PGOC(h->sync());
+      for (int64_t k = 0; k < N; ++k)
+        if (!std::isfinite(x[3 * k]) || !std::isfinite(x[3 * k + 1]) || !std::isfinite(x[3 * k + 2]))
+          return fail(PGO_ERR_NUMERIC, fn + ": pose " + std::to_string(caller(k)) + " is not finite");
+    }
+    PGOC(coarse_for_covariance(h));
+    coarse_on.reset(new CoarseOn(h));
+    PGOC(setup_system(h));
+    n3 = 3 * N;
+    ld = n3;
+    g = std::min(std::max(1, (int)((n3 + dev::WG - 1) / dev::WG)), 1024);
+    gs = std::min(std::max(1, (int)((N + dev::WG - 1) / dev::WG)), 1024);
+    gp = std::max(g, gs);
+    // every row of A needs a positive diagonal: a pose without edges has none
     DevScratch tmp;
     int32_t* bad = nullptr;
     PGOC(tmp.alloc(&bad, gs));
@@ -223,50 +240,53 @@ int pgo_pose_covariance(pgo_t* h, int32_t n, const int32_t* poses, const pgo_cov
     PGOC(h->sync());
     const int32_t first = *std::min_element(hb.begin(), hb.end());
     if (first < N)
-      return fail(PGO_ERR_NUMERIC, "pgo_pose_covariance: pose " + std::to_string(caller(first)) +
+      return fail(PGO_ERR_NUMERIC, fn + ": pose " + std::to_string(caller(first)) +
                                        " has a singular diagonal block in J'J (no edge constrains it, or a non-finite Jacobian)");
+    return PGO_OK;
   }
 
-  const int kpp = o.poses_per_pass;
-  const int mcap = 3 * std::min<int64_t>(kpp, n);
-  DevScratch buf;
-  double *X, *R, *Z, *P, *AP, *part_a, *part_b, *gath;
-  dev::CovCol* cs;
-  int32_t *rows, *rows_out;
-  const int n_out_max = o.cross ? 3 * n : mcap;
-  PGOC(buf.alloc(&X, mcap * ld));
-  PGOC(buf.alloc(&R, mcap * ld));
-  PGOC(buf.alloc(&Z, mcap * ld));
-  PGOC(buf.alloc(&P, mcap * ld));
-  PGOC(buf.alloc(&AP, mcap * ld));
-  PGOC(buf.alloc(&part_a, (int64_t)mcap * gp));
-  PGOC(buf.alloc(&part_b, (int64_t)mcap * gp));
-  PGOC(buf.alloc(&cs, mcap));
-  PGOC(buf.alloc(&rows, mcap));
-  PGOC(buf.alloc(&rows_out, n_out_max));
-  PGOC(buf.alloc(&gath, (int64_t)mcap * n_out_max));
-  uint8_t* rmask = nullptr;
-  PGOC(buf.alloc(&rmask, mcap));
-  if (o.cross) {
-    std::vector<int32_t> ro((size_t)3 * n);
-    for (int32_t j = 0; j < n; ++j)
-      for (int a = 0; a < 3; ++a) ro[3 * j + a] = (int32_t)(3 * internal(poses[j]) + a);
-    HIPC(hipMemcpyAsync(rows_out, ro.data(), ro.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    PGOC(h->sync());
+  // the panels of a pass of up to mcap columns
+  int alloc(int mcap) {
+    PGOC(buf.alloc(&X, mcap * ld));
+    PGOC(buf.alloc(&R, mcap * ld));
+    PGOC(buf.alloc(&Z, mcap * ld));
+    PGOC(buf.alloc(&P, mcap * ld));
+    PGOC(buf.alloc(&AP, mcap * ld));
+    PGOC(buf.alloc(&part_a, (int64_t)mcap * gp));
+    PGOC(buf.alloc(&part_b, (int64_t)mcap * gp));
+    PGOC(buf.alloc(&cs, mcap));
+    PGOC(buf.alloc(&rmask, mcap));
+    hc.resize((size_t)mcap);
+    return PGO_OK;
   }
-  const int every = std::max(1, h->opt.pcg_check_every);
-  std::vector<dev::CovCol> hc((size_t)mcap);
-  std::vector<double> hg, hpart;
-  int passes = 0, it_max = 0;
-  int64_t it_total = 0;
-  double rel_max = 0.0;
-  for (int32_t j0 = 0; j0 < n; j0 += kpp) {
-    const int k = (int)std::min<int64_t>(kpp, n - j0), m = 3 * k;
-    std::vector<int32_t> rr((size_t)m);
-    for (int j = 0; j < k; ++j)
-      for (int a = 0; a < 3; ++a) rr[3 * j + a] = (int32_t)(3 * internal(poses[j0 + j]) + a);
-    HIPC(hipMemcpyAsync(rows, rr.data(), rr.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    if (!o.cross) HIPC(hipMemcpyAsync(rows_out, rr.data(), rr.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+
+  int launch_rhs(int m, const PassRhs& B) {
+    if (B.rec)
+      hipLaunchKernelGGL(dev::k_cov_rhs<dev::RhsSparse>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, dev::RhsSparse{B.rec, B.cand, h->scale}, X, R, P, part_a);
+    else
+      hipLaunchKernelGGL(dev::k_cov_rhs<dev::RhsUnit>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, dev::RhsUnit{B.rows, h->scale}, X, R, P, part_a);
+    return h->check_launch("k_cov_rhs");
+  }
+  int launch_resid(int m, const PassRhs& B) {
+    if (B.rec)
+      hipLaunchKernelGGL(dev::k_cov_resid<dev::RhsSparse>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, dev::RhsSparse{B.rec, B.cand, h->scale}, (const double*)AP, part_b);
+    else
+      hipLaunchKernelGGL(dev::k_cov_resid<dev::RhsUnit>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, dev::RhsUnit{B.rows, h->scale}, (const double*)AP, part_b);
+    return h->check_launch("k_cov_resid");
+  }
+  void launch_replace(int m, const PassRhs& B) {
+    if (B.rec)
+      hipLaunchKernelGGL(dev::k_cov_replace<dev::RhsSparse>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, dev::RhsSparse{B.rec, B.cand, h->scale}, (const double*)AP, R,
+                         (const uint8_t*)rmask);
+    else
+      hipLaunchKernelGGL(dev::k_cov_replace<dev::RhsUnit>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, dev::RhsUnit{B.rows, h->scale}, (const double*)AP, R,
+                         (const uint8_t*)rmask);
+  }
+
+  // A X = B for the m columns of one pass (every one a non-zero right-hand side): start, PCG in chunks, the true residual,
+  // residual replacement and restart.  who(c) names column c's pose or candidate in messages.  X holds the solution.
+  int pass(int m, const PassRhs& B, const std::function<std::string(int)>& who) {
+    const int every = std::max(1, h->opt.pcg_check_every);
     // start: X = 0, R = B, Z = M^-1 R, P = Z
     std::vector<uint8_t> hdone((size_t)m, 0);   // columns known stopped at the latest host check: no preconditioner apply
     auto precond_open = [&]() -> int {
@@ -274,8 +294,7 @@ int pgo_pose_covariance(pgo_t* h, int32_t n, const int32_t* poses, const pgo_cov
         if (!hdone[c]) PGOC(precond_column(h, R + c * ld, Z + c * ld));
       return PGO_OK;
     };
-    hipLaunchKernelGGL(dev::k_cov_rhs<>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, (const int32_t*)rows, (const double*)h->scale, X, R, P, part_a);
-    PGOC(h->check_launch("k_cov_rhs"));
+    PGOC(launch_rhs(m, B));
     PGOC(precond_open());
     // (k_cov_dot skips done columns: cs must read "running" before the start kernel has written it)
     HIPC(hipMemsetAsync(cs, 0, (size_t)m * sizeof(dev::CovCol), h->stream));
@@ -308,8 +327,8 @@ int pgo_pose_covariance(pgo_t* h, int32_t n, const int32_t* poses, const pgo_cov
         bool all = true;
         for (int c = 0; c < m; ++c) {
           if (hc[c].done >= 2)
-            return fail(PGO_ERR_NUMERIC, "pgo_pose_covariance: PCG breakdown on column " + std::to_string(c % 3) + " of pose " +
-                                             std::to_string(poses[j0 + c / 3]) + (hc[c].done == 2 ? " (p'Ap <= 0)" : " (r'z <= 0)"));
+            return fail(PGO_ERR_NUMERIC, fn + ": PCG breakdown on column " + std::to_string(c % 3) + " of " + who(c) +
+                                             (hc[c].done == 2 ? " (p'Ap <= 0)" : " (r'z <= 0)"));
           hdone[c] = hc[c].done == 1;
           all = all && hdone[c];
         }
@@ -317,19 +336,16 @@ int pgo_pose_covariance(pgo_t* h, int32_t n, const int32_t* poses, const pgo_cov
         if (it >= o.max_iters) {
           for (int c = 0; c < m; ++c)
             if (!hc[c].done)
-              return fail(PGO_ERR_NUMERIC, "pgo_pose_covariance: PCG reached max_iters = " + std::to_string(o.max_iters) + " on pose " +
-                                               std::to_string(poses[j0 + c / 3]) + " (relative residual " +
-                                               std::to_string(std::sqrt(hc[c].rr / hc[c].bb)) + ")");
+              return fail(PGO_ERR_NUMERIC, fn + ": PCG reached max_iters = " + std::to_string(o.max_iters) + " on " + who(c) +
+                                               " (relative residual " + std::to_string(std::sqrt(hc[c].rr / hc[c].bb)) + ")");
         }
       }
-      // the TRUE residual |S e - A X| / |S e| of every column (one more product): the recurrence drifts from it on
+      // the TRUE residual |b - A x| / |b| of every column (one more product): the recurrence drifts from it on
       // ill-conditioned systems.  Columns above rtol restart from X with the true residual (residual replacement) as long
       // as that lowers it by 10 % or more.  Once it no longer does, the column has reached what double precision allows for this
       // system: accepted when that floor is <= COV_RES_FLOOR_MAX (reported in max_rel_residual), else PGO_ERR_NUMERIC.
       PGOC(spmm(h, m, ld, X, AP, part_a, gs));
-      hipLaunchKernelGGL(dev::k_cov_resid<>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, (const int32_t*)rows, (const double*)h->scale,
-                         (const double*)AP, part_b);
-      PGOC(h->check_launch("k_cov_resid"));
+      PGOC(launch_resid(m, B));
       hpart.resize((size_t)m * g);
       HIPC(hipMemcpyAsync(hpart.data(), part_b, hpart.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
       PGOC(h->sync());
@@ -343,9 +359,8 @@ int pgo_pose_covariance(pgo_t* h, int32_t n, const int32_t* poses, const pgo_cov
           if (!(res[c] <= 0.9 * res_prev[c]) || it >= o.max_iters) {   // no further gain from a replacement
             if (res[c] <= COV_RES_FLOOR_MAX) continue;
             char msg[200];
-            snprintf(msg, sizeof msg, "pgo_pose_covariance: the true residual of pose %d stalls at %.3e relative (rtol %.1e)",
-                     (int)poses[j0 + c / 3], res[c], o.rtol);
-            return fail(PGO_ERR_NUMERIC, msg);
+            snprintf(msg, sizeof msg, ": the true residual of %s stalls at %.3e relative (rtol %.1e)", who(c).c_str(), res[c], o.rtol);
+            return fail(PGO_ERR_NUMERIC, fn + msg);
           }
           mask[c] = 1;
           hdone[c] = 0;
@@ -355,8 +370,7 @@ int pgo_pose_covariance(pgo_t* h, int32_t n, const int32_t* poses, const pgo_cov
       if (!any) break;
       res_prev = res;
       HIPC(hipMemcpyAsync(rmask, mask.data(), (size_t)m, hipMemcpyHostToDevice, h->stream));
-      hipLaunchKernelGGL(dev::k_cov_replace<>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, (const int32_t*)rows, (const double*)h->scale,
-                         (const double*)AP, R, (const uint8_t*)rmask);
+      launch_replace(m, B);
       hipLaunchKernelGGL(dev::k_cov_reopen<>, dim3(1), dim3(64), 0, h->stream, cs, (const uint8_t*)rmask, m);
       PGOC(h->check_launch("k_cov_replace"));
       PGOC(precond_open());
@@ -371,8 +385,81 @@ int pgo_pose_covariance(pgo_t* h, int32_t n, const int32_t* poses, const pgo_cov
       it_total += hc[c].iters;
       rel_max = std::max(rel_max, res[c]);
     }
+    ++passes;
+    return PGO_OK;
+  }
+
+  void fill(pgo_covariance_report* report, int32_t columns, double t0) const {
+    if (!report) return;
+    report->columns = columns;
+    report->passes = passes;
+    report->pcg_iters_max = it_max;
+    report->pcg_iters_total = (int32_t)std::min<int64_t>(it_total, INT32_MAX);
+    report->max_rel_residual = rel_max;
+    report->seconds = wall_s() - t0;
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+void pgo_covariance_options_default(pgo_covariance_options* o) {
+  if (!o) return;
+  memset(o, 0, sizeof *o);
+  o->rtol = 1e-10;
+  o->max_iters = 20000;
+  o->poses_per_pass = 8;
+  o->cross = 0;
+}
+
+int pgo_pose_covariance(pgo_t* h, int32_t n, const int32_t* poses, const pgo_covariance_options* opt_or_null, double* out,
+                        pgo_covariance_report* report) {
+  const double t0 = wall_s();
+  if (!h) return fail(PGO_ERR_INVALID_ARG, "pgo_pose_covariance: null handle");
+  if (n < 0 || (n > 0 && (!poses || !out))) return fail(PGO_ERR_INVALID_ARG, "pgo_pose_covariance: bad argument");
+  Session S(h, "pgo_pose_covariance");
+  PGOC(S.check(opt_or_null));
+  const pgo_covariance_options& o = S.o;
+  const int64_t N = S.N;
+  for (int32_t k = 0; k < n; ++k)
+    if (poses[k] < 0 || poses[k] >= N)
+      return fail(PGO_ERR_INVALID_ARG, "pgo_pose_covariance: pose index " + std::to_string(poses[k]) + " (entry " + std::to_string(k) + ") out of range");
+  PGOC(S.need_switches());
+  if (report) memset(report, 0, sizeof *report);
+  if (n == 0) return PGO_OK;
+  PGOC(S.open());
+
+  const int64_t ld = S.ld;
+  const int kpp = o.poses_per_pass;
+  const int mcap = 3 * std::min<int64_t>(kpp, n);
+  PGOC(S.alloc(mcap));
+  double* gath;
+  int32_t *rows, *rows_out;
+  const int n_out_max = o.cross ? 3 * n : mcap;
+  PGOC(S.buf.alloc(&rows, mcap));
+  PGOC(S.buf.alloc(&rows_out, n_out_max));
+  PGOC(S.buf.alloc(&gath, (int64_t)mcap * n_out_max));
+  if (o.cross) {
+    std::vector<int32_t> ro((size_t)3 * n);
+    for (int32_t j = 0; j < n; ++j)
+      for (int a = 0; a < 3; ++a) ro[3 * j + a] = (int32_t)(3 * S.internal(poses[j]) + a);
+    HIPC(hipMemcpyAsync(rows_out, ro.data(), ro.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    PGOC(h->sync());
+  }
+  std::vector<double> hg;
+  for (int32_t j0 = 0; j0 < n; j0 += kpp) {
+    const int k = (int)std::min<int64_t>(kpp, n - j0), m = 3 * k;
+    std::vector<int32_t> rr((size_t)m);
+    for (int j = 0; j < k; ++j)
+      for (int a = 0; a < 3; ++a) rr[3 * j + a] = (int32_t)(3 * S.internal(poses[j0 + j]) + a);
+    HIPC(hipMemcpyAsync(rows, rr.data(), rr.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    if (!o.cross) HIPC(hipMemcpyAsync(rows_out, rr.data(), rr.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    PassRhs B;
+    B.rows = rows;
+    PGOC(S.pass(m, B, [&](int c) { return "pose " + std::to_string(poses[j0 + c / 3]); }));
     const int n_out = o.cross ? 3 * n : m;
-    hipLaunchKernelGGL(dev::k_cov_gather<>, dim3((unsigned)(((int64_t)m * n_out + 255) / 256)), dim3(256), 0, h->stream, m, ld, (const double*)X,
+    hipLaunchKernelGGL(dev::k_cov_gather<>, dim3((unsigned)(((int64_t)m * n_out + 255) / 256)), dim3(256), 0, h->stream, m, ld, (const double*)S.X,
                        (const double*)h->scale, (const int32_t*)rows_out, n_out, gath);
     PGOC(h->check_launch("k_cov_gather"));
     hg.resize((size_t)m * n_out);
@@ -388,7 +475,6 @@ int pgo_pose_covariance(pgo_t* h, int32_t n, const int32_t* poses, const pgo_cov
         for (int a = 0; a < 3; ++a)
           for (int b = 0; b < 3; ++b) out[9 * (int64_t)(j0 + jc) + 3 * a + b] = hg[(size_t)(3 * jc + b) * n_out + 3 * jc + a];
     }
-    ++passes;
   }
   // symmetric blocks: 1/2 (Sigma_ab + Sigma_ba')
   if (o.cross) {
@@ -405,14 +491,102 @@ int pgo_pose_covariance(pgo_t* h, int32_t n, const int32_t* poses, const pgo_cov
         for (int b = a + 1; b < 3; ++b) B[3 * a + b] = B[3 * b + a] = 0.5 * (B[3 * a + b] + B[3 * b + a]);
     }
   }
-  if (report) {
-    report->columns = 3 * n;
-    report->passes = passes;
-    report->pcg_iters_max = it_max;
-    report->pcg_iters_total = (int32_t)std::min<int64_t>(it_total, INT32_MAX);
-    report->max_rel_residual = rel_max;
-    report->seconds = wall_s() - t0;
+  S.fill(report, 3 * n, t0);
+  return PGO_OK;
+}
+
+int pgo_gate_evaluate(const double r[3], const double P[9], const double* info6_or_null, double out[3]) {
+  if (!r || !P || !out) return fail(PGO_ERR_INVALID_ARG, "pgo_gate_evaluate: null");
+  const int st = pgo::gate_evaluate(r, P, info6_or_null, out);
+  if (st == pgo::GATE_OMEGA_NOT_PD) return fail(PGO_ERR_INVALID_ARG, "pgo_gate_evaluate: the information matrix is not finite and positive definite");
+  if (st == pgo::GATE_M_NOT_PD) return fail(PGO_ERR_NUMERIC, "pgo_gate_evaluate: I + L'PL is not positive definite (P is indefinite or not finite)");
+  return PGO_OK;
+}
+
+int pgo_edge_gate(pgo_t* h, int32_t n, const int32_t* ia, const int32_t* ib, const double* meas_xyt, const double* info6_or_null,
+                  const pgo_covariance_options* opt_or_null, pgo_edge_gate_result* out, pgo_covariance_report* report) {
+  const double t0 = wall_s();
+  if (!h) return fail(PGO_ERR_INVALID_ARG, "pgo_edge_gate: null handle");
+  if (n < 0 || (n > 0 && (!ia || !ib || !meas_xyt || !out))) return fail(PGO_ERR_INVALID_ARG, "pgo_edge_gate: bad argument");
+  Session S(h, "pgo_edge_gate");
+  PGOC(S.check(opt_or_null));
+  const int64_t N = S.N;
+  for (int32_t k = 0; k < n; ++k) {
+    if (ia[k] < 0 || ia[k] >= N || ib[k] < 0 || ib[k] >= N)
+      return fail(PGO_ERR_INVALID_ARG, "pgo_edge_gate: candidate " + std::to_string(k) + " has a pose index out of range");
+    if (ia[k] == ib[k]) return fail(PGO_ERR_INVALID_ARG, "pgo_edge_gate: candidate " + std::to_string(k) + " joins pose " + std::to_string(ia[k]) + " to itself");
+    if (info6_or_null) {
+      const double* w = info6_or_null + 6 * (int64_t)k;
+      double l[6];
+      bool ok = true;
+      for (int c = 0; c < 6; ++c) ok = ok && std::isfinite(w[c]);
+      if (!ok || !pgo::gate_chol3(w, l))
+        return fail(PGO_ERR_INVALID_ARG, "pgo_edge_gate: the information matrix of candidate " + std::to_string(k) + " is not finite and positive definite");
+    }
   }
+  PGOC(S.need_switches());
+  if (report) memset(report, 0, sizeof *report);
+  if (n == 0) return PGO_OK;
+  PGOC(S.open());
+
+  // the candidates on the device, internal pose numbering; r, J and the plan flags of every one
+  int32_t *d_ia, *d_ib, *d_flags, *d_cand;
+  double *d_meas, *d_info = nullptr;
+  dev::GateRec* rec;
+  pgo_edge_gate_result* d_out;
+  PGOC(S.buf.alloc(&d_ia, n));
+  PGOC(S.buf.alloc(&d_ib, n));
+  PGOC(S.buf.alloc(&d_flags, n));
+  PGOC(S.buf.alloc(&d_cand, n));
+  PGOC(S.buf.alloc(&d_meas, 3 * (int64_t)n));
+  if (info6_or_null) PGOC(S.buf.alloc(&d_info, 6 * (int64_t)n));
+  PGOC(S.buf.alloc(&rec, n));
+  PGOC(S.buf.alloc(&d_out, n));
+  std::vector<int32_t> ha((size_t)n), hb((size_t)n), flags((size_t)n);
+  for (int32_t k = 0; k < n; ++k) {
+    ha[k] = (int32_t)S.internal(ia[k]);
+    hb[k] = (int32_t)S.internal(ib[k]);
+  }
+  HIPC(hipMemcpyAsync(d_ia, ha.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  HIPC(hipMemcpyAsync(d_ib, hb.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  HIPC(hipMemcpyAsync(d_meas, meas_xyt, (size_t)3 * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (d_info) HIPC(hipMemcpyAsync(d_info, info6_or_null, (size_t)6 * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(dev::k_gate_eval<>, dim3((unsigned)((n + dev::WG - 1) / dev::WG)), dim3(dev::WG), 0, h->stream, (int)n, (const int32_t*)d_ia,
+                     (const int32_t*)d_ib, (const double*)d_meas, (const double*)h->poses, (const double*)h->scale, rec, d_flags);
+  PGOC(h->check_launch("k_gate_eval"));
+  HIPC(hipMemcpyAsync(flags.data(), d_flags, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  PGOC(h->sync());
+  // the pass plan: candidates with status 1, and those whose right-hand sides are zero (both endpoints constant), take no columns
+  std::vector<int32_t> plan, rest;
+  for (int32_t k = 0; k < n; ++k) (flags[k] == 2 ? plan : rest).push_back(k);
+  const int32_t n_solve = (int32_t)plan.size();
+  plan.insert(plan.end(), rest.begin(), rest.end());
+  HIPC(hipMemcpyAsync(d_cand, plan.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  PGOC(h->sync());
+  const int kpp = S.o.poses_per_pass;
+  if (n_solve > 0) PGOC(S.alloc(3 * std::min<int32_t>(kpp, n_solve)));
+  for (int32_t j0 = 0; j0 < n_solve; j0 += kpp) {
+    const int k = (int)std::min<int32_t>(kpp, n_solve - j0), m = 3 * k;
+    PassRhs B;
+    B.rec = rec;
+    B.cand = d_cand + j0;
+    PGOC(S.pass(m, B, [&](int c) { return "candidate " + std::to_string(plan[j0 + c / 3]); }));
+    hipLaunchKernelGGL(dev::k_gate_reduce<>, dim3(1), dim3(64), 0, h->stream, k, (const int32_t*)(d_cand + j0), (const dev::GateRec*)rec, (const double*)S.X,
+                       S.ld, (const double*)h->scale, (const double*)d_info, d_out);
+    PGOC(h->check_launch("k_gate_reduce"));
+  }
+  if (n > n_solve) {
+    const int k = n - n_solve;
+    hipLaunchKernelGGL(dev::k_gate_reduce<>, dim3((unsigned)((k + 63) / 64)), dim3(64), 0, h->stream, k, (const int32_t*)(d_cand + n_solve),
+                       (const dev::GateRec*)rec, (const double*)nullptr, S.ld, (const double*)h->scale, (const double*)d_info, d_out);
+    PGOC(h->check_launch("k_gate_reduce"));
+  }
+  HIPC(hipMemcpyAsync(out, d_out, (size_t)n * sizeof(pgo_edge_gate_result), hipMemcpyDeviceToHost, h->stream));
+  PGOC(h->sync());
+  for (int32_t k = 0; k < n; ++k)
+    if (out[k].status == 0 && !(std::isfinite(out[k].chi2_marginal) && std::isfinite(out[k].info_gain)))
+      return fail(PGO_ERR_NUMERIC, "pgo_edge_gate: I + L'PL of candidate " + std::to_string(k) + " is not positive definite");
+  S.fill(report, 3 * n_solve, t0);
   return PGO_OK;
 }
 
