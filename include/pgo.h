@@ -541,6 +541,77 @@ int pgo_edge_gate(pgo_t* h, int32_t n, const int32_t* ia, const int32_t* ib, con
                   const double* info6_or_null /* n x 6 */, const pgo_covariance_options* opt_or_null,
                   pgo_edge_gate_result* out /* n */, pgo_covariance_report* report_or_null);                /* [gpu]  */
 
+/* ---------------------------------------------------------- window solves
+ * The layer managers' most frequent ceres::Solve: the local window around a newly added loop edge
+ * (SimpleLayerManagerV2::optimize_local_window, src/simple_layer_manager.cpp:500-565, window_size 20 at :222,243;
+ * SimpleLayerManager::optimize_layer_local, src/layer_manager.cpp:137-179) -- 42 poses, 41 edges, one constant pose, 1-2 LM
+ * iterations, exact linear solve.  pgo_window_solve solves MANY such windows of the handle's graph in ONE kernel launch, one
+ * workgroup per window, the whole LM loop on the device (evaluate, assemble, dense Cholesky, candidate, accept / reject,
+ * termination tests); no host round trip inside the call beyond the final copy-out.
+ * - Window w is the problem whose parameter blocks are the poses pose_idx[pose_ptr[w] .. pose_ptr[w+1]) and whose residual blocks
+ *   are the handle's edges edge_idx[edge_ptr[w] .. edge_ptr[w+1]) (pose_ptr[0] = edge_ptr[0] = 0).  Pose indices: the caller's
+ *   numbering, distinct within a window.  Edge indices: the caller's edge order (an edge may be listed twice: two residual
+ *   blocks); both endpoints of every edge must be in the window's pose list.  anchor[w] is a pose of the list: the one constant
+ *   block.  A listed pose without a listed edge is not in the problem (Ceres would not have it) and comes back unchanged.
+ *   The handle's own active set (pgo_set_active), opt.fixed_pose and pose_constant play no part: the lists ARE the problem,
+ *   as pgo_edge_gate's candidates need not be edges of the active problem.
+ * - Objective and policy are the handle's: opt.method 0 or 1 (DCS on the edges whose kind says so), phi, the loss classes
+ *   (pgo_set_losses; Huber(huber_delta) by default), jacobi_scaling and every LM constant of pgo_options; max_iters is the
+ *   call's own, 1..PGO_WINDOW_MAX_ITERS.  The policy is that of pgo_batch_solve / pgo_solve: Jacobi scales from the initial point
+ *   only; D'D = clip(diag, min_lm_diagonal, max_lm_diagonal) / radius; model decrease without the D term; the parameter and
+ *   function tolerance tests on the candidate before the accept test; the same radius, decrease-factor and five-invalid-steps
+ *   rules; a non-finite evaluation at the initial or at an accepted point is PGO_TERM_FAILURE.  The linear system
+ *   (S J'J S + D'D) y = S J'r is solved by a dense Cholesky (what SPARSE_NORMAL_CHOLESKY is at this size): a lost pivot, a
+ *   non-finite value or a non-positive model decrease is an invalid step.
+ * - Every window reads the handle's CURRENT poses as they are at the call; windows are independent.  poses_out (or NULL) gets
+ *   each window's final poses in list order.  commit != 0: they are also written into the handle, as pgo_set_poses would write
+ *   them (a solve begun with pgo_lm_begin becomes stale); the pose lists of the call must then be pairwise disjoint (checked on
+ *   the host before any launch).  commit == 0: the handle is left exactly as it was -- a following pgo_lm_step gives bitwise
+ *   the records and poses it gives without the call.
+ * - records (or NULL): (max_iters + 1) rows per window as the batch writes them -- row 0 the initial point, pcg_iters 0,
+ *   seconds 0 --, results[w].n_records of them filled, the rest zero.
+ * - No floating-point atomics; every sum runs in the order of the window's own edge and pose lists, not in the handle's internal
+ *   numbering: two calls are bitwise equal, a handle with pose_ordering 1 gives bitwise what one with 0 gives, a batch gives
+ *   bitwise what a solo handle with the same poses gives.
+ * - A window that fails (PGO_TERM_FAILURE) is not a call failure: its poses come back unchanged, the others are unaffected.
+ * - Errors: PGO_ERR_UNSUPPORTED for METHOD 2, info_weighting = 1, a communicator or PGO_FORCE_COLLECTIVES=1, a window of more
+ *   than PGO_WINDOW_MAX_POSES poses or PGO_WINDOW_MAX_EDGES edges (pgo_last_error names the window; such windows stay on
+ *   pgo_set_active); PGO_ERR_INVALID_ARG for a null pointer, an index out of range, a duplicate pose in a list, an edge endpoint
+ *   or an anchor not in the list, max_iters out of range, overlapping lists under commit.  n_windows == 0 is PGO_OK.  Nothing
+ *   changes on error.
+ * pgo_batch_window_solve: the same on the problems of a batch; window w belongs to problem[w] and its indices are that
+ * problem's own.                                                                                                         */
+#define PGO_WINDOW_MAX_POSES 64    /* 192 unknowns: the packed triangle and the vectors take 156,032 of a workgroup's 163,840 LDS bytes */
+#define PGO_WINDOW_MAX_EDGES 256   /* one lane per edge */
+#define PGO_WINDOW_MAX_ITERS 32
+typedef struct pgo_window_result {
+  int32_t termination;        /* pgo_termination */
+  int32_t iterations, successful_steps, n_records;
+  double  initial_cost, final_cost;
+} pgo_window_result;
+/* The reference's window rule (src/simple_layer_manager.cpp:510-555), pure logic.  active = the union over the focus edges of
+ * [a - radius, a + radius] and [b - radius, b + radius], clipped to [0, n_poses - 1]; edges = every PGO_EDGE_ODOMETRY edge
+ * with both ends active, in graph order, followed by the focus edges with a != b in the order given, an edge listed once;
+ * poses = the endpoints of those edges, ascending; anchor = pose 0 if it is among them, else the smallest (-1: no pose).  The
+ * caller passes radius = max(1, window_size / 2).  A cap that is too small: the counts are still returned, the lists are not
+ * written, PGO_ERR_INVALID_ARG.                                                                                           */
+int pgo_window_plan(int32_t n_poses, int32_t n_edges, const int32_t* ia, const int32_t* ib, const uint8_t* kind,
+                    int32_t n_focus, const int32_t* focus_edges, int32_t radius,
+                    int32_t pose_cap, int32_t* pose_idx_out, int32_t* n_poses_out,
+                    int32_t edge_cap, int32_t* edge_idx_out, int32_t* n_edges_out, int32_t* anchor_out);          /* [host] */
+int pgo_window_solve(pgo_t* h, int32_t n_windows,
+                     const int32_t* pose_ptr /* n_windows + 1 */, const int32_t* pose_idx,
+                     const int32_t* edge_ptr /* n_windows + 1 */, const int32_t* edge_idx,
+                     const int32_t* anchor   /* n_windows */,
+                     int32_t max_iters, int32_t commit,
+                     double* poses_out /* pose_ptr[n_windows] x 3, or NULL */,
+                     pgo_window_result* results /* n_windows */,
+                     pgo_iter_record* records_or_null /* n_windows x (max_iters + 1) */);                           /* [gpu] */
+int pgo_batch_window_solve(pgo_batch_t* b, int32_t n_windows, const int32_t* problem /* n_windows */,
+                           const int32_t* pose_ptr, const int32_t* pose_idx, const int32_t* edge_ptr, const int32_t* edge_idx,
+                           const int32_t* anchor, int32_t max_iters, int32_t commit, double* poses_out,
+                           pgo_window_result* results, pgo_iter_record* records_or_null);                           /* [gpu] */
+
 /* ------------------------------------------------ kernel-level entry points
  * Used by the parity tests and by bench.py's roofline leg: each launches exactly
  * one kind of kernel `reps` times on the handle's stream, brackets the launches

@@ -22,7 +22,8 @@ from . import _build
 
 __all__ = ["PgoError", "Options", "Summary", "IterRecord", "ReadG2O", "Graph", "Solver", "Batch", "Comm", "lib", "build",
            "HandleInfo", "synth_manhattan", "solve_batch", "shard_plan", "shard_halo", "pose_order", "set_knob", "KernelStats", "EXPORTS", "TERMINATION",
-           "CovarianceOptions", "CovarianceReport", "Loss", "LOSS_TYPES", "active_plan", "EdgeGateResult", "gate_evaluate"]
+           "CovarianceOptions", "CovarianceReport", "Loss", "LOSS_TYPES", "active_plan", "EdgeGateResult", "gate_evaluate",
+           "window_plan", "WindowResult", "WINDOW_MAX_POSES", "WINDOW_MAX_EDGES", "WINDOW_MAX_ITERS"]
 
 EDGE_ODOMETRY, EDGE_CLOSURE, EDGE_BOGUS = 0, 1, 2
 TERMINATION = {1: "CONVERGENCE_FTOL", 2: "CONVERGENCE_GTOL", 3: "CONVERGENCE_PTOL", 4: "NO_CONVERGENCE",
@@ -49,7 +50,9 @@ EXPORTS = [
     "pgo_loss_evaluate", "pgo_set_losses", "pgo_batch_set_losses",
     "pgo_set_active", "pgo_batch_set_active", "pgo_active_plan",
     "pgo_gate_evaluate", "pgo_edge_gate",
+    "pgo_window_plan", "pgo_window_solve", "pgo_batch_window_solve",
 ]
+WINDOW_MAX_POSES, WINDOW_MAX_EDGES, WINDOW_MAX_ITERS = 64, 256, 32   # PGO_WINDOW_MAX_* (include/pgo.h)
 LOSS_TYPES = {"trivial": 0, "huber": 1, "softlone": 2, "cauchy": 3, "arctan": 4, "tukey": 5}   # pgo_loss_type
 
 
@@ -186,6 +189,17 @@ class EdgeGateResult(C.Structure):
                 ("chi2_marginal", C.c_double), ("info_gain", C.c_double), ("status", C.c_int32), ("_pad", C.c_int32)]
 
 
+class WindowResult(C.Structure):
+    """mirror of pgo_window_result: one window of Solver.window_solve / Batch.window_solve"""
+    _fields_ = [("termination", C.c_int32), ("iterations", C.c_int32), ("successful_steps", C.c_int32),
+                ("n_records", C.c_int32), ("initial_cost", C.c_double), ("final_cost", C.c_double)]
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_}
+        d["termination_name"] = TERMINATION.get(self.termination, "?")
+        return d
+
+
 _LIB = None
 
 
@@ -298,6 +312,11 @@ def lib():
     L.pgo_gate_evaluate.argtypes = [dp, dp, dp, dp]
     L.pgo_edge_gate.argtypes = [vp, C.c_int32, ip, ip, dp, dp, C.POINTER(CovarianceOptions), C.POINTER(EdgeGateResult),
                                 C.POINTER(CovarianceReport)]
+    L.pgo_window_plan.argtypes = [C.c_int32, C.c_int32, ip, ip, bp, C.c_int32, ip, C.c_int32, C.c_int32, ip, ip, C.c_int32, ip, ip, ip]
+    L.pgo_window_solve.argtypes = [vp, C.c_int32, ip, ip, ip, ip, ip, C.c_int32, C.c_int32, dp, C.POINTER(WindowResult),
+                                   C.POINTER(IterRecord)]
+    L.pgo_batch_window_solve.argtypes = [vp, C.c_int32, ip, ip, ip, ip, ip, ip, C.c_int32, C.c_int32, dp, C.POINTER(WindowResult),
+                                         C.POINTER(IterRecord)]
     _LIB = L
     return L
 
@@ -480,6 +499,63 @@ def active_plan(n_poses, ia, ib, edge_active=None, pose_constant=None, fixed_pos
     return const, na.value, nf.value
 
 
+def window_plan(n_poses, ia, ib, kind, focus_edges, radius, pose_cap=None, edge_cap=None):
+    """pgo_window_plan (host only), the layer managers' window rule: the poses within `radius` of an end of a focus edge, the
+    odometry edges among them, then the focus edges.  Returns (pose_idx, edge_idx, anchor) -- one window of
+    Solver.window_solve.  pose_cap / edge_cap (default: no limit): a window above a cap raises PgoError, whose n_poses /
+    n_edges attributes carry the counts."""
+    ia = np.ascontiguousarray(ia, np.int32)
+    ib = np.ascontiguousarray(ib, np.int32)
+    kind = np.ascontiguousarray(kind, np.uint8)
+    if not (len(ia) == len(ib) == len(kind)):
+        raise ValueError("window_plan: ia, ib and kind must have one entry per edge")
+    fe = np.ascontiguousarray(np.asarray(focus_edges, np.int64).reshape(-1), np.int32)
+    pc = max(int(n_poses), 0) if pose_cap is None else int(pose_cap)
+    ec = len(ia) if edge_cap is None else int(edge_cap)
+    po, eo = np.zeros(max(pc, 1), np.int32), np.zeros(max(ec, 1), np.int32)
+    npo, neo, an = C.c_int32(-1), C.c_int32(-1), C.c_int32(-1)
+    st = lib().pgo_window_plan(n_poses, len(ia), _ip(ia), _ip(ib), _bp(kind), len(fe), _ip(fe), int(radius), pc, _ip(po), C.byref(npo),
+                               ec, _ip(eo), C.byref(neo), C.byref(an))
+    if st != 0:
+        try:
+            _check(st)
+        except PgoError as e:
+            e.n_poses, e.n_edges = npo.value, neo.value
+            raise
+    return po[:npo.value].copy(), eo[:neo.value].copy(), an.value
+
+
+def _window_args(windows, with_problem):
+    """the CSR arrays of a list of windows, (pose_idx, edge_idx, anchor) or (problem, pose_idx, edge_idx, anchor) each"""
+    off = 1 if with_problem else 0
+    ps = [np.asarray(w[off], np.int64).reshape(-1) for w in windows]
+    es = [np.asarray(w[off + 1], np.int64).reshape(-1) for w in windows]
+    i32 = lambda a: np.ascontiguousarray(a, np.int32)
+    pp = i32(np.concatenate([[0], np.cumsum([len(x) for x in ps])]))
+    ep = i32(np.concatenate([[0], np.cumsum([len(x) for x in es])]))
+    pi = i32(np.concatenate(ps + [np.zeros(1, np.int64)]))   # (one spare entry: never an empty array)
+    ei = i32(np.concatenate(es + [np.zeros(1, np.int64)]))
+    an = i32([int(w[off + 2]) for w in windows] + [0])
+    pr = i32([int(w[0]) for w in windows] + [0]) if with_problem else None
+    return pr, pp, pi, ep, ei, an
+
+
+def _window_solve(fn, h, windows, with_problem, max_iters, commit, want_records):
+    n = len(windows)
+    pr, pp, pi, ep, ei, an = _window_args(windows, with_problem)
+    out = np.zeros((max(int(pp[-1]), 1), 3))
+    res = (WindowResult * max(n, 1))()
+    rows = max(int(max_iters), 0) + 1
+    recs = (IterRecord * max(n * rows, 1))() if want_records else None
+    head = (h, n, _ip(pr)) if with_problem else (h, n)
+    _check(fn(*head, _ip(pp), _ip(pi), _ip(ep), _ip(ei), _ip(an), int(max_iters), int(bool(commit)), _dp(out), res, recs))
+    poses = [out[pp[w]:pp[w + 1]].copy() for w in range(n)]
+    results = [res[w] for w in range(n)]
+    if not want_records:
+        return poses, results
+    return poses, results, [[recs[w * rows + k].as_dict() for k in range(results[w].n_records)] for w in range(n)]
+
+
 def gate_evaluate(r, P, info=None):
     """pgo_gate_evaluate (host only), the 3x3 algebra of Solver.gate: (chi2, chi2_marginal, info_gain) from the residual r,
     the covariance P (3x3) of the predicted residual and the information (I11 I12 I13 I22 I23 I33), None = the identity"""
@@ -590,6 +666,11 @@ class Batch:
         ea = cat(edge_active, [g.n_edges for g in self.graphs], "edge_active")
         pc = cat(pose_constant, [g.n_poses for g in self.graphs], "pose_constant")
         _check(lib().pgo_batch_set_active(self._h, _bp(ea) if ea is not None else None, _bp(pc) if pc is not None else None))
+
+    def window_solve(self, windows, max_iters=2, commit=False, want_records=False):
+        """pgo_batch_window_solve: windows = a list of (problem, pose_idx, edge_idx, anchor), indices in that problem's own
+        numbering; otherwise Solver.window_solve"""
+        return _window_solve(lib().pgo_batch_window_solve, self._h, windows, True, max_iters, commit, want_records)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -751,6 +832,14 @@ class Solver:
                "chi2": a["chi2"].copy(), "chi2_marginal": a["chi2_marginal"].copy(), "info_gain": a["info_gain"].copy(),
                "status": a["status"].copy()}
         return out, rep.as_dict()
+
+    def window_solve(self, windows, max_iters=2, commit=False, want_records=False):
+        """pgo_window_solve: many small windows of the graph in one kernel launch, one workgroup per window (the layer
+        managers' optimize_local_window).  windows = a list of (pose_idx, edge_idx, anchor) -- what window_plan returns --
+        of at most WINDOW_MAX_POSES poses and WINDOW_MAX_EDGES edges each; every window starts from the handle's current poses.
+        Returns (list of (n_w, 3) final poses in list order, list of WindowResult[, list of iteration-record dicts per window]).
+        commit=True also writes the poses into the handle (the lists must be disjoint)."""
+        return _window_solve(lib().pgo_window_solve, self._h, windows, False, max_iters, commit, want_records)
 
     def write_back(self):
         """poses are optimised IN PLACE in Node::p in the reference (main.cpp:99,163)"""

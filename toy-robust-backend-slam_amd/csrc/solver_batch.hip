@@ -30,6 +30,7 @@ struct pgo_batch {
   std::vector<int32_t> h_accept;
   std::vector<double> h_radius;
   bool begun = false;
+  std::vector<int32_t> win_eoff, win_pi, win_ei, win_an;   // pgo_batch_window_solve: edge offsets of the problems, staging
 
   int reduce(bool with_cost, bool with_grad, const double* x) {
     pgo_handle& H = *U;
@@ -408,6 +409,55 @@ int pgo_batch_set_active(pgo_batch_t* b, const uint8_t* edge_active, const uint8
   }
   PGOC(H.set_active(edge_active, pose_constant ? rows.data() : nullptr));
   b->begun = false;
+  return PGO_OK;
+}
+
+// pgo_window_solve on the problems of a batch: window w lists poses and edges of problem[w] in that problem's own numbering.
+// Everything that names a problem is checked here, in the caller's numbering; then the indices are shifted to the union's (rows
+// from row0, the problems' edges concatenated) and the union handle checks the rest and solves
+int pgo_batch_window_solve(pgo_batch_t* b, int32_t nw, const int32_t* problem, const int32_t* pose_ptr, const int32_t* pose_idx,
+                           const int32_t* edge_ptr, const int32_t* edge_idx, const int32_t* anchor, int32_t max_iters, int32_t commit,
+                           double* poses_out, pgo_window_result* results, pgo_iter_record* records) {
+  const std::string who = "pgo_batch_window_solve";
+  if (!b) return fail(PGO_ERR_INVALID_ARG, who + ": null batch");
+  pgo_handle& H = *b->U;
+  if (nw <= 0)   // (n_windows == 0 is PGO_OK, after the handle's own UNSUPPORTED tests)
+    return H.window_solve(who.c_str(), nw, pose_ptr, pose_idx, edge_ptr, edge_idx, anchor, max_iters, commit, poses_out, results, records);
+  if (!problem || !pose_ptr || !pose_idx || !edge_ptr || !edge_idx || !anchor || !results) return fail(PGO_ERR_INVALID_ARG, who + ": null pointer");
+  if (pose_ptr[0] != 0 || edge_ptr[0] != 0) return fail(PGO_ERR_INVALID_ARG, who + ": pose_ptr[0] and edge_ptr[0] must be 0");
+  if (b->win_eoff.empty()) {
+    b->win_eoff.assign((size_t)b->n + 1, 0);
+    for (int32_t k = 0; k < b->n; ++k) b->win_eoff[k + 1] = b->win_eoff[k] + b->nedge[k];
+  }
+  for (int32_t w = 0; w < nw; ++w) {
+    const std::string at = who + ": window " + std::to_string(w) + ": ";
+    if (problem[w] < 0 || problem[w] >= b->n) return fail(PGO_ERR_INVALID_ARG, at + "problem " + std::to_string(problem[w]) + " out of range");
+    if (pose_ptr[w + 1] < pose_ptr[w] || edge_ptr[w + 1] < edge_ptr[w]) return fail(PGO_ERR_INVALID_ARG, at + "pose_ptr / edge_ptr must not decrease");
+    const int32_t k = problem[w], np = b->npos[k], ne = b->nedge[k];
+    for (int32_t i = pose_ptr[w]; i < pose_ptr[w + 1]; ++i)
+      if (pose_idx[i] < 0 || pose_idx[i] >= np)
+        return fail(PGO_ERR_INVALID_ARG, at + "pose index " + std::to_string(pose_idx[i]) + " out of range in problem " + std::to_string(k));
+    for (int32_t i = edge_ptr[w]; i < edge_ptr[w + 1]; ++i)
+      if (edge_idx[i] < 0 || edge_idx[i] >= ne)
+        return fail(PGO_ERR_INVALID_ARG, at + "edge index " + std::to_string(edge_idx[i]) + " out of range in problem " + std::to_string(k));
+    if (anchor[w] < 0 || anchor[w] >= np)
+      return fail(PGO_ERR_INVALID_ARG, at + "the anchor " + std::to_string(anchor[w]) + " is out of range in problem " + std::to_string(k));
+  }
+  // (staging kept on the batch: repeated calls of the same size allocate nothing)
+  std::vector<int32_t>&pi = b->win_pi, &ei = b->win_ei, &an = b->win_an;
+  pi.resize((size_t)pose_ptr[nw]);
+  ei.resize((size_t)edge_ptr[nw]);
+  an.resize((size_t)nw);
+  for (int32_t w = 0; w < nw; ++w) {
+    const int32_t k = problem[w];
+    for (int32_t i = pose_ptr[w]; i < pose_ptr[w + 1]; ++i) pi[i] = b->row0[k] + pose_idx[i];
+    for (int32_t i = edge_ptr[w]; i < edge_ptr[w + 1]; ++i) ei[i] = b->win_eoff[k] + edge_idx[i];
+    an[w] = b->row0[k] + anchor[w];
+  }
+  static const int32_t none = 0;   // (a call whose lists are all empty still passes non-null pointers on)
+  PGOC(H.window_solve(who.c_str(), nw, pose_ptr, pi.empty() ? &none : pi.data(), edge_ptr, ei.empty() ? &none : ei.data(), an.data(),
+                      max_iters, commit, poses_out, results, records));
+  if (commit) b->begun = false;
   return PGO_OK;
 }
 

@@ -7,6 +7,7 @@
 //   solver_direct.hip   the direct chain + low-rank solve
 //   solver_batch.hip    pgo_batch: many independent problems in one handle
 //   solver_abi.hip      the [gpu] part of the C-ABI, test hooks, debug / bench entry points
+//   solver_window.hip   pgo_window_solve: many tiny windows of the graph, one workgroup each (window.hip.h)
 // Every kernel header declares its kernels `static`: a translation unit carries the kernels it launches.
 //
 // Replaces, for DCS-ceres/main.cpp METHOD 0/1 (paths relative to /root/reference/DCS-ceres):
@@ -489,6 +490,21 @@ struct pgo_handle {
   void launch_cg_init_chain(const double* b, double* part_rz, double* part_bb);
   void launch_cg_sr_chain(const dev::CgVec& V, double* part_gamma, double* part_rr);
   void launch_cg_update1_chain(const dev::CgVec& V, int par, const double* pap, int n_pap, double* part_rz, double* part_rr);
+
+  // window solves (pgo_window_solve, solver_window.hip): the lists of a call are resolved on the host into win_host, uploaded
+  // into win_in; win_work holds the per-edge records and the outputs.  Both buffers are grown on demand and kept.
+  std::vector<int32_t> win_edge_local;      // caller's edge -> local edge (built at the first call)
+  std::vector<int32_t> win_pos, win_owner;  // row -> list position in the window being resolved / window that lists it (-1 when idle)
+  std::vector<int32_t> win_host;
+  std::vector<uint32_t> win_sort;
+  void *win_in = nullptr, *win_work = nullptr;
+  int64_t win_in_cap = 0, win_work_cap = 0;
+  bool win_lds_set = false;
+  int win_reserve(void** buf, int64_t* cap, int64_t bytes);
+  // pose_idx / edge_idx / anchor: this handle's caller numbering (a batch: the union's); `who` prefixes the error texts
+  int window_solve(const char* who, int32_t n_windows, const int32_t* pose_ptr, const int32_t* pose_idx, const int32_t* edge_ptr,
+                   const int32_t* edge_idx, const int32_t* anchor, int32_t max_iters, int32_t commit, double* poses_out,
+                   pgo_window_result* results, pgo_iter_record* records);
 
   int create(int32_t N, const double* poses_h, int32_t E, const int32_t* ia, const int32_t* ib, const double* meas,
              const double* info6, const uint8_t* kind);

@@ -493,3 +493,56 @@ extern "C" int pgo_active_plan(int32_t n_poses, int32_t n_edges, const int32_t* 
   if (n_free_poses) *n_free_poses = n_free;
   return PGO_OK;
 }
+
+// The layer managers' window rule (SimpleLayerManagerV2::optimize_local_window, src/simple_layer_manager.cpp:510-555): the poses
+// within `radius` of an end of a focus edge, the odometry edges among them, the focus edges themselves.
+extern "C" int pgo_window_plan(int32_t n_poses, int32_t n_edges, const int32_t* ia, const int32_t* ib, const uint8_t* kind,
+                               int32_t n_focus, const int32_t* focus_edges, int32_t radius, int32_t pose_cap, int32_t* pose_idx_out,
+                               int32_t* n_poses_out, int32_t edge_cap, int32_t* edge_idx_out, int32_t* n_edges_out,
+                               int32_t* anchor_out) {
+  if (n_poses <= 0 || n_edges < 0 || n_focus < 0 || radius < 0 || pose_cap < 0 || edge_cap < 0 || (n_edges && (!ia || !ib || !kind)) ||
+      (n_focus && !focus_edges) || (pose_cap && !pose_idx_out) || (edge_cap && !edge_idx_out))
+    return pgo::fail(PGO_ERR_INVALID_ARG, "pgo_window_plan: bad argument");
+  for (int32_t e = 0; e < n_edges; ++e)
+    if (ia[e] < 0 || ia[e] >= n_poses || ib[e] < 0 || ib[e] >= n_poses)
+      return pgo::fail(PGO_ERR_INVALID_ARG, "pgo_window_plan: endpoint out of range");
+  for (int32_t k = 0; k < n_focus; ++k)
+    if (focus_edges[k] < 0 || focus_edges[k] >= n_edges)
+      return pgo::fail(PGO_ERR_INVALID_ARG, "pgo_window_plan: focus edge out of range");
+  std::vector<uint8_t> active((size_t)n_poses, 0), taken((size_t)n_edges, 0), used((size_t)n_poses, 0);
+  for (int32_t k = 0; k < n_focus; ++k)
+    for (const int32_t c : {ia[focus_edges[k]], ib[focus_edges[k]]}) {
+      const int32_t lo = std::max<int64_t>(0, (int64_t)c - radius), hi = (int32_t)std::min<int64_t>(n_poses - 1, (int64_t)c + radius);
+      for (int32_t i = lo; i <= hi; ++i) active[i] = 1;
+    }
+  std::vector<int32_t> edges;
+  for (int32_t e = 0; e < n_edges; ++e)
+    if (kind[e] == PGO_EDGE_ODOMETRY && active[ia[e]] && active[ib[e]]) {
+      edges.push_back(e);
+      taken[e] = 1;
+    }
+  for (int32_t k = 0; k < n_focus; ++k) {
+    const int32_t e = focus_edges[k];
+    if (ia[e] != ib[e] && !taken[e]) {
+      edges.push_back(e);
+      taken[e] = 1;
+    }
+  }
+  for (const int32_t e : edges) used[ia[e]] = used[ib[e]] = 1;
+  int32_t np = 0;
+  for (int32_t i = 0; i < n_poses; ++i) np += used[i];
+  if (n_poses_out) *n_poses_out = np;
+  if (n_edges_out) *n_edges_out = (int32_t)edges.size();
+  if (np > pose_cap || (int64_t)edges.size() > edge_cap)
+    return pgo::fail(PGO_ERR_INVALID_ARG, "pgo_window_plan: the window has " + std::to_string(np) + " poses and " +
+                                              std::to_string(edges.size()) + " edges: a cap is too small");
+  int32_t k = 0, first = -1;
+  for (int32_t i = 0; i < n_poses; ++i)
+    if (used[i]) {
+      if (first < 0) first = i;
+      pose_idx_out[k++] = i;
+    }
+  std::copy(edges.begin(), edges.end(), edge_idx_out);
+  if (anchor_out) *anchor_out = first;   // (pose 0, when it is among them, is the smallest)
+  return PGO_OK;
+}
