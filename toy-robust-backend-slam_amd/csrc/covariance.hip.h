@@ -343,8 +343,8 @@ __global__ __launch_bounds__(WG) void k_cov_check_rows(int n, const double* __re
 }
 
 // ---------------------------------------------------------------- pgo_edge_gate
-// One lane per candidate (a, b, meas) at the current poses: the plain residual of k_edge_chi2 (heading clamped), the
-// Jacobian of the plain functor in K1's form (g = cos delta / sqrt(1 - sin^2 delta), unclamped), both unscaled.  ia, ib:
+// One lane per candidate (a, b, meas) at the current poses: the plain model of edge_model.h -- the residual with the heading
+// clamped as in k_edge_chi2, the Jacobian as in K1 (g = cos delta / sqrt(1 - sin^2 delta), unclamped) -- both unscaled.  ia, ib:
 // internal pose indices.  flags[k] = status | nonzero << 1 for the host's pass plan.
 template <int PGO_UNIT_ = 0>
 __global__ __launch_bounds__(WG) void k_gate_eval(int n, const int32_t* __restrict__ ia, const int32_t* __restrict__ ib, const double* __restrict__ meas,
@@ -356,24 +356,10 @@ __global__ __launch_bounds__(WG) void k_gate_eval(int n, const int32_t* __restri
   const double dx = meas[3 * (int64_t)k], dy = meas[3 * (int64_t)k + 1], dth = meas[3 * (int64_t)k + 2];
   const double x1 = poses[3 * (int64_t)a], y1 = poses[3 * (int64_t)a + 1], t1 = poses[3 * (int64_t)a + 2];
   const double x2 = poses[3 * (int64_t)b], y2 = poses[3 * (int64_t)b + 1], t2 = poses[3 * (int64_t)b + 2];
-  double s1, c1, s2, c2, sd, cd;
-  sincos(t1, &s1, &c1);
-  sincos(t2, &s2, &c2);
-  sincos(dth, &sd, &cd);
-  const double Dx = x2 - x1, Dy = y2 - y1;
-  const double pa = c1 * Dx + s1 * Dy, pb = -s1 * Dx + c1 * Dy;
-  const double ux = pa - dx, uy = pb - dy;
-  const double ex = cd * ux + sd * uy, ey = -sd * ux + cd * uy;
-  const double c21 = c1 * c2 + s1 * s2, s21 = c1 * s2 - s1 * c2;
-  const double sind = cd * s21 - sd * c21, cosd = cd * c21 + sd * s21;
-  const double et = asin(fmin(1.0, fmax(-1.0, sind)));
-  const double cm = c1 * cd - s1 * sd, sm = s1 * cd + c1 * sd;
-  const double g = cosd / sqrt(1.0 - sind * sind);
   GateRec R;
-  double* J = R.J;
-  J[0] = -cm;  J[1] = -sm;  J[2] = cd * pb - sd * pa;   J[3] = cm;   J[4] = sm;   J[5] = 0.0;
-  J[6] = sm;   J[7] = -cm;  J[8] = -sd * pb - cd * pa;  J[9] = -sm;  J[10] = cm;  J[11] = 0.0;
-  J[12] = 0.0; J[13] = 0.0; J[14] = -g;                 J[15] = 0.0; J[16] = 0.0; J[17] = g;
+  double ex, ey, sind;
+  edge_plain<true>(x1, y1, t1, x2, y2, t2, dx, dy, dth, ex, ey, sind, R.J);   // (edge_model.h)
+  const double et = asin(fmin(1.0, fmax(-1.0, sind)));
   R.r[0] = ex;
   R.r[1] = ey;
   R.r[2] = et;
@@ -385,7 +371,7 @@ __global__ __launch_bounds__(WG) void k_gate_eval(int n, const int32_t* __restri
   for (int c = 0; c < 3; ++c)
 #pragma unroll
     for (int d = 0; d < 6; ++d) {
-      const double v = J[6 * c + d];
+      const double v = R.J[6 * c + d];
       finite = finite && isfinite(v);
       nz = nz || (scale[(d < 3 ? R.ra + d : R.rb + d - 3)] * v != 0.0);
     }

@@ -1,7 +1,7 @@
 // HIP kernels of the pose-graph backend, written for gfx950 (CDNA4, wave64).
 // Everything here is HBM-bandwidth bound fp64 work on 3x3 blocks: no MFMA.
 //
-//   K1  k_edge_eval      fused per-edge SE(2) residual + 3x6 Jacobian + DCS weight + Huber (or, with pgo_set_losses,
+//   K1  k_edge_eval      fused per-edge SE(2) residual + 3x6 Jacobian + DCS weight (edge_model.h) + Huber (or, with pgo_set_losses,
 //                        any loss of loss.h per edge class) corrector (reference: src/ceres_error.cpp:42-94, 135-196 evaluated through
 //                        AutoDiffCostFunction, main.cpp:66-68 loss); writes a 112-byte record per edge
 //   K2  k_assemble       row-tiled segmented reduction of (JS)'(JS) and S J'r (S = Jacobi column
@@ -14,7 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "loss.h"
+#include "edge_model.h"
 
 namespace pgo {
 namespace dev {
@@ -222,17 +222,6 @@ struct EdgeArgs {
   LossClass loss0, loss1, loss2, loss3;
 };
 
-// the loss class of an edge, picked field by field with selects
-__device__ __forceinline__ LossClass pick_loss(const EdgeArgs& A, unsigned k) {
-  LossClass L;
-  L.type = k == 0u ? A.loss0.type : k == 1u ? A.loss1.type : k == 2u ? A.loss2.type : A.loss3.type;
-  L._pad = 0;
-  L.a = k == 0u ? A.loss0.a : k == 1u ? A.loss1.a : k == 2u ? A.loss2.a : A.loss3.a;
-  L.b = k == 0u ? A.loss0.b : k == 1u ? A.loss1.b : k == 2u ? A.loss2.b : A.loss3.b;
-  L.c = k == 0u ? A.loss0.c : k == 1u ? A.loss1.c : k == 2u ? A.loss2.c : A.loss3.c;
-  return L;
-}
-
 // Cholesky factor of a 3x3 information matrix, Omega = L L' (positive definiteness is checked on the host at create)
 struct Chol3 {
   double l00, l10, l11, l20, l21, l22;
@@ -288,26 +277,9 @@ __global__ __launch_bounds__(WG) void k_edge_eval(EdgeArgs A, double* __restrict
     const unsigned fl = A.flags[e];
     const double x1 = A.poses[3 * (int64_t)a], y1 = A.poses[3 * (int64_t)a + 1], t1 = A.poses[3 * (int64_t)a + 2];
     const double x2 = A.poses[3 * (int64_t)b], y2 = A.poses[3 * (int64_t)b + 1], t2 = A.poses[3 * (int64_t)b + 2];
-    double s1, c1, s2, c2, sd, cd;
-    sincos(t1, &s1, &c1);
-    sincos(t2, &s2, &c2);
-    sincos(dth, &sd, &cd);
-    // diff = T^-1 (Ta^-1 Tb)  in closed form
-    const double Dx = x2 - x1, Dy = y2 - y1;
-    const double pa = c1 * Dx + s1 * Dy, pb = -s1 * Dx + c1 * Dy;  // R(t1)' D
-    const double ux = pa - dx, uy = pb - dy;
-    double ex = cd * ux + sd * uy, ey = -sd * ux + cd * uy;         // R(dth)' u
-    const double c21 = c1 * c2 + s1 * s2, s21 = c1 * s2 - s1 * c2;  // R(t2 - t1)
-    const double sind = cd * s21 - sd * c21, cosd = cd * c21 + sd * s21;
+    double ex, ey, sind, J[18];
+    edge_plain<WITH_JAC>(x1, y1, t1, x2, y2, t2, dx, dy, dth, ex, ey, sind, J);   // (edge_model.h)
     double et = asin(sind);
-    double J[18];
-    if (WITH_JAC) {
-      const double cm = c1 * cd - s1 * sd, sm = s1 * cd + c1 * sd;  // R(t1 + dth)
-      const double g = cosd / sqrt(1.0 - sind * sind);              // d asin(u) = du / sqrt(1-u^2)
-      J[0] = -cm;  J[1] = -sm;  J[2] = cd * pb - sd * pa;   J[3] = cm;   J[4] = sm;   J[5] = 0.0;
-      J[6] = sm;   J[7] = -cm;  J[8] = -sd * pb - cd * pa;  J[9] = -sm;  J[10] = cm;  J[11] = 0.0;
-      J[12] = 0.0; J[13] = 0.0; J[14] = -g;                 J[15] = 0.0; J[16] = 0.0; J[17] = g;
-    }
     if (INFO) {  // whiten: e <- L' e, J <- L' J  (|e|^2 becomes e' Omega e)
       const int64_t ne = A.n_edges;
       const Chol3 c = chol3(A.info[e], A.info[ne + e], A.info[2 * ne + e], A.info[3 * ne + e], A.info[4 * ne + e],
@@ -352,30 +324,14 @@ __global__ __launch_bounds__(WG) void k_edge_eval(EdgeArgs A, double* __restrict
 #pragma unroll
         for (int c = 0; c < 18; ++c) J[c] *= sval;
       }
-    } else if (fl & 1u) {  // DCS (src/ceres_error.cpp:185-193): psi = min(1, sqrt(2 phi / (phi + ex^2 + ey^2)))
-      const double res = ex * ex + ey * ey;
-      const double psi_org = sqrt(2.0 * A.phi / (A.phi + res));
-      if (psi_org < 1.0) {
-        if (WITH_JAC) {
-          const double k = -psi_org / (A.phi + res);
-#pragma unroll
-          for (int c = 0; c < 6; ++c) {
-            const double dpsi = k * (ex * J[c] + ey * J[6 + c]);
-            J[c] = psi_org * J[c] + ex * dpsi;
-            J[6 + c] = psi_org * J[6 + c] + ey * dpsi;
-            J[12 + c] = psi_org * J[12 + c] + et * dpsi;
-          }
-        }
-        ex *= psi_org;
-        ey *= psi_org;
-        et *= psi_org;
-      }
+    } else if (fl & 1u) {  // DCS on the plain objective (edge_model.h)
+      edge_dcs<WITH_JAC>(A.phi, ex, ey, et, J);
     }
     const double s = ex * ex + ey * ey + et * et;
     double rho0 = s, sc = 1.0;
     if constexpr (LOSSES) {  // the class's loss; rho'' <= 0 for all of them: the corrector scales by sqrt(rho')
       double rho[3];
-      loss_rho(pick_loss(A, (fl >> 2) & 3u), s, rho);
+      loss_rho(pick_loss(A.loss0, A.loss1, A.loss2, A.loss3, (fl >> 2) & 3u), s, rho);
       rho0 = rho[0];
       if (A.apply_loss) sc = sqrt(rho[1]);
     } else if (A.huber_delta > 0.0) {  // ceres::HuberLoss(a): b = a^2
@@ -463,16 +419,8 @@ __global__ __launch_bounds__(WG) void k_edge_chi2(EdgeArgs A, const int32_t* __r
     const double dx = A.mx[e], dy = A.my[e], dth = A.mt[e];
     const double x1 = A.poses[3 * (int64_t)a], y1 = A.poses[3 * (int64_t)a + 1], t1 = A.poses[3 * (int64_t)a + 2];
     const double x2 = A.poses[3 * (int64_t)b], y2 = A.poses[3 * (int64_t)b + 1], t2 = A.poses[3 * (int64_t)b + 2];
-    double s1, c1, s2, c2, sd, cd;
-    sincos(t1, &s1, &c1);
-    sincos(t2, &s2, &c2);
-    sincos(dth, &sd, &cd);
-    const double Dx = x2 - x1, Dy = y2 - y1;
-    const double pa = c1 * Dx + s1 * Dy, pb = -s1 * Dx + c1 * Dy;
-    const double ux = pa - dx, uy = pb - dy;
-    const double ex = cd * ux + sd * uy, ey = -sd * ux + cd * uy;
-    const double c21 = c1 * c2 + s1 * s2, s21 = c1 * s2 - s1 * c2;
-    const double sind = cd * s21 - sd * c21;
+    double ex, ey, sind;
+    edge_plain<false>(x1, y1, t1, x2, y2, t2, dx, dy, dth, ex, ey, sind, nullptr);   // (edge_model.h)
     const double et = asin(fmin(1.0, fmax(-1.0, sind)));
     const double w00 = A.info[e], w01 = A.info[ne + e], w02 = A.info[2 * ne + e], w11 = A.info[3 * ne + e],
                  w12 = A.info[4 * ne + e], w22 = A.info[5 * ne + e];

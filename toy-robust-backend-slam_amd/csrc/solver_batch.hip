@@ -14,8 +14,9 @@ struct pgo_batch {
   std::vector<int32_t> row0, npos, nedge;     // per problem: first row of the union, poses, edges
   struct State {
     bool active = true;
-    int iter = 0, prev_success = 1, invalid_run = 0, successful = 0, total_pcg = 0, termination = 0;
-    double cost = 0, initial_cost = 0, radius = 0, decrease_factor = 2, x_norm = 0, gmax = 0, seconds = 0;
+    int iter = 0, successful = 0, total_pcg = 0, termination = 0;
+    double cost = 0, initial_cost = 0, x_norm = 0, gmax = 0, seconds = 0;
+    pgo::TrustRegion tr = pgo::tr_begin(0.0);
     std::vector<pgo_iter_record> recs;
   };
   std::vector<State> st;
@@ -68,13 +69,13 @@ int pgo_batch::begin() {
     z.cost = z.initial_cost = h_sums[k].cost;
     z.gmax = h_sums[k].gmax;
     z.x_norm = std::sqrt(h_sums[k].xnorm2);
-    z.radius = o.radius0;
+    z.tr = pgo::tr_begin(o.radius0);
     pgo_iter_record R;
     memset(&R, 0, sizeof R);
     R.step_ok = 1;
     R.cost = z.cost;
     R.gradient_max_norm = z.gmax;
-    R.radius = z.radius;
+    R.radius = z.tr.radius;
     z.recs.push_back(R);
     if (!std::isfinite(z.cost)) {  // "Residual and Jacobian evaluation failed" at the initial point
       z.termination = PGO_TERM_FAILURE;
@@ -85,7 +86,7 @@ int pgo_batch::begin() {
   return PGO_OK;
 }
 
-// one TrustRegionMinimizer iteration of every problem that is still running (same policy as pgo_handle::lm_iteration)
+// one TrustRegionMinimizer iteration of every problem that is still running (the decisions are trust_region.h's)
 int pgo_batch::iterate(bool* all_done) {
   pgo_handle& H = *U;
   const pgo_options& o = H.opt;
@@ -94,13 +95,11 @@ int pgo_batch::iterate(bool* all_done) {
   for (int k = 0; k < n; ++k) {
     State& z = st[k];
     if (z.active) {
-      if (z.iter >= o.max_iters) z.termination = PGO_TERM_NO_CONVERGENCE;
-      else if (z.prev_success && z.gmax <= o.gtol) z.termination = PGO_TERM_CONVERGENCE_GTOL;
-      else if (z.radius < o.min_radius) z.termination = PGO_TERM_MIN_RADIUS;
+      z.termination = pgo::tr_stop_before_step(z.tr, z.iter, o.max_iters, z.gmax, o.gtol, o.min_radius);
       if (z.termination) z.active = false;
     }
     h_prob[k].active = z.active ? 1 : 0;
-    h_radius[k] = z.radius;
+    h_radius[k] = z.tr.radius;
     n_active += z.active;
   }
   *all_done = n_active == 0;
@@ -143,53 +142,45 @@ int pgo_batch::iterate(bool* all_done) {
     r.pcg_rel_residual = q.bb > 0.0 ? std::sqrt(q.rr / q.bb) : 0.0;
     const double model = q.ydotg - 0.5 * q.yHy;
     r.gradient_max_norm = z.gmax;
-    if (!std::isfinite(model) || !std::isfinite(q.step2) || !(model > 0.0)) {  // invalid step
-      if (++z.invalid_run >= 5) {
+    if (!pgo::tr_step_usable(model, q.step2)) {  // invalid step
+      if (pgo::tr_invalid_step(z.tr)) {
         z.termination = PGO_TERM_FAILURE;
         z.active = false;
-        --z.iter;
+        --z.iter;  // the failed iteration is not counted (pgo_handle::lm_iteration_tail counts it)
         continue;
       }
-      z.radius /= z.decrease_factor;
-      z.decrease_factor *= 2.0;
-      z.prev_success = 0;
       r.step_ok = -1;
       r.cost = z.cost;
-      r.radius = z.radius;
+      r.radius = z.tr.radius;
       z.recs.push_back(r);
       continue;
     }
-    z.invalid_run = 0;
+    pgo::tr_valid_step(z.tr);
     double cand_cost = h_sums[k].cost;
-    if (!std::isfinite(cand_cost)) cand_cost = std::numeric_limits<double>::max();
+    if (!std::isfinite(cand_cost)) cand_cost = pgo::TR_DBL_MAX;
     r.step_norm = std::sqrt(q.step2);
     r.cost_change = z.cost - cand_cost;
-    if (r.step_norm <= o.ptol * (z.x_norm + o.ptol) || std::fabs(r.cost_change) <= o.ftol * z.cost) {
-      z.termination = (r.step_norm <= o.ptol * (z.x_norm + o.ptol)) ? PGO_TERM_CONVERGENCE_PTOL : PGO_TERM_CONVERGENCE_FTOL;
+    z.termination = pgo::tr_tolerance_reached(r.step_norm, z.x_norm, o.ptol, r.cost_change, z.cost, o.ftol);
+    if (z.termination) {
       z.active = false;
       r.cost = z.cost;
-      r.radius = z.radius;
+      r.radius = z.tr.radius;
       z.recs.push_back(r);
       continue;
     }
-    const double rho = (cand_cost >= std::numeric_limits<double>::max()) ? -std::numeric_limits<double>::max() : r.cost_change / model;
+    const double rho = pgo::tr_rho(cand_cost, r.cost_change, model);
     r.relative_decrease = rho;
     if (rho > o.min_relative_decrease) {
       h_accept[k] = 1;
       any_accept = true;
-      const double t = 2.0 * rho - 1.0;
-      z.radius = std::min(o.max_radius, z.radius / std::max(1.0 / 3.0, 1.0 - t * t * t));
-      z.decrease_factor = 2.0;
-      z.prev_success = 1;
+      pgo::tr_accept(z.tr, rho, o.max_radius);  // (before the re-linearisation below: a failure there records the new radius)
       ++z.successful;
       r.step_ok = 1;
     } else {
-      z.radius /= z.decrease_factor;
-      z.decrease_factor *= 2.0;
-      z.prev_success = 0;
+      pgo::tr_reject(z.tr);
       r.step_ok = 0;
       r.cost = cand_cost;
-      r.radius = z.radius;
+      r.radius = z.tr.radius;
       z.recs.push_back(r);
     }
   }
@@ -216,7 +207,7 @@ int pgo_batch::iterate(bool* all_done) {
       }
       r.cost = z.cost;
       r.gradient_max_norm = z.gmax;
-      r.radius = z.radius;
+      r.radius = z.tr.radius;
       z.recs.push_back(r);
     }
   }

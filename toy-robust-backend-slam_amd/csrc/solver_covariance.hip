@@ -134,12 +134,12 @@ int setup_system(pgo_handle* h) {
       PGOC(h->linearize(true));
     }
   }
-  const double radius_saved = h->radius;
-  h->radius = std::numeric_limits<double>::infinity();
+  const double radius_saved = h->tr.radius;
+  h->tr.radius = std::numeric_limits<double>::infinity();
   int st = PGO_OK;
   if (h->has_sw) {   // switches eliminated per edge with zero damping: the pose marginal of the joint system
     const int g_sw = std::min(std::max(1, (h->S.n_edges_local + dev::WG - 1) / dev::WG), 1024);
-    hipLaunchKernelGGL(dev::k_switch_prepare<>, dim3(g_sw), dim3(dev::WG), 0, h->stream, h->switch_arrays(), (const double*)h->jr, h->radius,
+    hipLaunchKernelGGL(dev::k_switch_prepare<>, dim3(g_sw), dim3(dev::WG), 0, h->stream, h->switch_arrays(), (const double*)h->jr, h->tr.radius,
                        h->opt.min_lm_diagonal, h->opt.max_lm_diagonal, h->part[2], h->part[3]);
     st = h->check_launch("k_switch_prepare (covariance)");
     if (st == PGO_OK) st = h->assemble_enqueue();
@@ -147,7 +147,7 @@ int setup_system(pgo_handle* h) {
   }
   if (st == PGO_OK) st = h->prepare_system();
   if (st == PGO_OK && h->direct) st = h->prepare_preconditioner();   // (a handle on the direct solve does not set it up per iteration)
-  h->radius = radius_saved;
+  h->tr.radius = radius_saved;
   return st;
 }
 

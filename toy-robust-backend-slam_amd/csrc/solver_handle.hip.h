@@ -37,6 +37,7 @@
 
 #include "comm.h"
 #include "kernels.hip.h"
+#include "trust_region.h"
 #include "solo.hip.h"
 #include "direct.hip.h"
 #include "coarse.hip.h"
@@ -261,8 +262,9 @@ struct pgo_handle {
 
   // LM state (TrustRegionMinimizer)
   bool lm_active = false, lin_valid = false, lm_done = false;
-  int iter = 0, prev_success = 1, invalid_run = 0, successful = 0, total_pcg = 0, termination = 0;
-  double cost = 0, initial_cost = 0, radius = 0, decrease_factor = 2, x_norm = 0, gmax = 0;
+  int iter = 0, successful = 0, total_pcg = 0, termination = 0;
+  double cost = 0, initial_cost = 0, x_norm = 0, gmax = 0;
+  pgo::TrustRegion tr = pgo::tr_begin(0.0);   // radius, decrease factor, invalid-step run, previous step successful
   double t_eval = 0, t_asm = 0, t_lin = 0, t_cand = 0, t_total = 0;   // (t_cand stays 0: the candidate is evaluated with the model terms, inside t_lin)
   std::vector<pgo_iter_record> recs;
 

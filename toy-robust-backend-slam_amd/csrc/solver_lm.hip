@@ -25,7 +25,7 @@ int pgo_handle::linearize(bool reuse_records, bool assemble) {
 // the current radius, re-assembly of the reduced pose system, gradient max-norm over poses AND switches, sum s^2.
 int pgo_handle::refresh_switch_system() {
   const int g_sw = std::min(std::max(1, (S.n_edges_local + dev::WG - 1) / dev::WG), 1024);
-  hipLaunchKernelGGL(dev::k_switch_prepare<>, dim3(g_sw), dim3(dev::WG), 0, stream, switch_arrays(), (const double*)jr, radius,
+  hipLaunchKernelGGL(dev::k_switch_prepare<>, dim3(g_sw), dim3(dev::WG), 0, stream, switch_arrays(), (const double*)jr, tr.radius,
                      opt.min_lm_diagonal, opt.max_lm_diagonal, part[2], part[3]);
   PGOC(check_launch("k_switch_prepare"));
   PGOC(assemble_enqueue());
@@ -47,13 +47,10 @@ int pgo_handle::lm_begin() {
   lm_active = true;
   lm_done = false;
   iter = 0;
-  prev_success = 1;
-  invalid_run = 0;
   successful = 0;
   total_pcg = 0;
   termination = 0;
-  radius = opt.radius0;
-  decrease_factor = 2.0;
+  tr = pgo::tr_begin(opt.radius0);
   last_pcg_iters = 0;
   if (dl_possible) {   // every solve of the handle takes the same solver decisions (lm_iteration)
     direct = false;
@@ -109,13 +106,13 @@ int pgo_handle::lm_begin() {
   R.step_ok = 1;
   R.cost = cost;
   R.gradient_max_norm = gmax;
-  R.radius = radius;
+  R.radius = tr.radius;
   R.seconds = wall_s() - t_begin;
   t_total += R.seconds;
   recs.push_back(R);
   if (opt.verbose) {
     printf("iter      cost      cost_change  |gradient|   |step|    tr_ratio  tr_radius  pcg_it  pcg_rel\n");
-    printf("%4d % .6e  % .2e  % .2e  % .2e  % .2e  % .2e  %6d  %.1e\n", 0, cost, 0.0, gmax, 0.0, 0.0, radius, 0, 0.0);
+    printf("%4d % .6e  % .2e  % .2e  % .2e  % .2e  % .2e  %6d  %.1e\n", 0, cost, 0.0, gmax, 0.0, 0.0, tr.radius, 0, 0.0);
   }
   return PGO_OK;
 }
@@ -123,23 +120,13 @@ int pgo_handle::lm_begin() {
 // one TrustRegionMinimizer iteration.  *stop is set when a termination test fires.
 int pgo_handle::lm_iteration(bool* stop) {
   *stop = false;
+  // METHOD 2: the radius changed since the last assembly (rejected / invalid step); gmax below is over poses AND switches.
+  // (Not at the iteration limit: the solve stops there before anything is assembled.)
+  if (has_sw && !sw_fresh && iter < opt.max_iters) PGOC(refresh_switch_system());
   // FinalizeIterationAndCheckIfMinimizerCanContinue
-  if (iter >= opt.max_iters) {
-    termination = PGO_TERM_NO_CONVERGENCE;
-    *stop = true;
-    return PGO_OK;
-  }
-  if (has_sw && !sw_fresh) PGOC(refresh_switch_system());  // the radius changed since the last assembly (rejected / invalid step)
-  if (prev_success && gmax <= opt.gtol) {
-    termination = PGO_TERM_CONVERGENCE_GTOL;
-    *stop = true;
-    return PGO_OK;
-  }
-  if (radius < opt.min_radius) {
-    termination = PGO_TERM_MIN_RADIUS;
-    *stop = true;
-    return PGO_OK;
-  }
+  termination = pgo::tr_stop_before_step(tr, iter, opt.max_iters, gmax, opt.gtol, opt.min_radius);
+  *stop = termination != 0;
+  if (*stop) return PGO_OK;
   const double it0 = wall_s();
   ++iter;
   pgo_iter_record R;
@@ -270,7 +257,7 @@ int pgo_handle::lm_iteration_tail(bool* stop, pgo_iter_record& R, double it0, do
   t_lin += wall_s() - t0;
   const double ydotg = h_scal[0], yHy = h_scal[1], step2 = h_scal[2] + step2_sw;
   const double model = ydotg - 0.5 * yHy + model_sw;
-  if (!std::isfinite(model) || !std::isfinite(step2) || !(model > 0.0)) {  // invalid step
+  if (!pgo::tr_step_usable(model, step2)) {  // invalid step
     if (direct && !dl_retry) {
       // the direct solve produced no usable step (a capacitance matrix that lost positive definiteness to rounding, a
       // residual the refinement could not repair): this LM iteration is redone by PCG before Ceres' invalid-step rule applies
@@ -284,48 +271,41 @@ int pgo_handle::lm_iteration_tail(bool* stop, pgo_iter_record& R, double it0, do
       dl_retry = false;
       return st2;
     }
-    if (++invalid_run >= 5) {
+    if (pgo::tr_invalid_step(tr)) {  // (the failed iteration stays counted in `iter`; pgo_batch and the window take it back)
       termination = PGO_TERM_FAILURE;
       *stop = true;
       return PGO_OK;
     }
-    radius /= decrease_factor;
-    decrease_factor *= 2.0;
     sw_fresh = false;
-    prev_success = 0;
     R.step_ok = -1;
     R.cost = cost;
-    R.radius = radius;
+    R.radius = tr.radius;
     R.gradient_max_norm = gmax;
     R.seconds = wall_s() - it0;
     t_total += R.seconds;
     recs.push_back(R);
     return PGO_OK;
   }
-  invalid_run = 0;
+  pgo::tr_valid_step(tr);
   double cand_cost = h_scal[6];
-  if (h_scal[7] > 0.0 || !std::isfinite(cand_cost)) cand_cost = std::numeric_limits<double>::max();
+  if (h_scal[7] > 0.0 || !std::isfinite(cand_cost)) cand_cost = pgo::TR_DBL_MAX;
   R.step_norm = std::sqrt(step2);
   R.cost_change = cost - cand_cost;
   R.gradient_max_norm = gmax;
   auto finish = [&](int term) {
     termination = term;
     R.cost = cost;
-    R.radius = radius;
+    R.radius = tr.radius;
     R.seconds = wall_s() - it0;
     t_total += R.seconds;
     recs.push_back(R);
     *stop = true;
   };
-  if (R.step_norm <= opt.ptol * (x_norm + opt.ptol)) {  // ParameterToleranceReached
-    finish(PGO_TERM_CONVERGENCE_PTOL);
+  if (const int term = pgo::tr_tolerance_reached(R.step_norm, x_norm, opt.ptol, R.cost_change, cost, opt.ftol)) {
+    finish(term);
     return PGO_OK;
   }
-  if (std::fabs(R.cost_change) <= opt.ftol * cost) {  // FunctionToleranceReached
-    finish(PGO_TERM_CONVERGENCE_FTOL);
-    return PGO_OK;
-  }
-  const double rho = (cand_cost >= std::numeric_limits<double>::max()) ? -std::numeric_limits<double>::max() : R.cost_change / model;
+  const double rho = pgo::tr_rho(cand_cost, R.cost_change, model);
   R.relative_decrease = rho;
   if (rho > opt.min_relative_decrease) {  // HandleSuccessfulStep
     std::swap(poses, cand);
@@ -333,7 +313,8 @@ int pgo_handle::lm_iteration_tail(bool* stop, pgo_iter_record& R, double it0, do
     hipLaunchKernelGGL(dev::k_xnorm<>, dim3(g_flat), dim3(dev::WG), 0, stream, S.n_loc, S.lo, poses, scale, part[1]);
     PGOC(check_launch("k_xnorm"));
     PGOC(reduce_to_scal({{part[1], g_flat, 0}}, 3));
-    const double t = 2.0 * rho - 1.0;
+    // pgo::tr_accept is applied only once the accepted point has been re-linearised: a failure there records the old radius
+    // (k_window_solve and pgo_batch update the radius first)
     if (has_sw) {
       int st_lin = linearize(false, false);  // METHOD 2 assembles in refresh_switch_system(), with the new radius
       if (st_lin == PGO_ERR_NUMERIC) {
@@ -342,8 +323,7 @@ int pgo_handle::lm_iteration_tail(bool* stop, pgo_iter_record& R, double it0, do
       }
       PGOC(st_lin);
       cost = h_scal[0];
-      radius = radius / std::max(1.0 / 3.0, 1.0 - t * t * t);
-      radius = std::min(opt.max_radius, radius);
+      pgo::tr_accept(tr, rho, opt.max_radius);
       PGOC(fetch_scal(3, 1));
       xnorm2_pose = h_scal[3];
       PGOC(refresh_switch_system());  // gmax over poses and switches, x_norm, reduced system for the next iteration
@@ -365,33 +345,28 @@ int pgo_handle::lm_iteration_tail(bool* stop, pgo_iter_record& R, double it0, do
         return PGO_OK;
       }
       cost = h_scal[0];
-      radius = radius / std::max(1.0 / 3.0, 1.0 - t * t * t);
-      radius = std::min(opt.max_radius, radius);
+      pgo::tr_accept(tr, rho, opt.max_radius);
       gmax = h_scal[2];
       xnorm2_pose = h_scal[3];
       x_norm = std::sqrt(xnorm2_pose);
     }
-    decrease_factor = 2.0;
-    prev_success = 1;
     ++successful;
     R.step_ok = 1;
     R.cost = cost;
     R.gradient_max_norm = gmax;
   } else {  // HandleUnsuccessfulStep
-    radius /= decrease_factor;
-    decrease_factor *= 2.0;
+    pgo::tr_reject(tr);
     sw_fresh = false;
-    prev_success = 0;
     R.step_ok = 0;
     R.cost = cand_cost;
   }
-  R.radius = radius;
+  R.radius = tr.radius;
   R.seconds = wall_s() - it0;
   t_total += R.seconds;
   recs.push_back(R);
   if (opt.verbose)
     printf("%4d % .6e  % .2e  % .2e  % .2e  % .2e  % .2e  %6d  %.1e\n", iter, R.cost, R.cost_change, gmax, R.step_norm, rho,
-           radius, k_it, rel);
+           tr.radius, k_it, rel);
   return PGO_OK;
 }
 

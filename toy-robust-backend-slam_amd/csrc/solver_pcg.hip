@@ -414,7 +414,7 @@ int pgo_handle::factor_chain() {
 
 // LM diagonal for the current radius (per problem in a batched handle) + the preconditioner's set-up
 int pgo_handle::prepare_system() {
-  hipLaunchKernelGGL(dev::k_prepare<>, dim3(g_rows), dim3(dev::WG), 0, stream, hd, (const double*)diag_full, S.n_loc, S.lo, fixed_internal, radius,
+  hipLaunchKernelGGL(dev::k_prepare<>, dim3(g_rows), dim3(dev::WG), 0, stream, hd, (const double*)diag_full, S.n_loc, S.lo, fixed_internal, tr.radius,
                      opt.min_lm_diagonal, opt.max_lm_diagonal, d2, minv, (const uint8_t*)fixed_mask, (const int32_t*)prob_of_256,
                      (const double*)prob_radius, chain_len ? chain_c : (double*)nullptr, hdd);
   PGOC(check_launch("k_prepare"));

@@ -20,6 +20,7 @@
 // fixed lane tree of block_sum_bcast; no atomics.  The handle's internal numbering only enters through the gather indices.
 #pragma once
 #include "kernels.hip.h"
+#include "trust_region.h"
 
 namespace pgo {
 namespace dev {
@@ -64,60 +65,20 @@ __host__ __device__ constexpr int64_t win_lds_doubles(int64_t n3) { return n3 * 
 
 __device__ __forceinline__ int win_tri(int i, int j) { return ((i * (i + 1)) >> 1) + j; }   // j <= i
 
-__device__ __forceinline__ LossClass win_pick_loss(const WinArgs& A, unsigned k) {
-  LossClass L;
-  L.type = k == 0u ? A.loss0.type : k == 1u ? A.loss1.type : k == 2u ? A.loss2.type : A.loss3.type;
-  L._pad = 0;
-  L.a = k == 0u ? A.loss0.a : k == 1u ? A.loss1.a : k == 2u ? A.loss2.a : A.loss3.a;
-  L.b = k == 0u ? A.loss0.b : k == 1u ? A.loss1.b : k == 2u ? A.loss2.b : A.loss3.b;
-  L.c = k == 0u ? A.loss0.c : k == 1u ? A.loss1.c : k == 2u ? A.loss2.c : A.loss3.c;
-  return L;
-}
-
-// One residual block: K1's closed form (k_edge_eval, plain objective: no information weighting, no switch), DCS when flags
-// bit 0 says so, the corrector of the class's loss.  r, J: what Ceres' ResidualBlock::Evaluate hands the minimiser.
+// One residual block on the plain objective (edge_model.h: no information weighting, no switch): DCS when flags bit 0 says
+// so, the corrector of the class's loss.  r, J: what Ceres' ResidualBlock::Evaluate hands the minimiser.
 // cost = 1/2 rho(|e|^2), NaN when |e|^2 is not finite; jac_finite = every entry of the corrected Jacobian is finite.
 __device__ __forceinline__ void win_edge_eval(const double* __restrict__ Pa, const double* __restrict__ Pb, double dx, double dy,
                                               double dth, unsigned fl, double phi, const LossClass& L, double (&r)[3],
                                               double (&J)[18], double& cost, bool& jac_finite) {
-  const double x1 = Pa[0], y1 = Pa[1], t1 = Pa[2], x2 = Pb[0], y2 = Pb[1], t2 = Pb[2];
-  double s1, c1, s2, c2, sd, cd;
-  sincos(t1, &s1, &c1);
-  sincos(t2, &s2, &c2);
-  sincos(dth, &sd, &cd);
-  const double Dx = x2 - x1, Dy = y2 - y1;
-  const double pa = c1 * Dx + s1 * Dy, pb = -s1 * Dx + c1 * Dy;   // R(t1)' D
-  const double ux = pa - dx, uy = pb - dy;
-  double ex = cd * ux + sd * uy, ey = -sd * ux + cd * uy;          // R(dth)' u
-  const double c21 = c1 * c2 + s1 * s2, s21 = c1 * s2 - s1 * c2;   // R(t2 - t1)
-  const double sind = cd * s21 - sd * c21, cosd = cd * c21 + sd * s21;
+  double ex, ey, sind;
+  edge_plain<true>(Pa[0], Pa[1], Pa[2], Pb[0], Pb[1], Pb[2], dx, dy, dth, ex, ey, sind, J);
   double et = asin(sind);
-  const double cm = c1 * cd - s1 * sd, sm = s1 * cd + c1 * sd;     // R(t1 + dth)
-  const double g = cosd / sqrt(1.0 - sind * sind);                 // d asin(u) = du / sqrt(1 - u^2)
-  J[0] = -cm;  J[1] = -sm;  J[2] = cd * pb - sd * pa;   J[3] = cm;   J[4] = sm;   J[5] = 0.0;
-  J[6] = sm;   J[7] = -cm;  J[8] = -sd * pb - cd * pa;  J[9] = -sm;  J[10] = cm;  J[11] = 0.0;
-  J[12] = 0.0; J[13] = 0.0; J[14] = -g;                 J[15] = 0.0; J[16] = 0.0; J[17] = g;
-  if (fl & 1u) {   // DCS (src/ceres_error.cpp:185-193): psi = min(1, sqrt(2 phi / (phi + ex^2 + ey^2)))
-    const double res = ex * ex + ey * ey;
-    const double psi = sqrt(2.0 * phi / (phi + res));
-    if (psi < 1.0) {
-      const double k = -psi / (phi + res);
-#pragma unroll
-      for (int c = 0; c < 6; ++c) {
-        const double dpsi = k * (ex * J[c] + ey * J[6 + c]);
-        J[c] = psi * J[c] + ex * dpsi;
-        J[6 + c] = psi * J[6 + c] + ey * dpsi;
-        J[12 + c] = psi * J[12 + c] + et * dpsi;
-      }
-      ex *= psi;
-      ey *= psi;
-      et *= psi;
-    }
-  }
+  if (fl & 1u) edge_dcs<true>(phi, ex, ey, et, J);
   const double s = ex * ex + ey * ey + et * et;
   double rho[3];
   loss_rho(L, s, rho);
-  const double sc = sqrt(rho[1]);
+  const double sc = sqrt(rho[1]);   // the corrector of a loss with rho'' <= 0, as in k_edge_eval
   bool fin = true;
 #pragma unroll
   for (int c = 0; c < 18; ++c) {
@@ -179,7 +140,6 @@ __global__ __launch_bounds__(WIN_WG) void k_window_solve(WinArgs A) {
   double* __restrict__ zv = gv + A.n3cap;
   double* red = zv + A.n3cap;
   double* rec = A.rec + (int64_t)W.edge0 * WIN_REC;   // (written and read by different lanes: no __restrict__)
-  const double DMAX = 1.7976931348623157e308;
 
   // ---- gather: poses through the translation list, the lane's edge from the handle's arrays (read in place)
   int my_row = 0;
@@ -200,7 +160,7 @@ __global__ __launch_bounds__(WIN_WG) void k_window_solve(WinArgs A) {
     pa = ab & 255;
     pb = ab >> 8;
   }
-  const LossClass L = win_pick_loss(A, (fl >> 2) & 3u);
+  const LossClass L = pick_loss(A.loss0, A.loss1, A.loss2, A.loss3, (fl >> 2) & 3u);
   __syncthreads();
 
   // ---- the initial point
@@ -222,8 +182,8 @@ __global__ __launch_bounds__(WIN_WG) void k_window_solve(WinArgs A) {
   double gmax = block_max_bcast(is_free ? fabs(gv[tid]) : 0.0, red);
   double x_norm = sqrt(block_sum_bcast(is_free ? xs[tid] * xs[tid] : 0.0, red));
   const double initial_cost = cost;
-  double radius = A.radius0, decrease_factor = 2.0;
-  int iter = 0, prev_success = 1, invalid_run = 0, successful = 0, termination = 0, n_rec = 0;
+  TrustRegion T = tr_begin(A.radius0);   // (wavefront-uniform scalars; handed to trust_region.h by reference: registers)
+  int iter = 0, successful = 0, termination = 0, n_rec = 0;
   pgo_iter_record* recs = A.records ? A.records + (int64_t)blockIdx.x * (A.max_iters + 1) : nullptr;
   auto push = [&](int it, int ok, double c, double dc, double gm, double sn, double rd, double rad) {
     if (recs && tid == 0) {
@@ -244,14 +204,13 @@ __global__ __launch_bounds__(WIN_WG) void k_window_solve(WinArgs A) {
     }
     ++n_rec;
   };
-  push(0, 1, cost, 0.0, gmax, 0.0, 0.0, radius);
+  push(0, 1, cost, 0.0, gmax, 0.0, 0.0, T.radius);
   if (!isfinite(cost)) termination = PGO_TERM_FAILURE;   // "Residual and Jacobian evaluation failed" at the initial point
 
-  // ---- TrustRegionMinimizer + LevenbergMarquardtStrategy (pgo_batch::iterate's policy), scalar-uniform
+  // ---- TrustRegionMinimizer + LevenbergMarquardtStrategy: the decisions are trust_region.h's, scalar-uniform
   while (!termination) {
-    if (iter >= A.max_iters) { termination = PGO_TERM_NO_CONVERGENCE; break; }
-    if (prev_success && gmax <= A.gtol) { termination = PGO_TERM_CONVERGENCE_GTOL; break; }
-    if (radius < A.min_radius) { termination = PGO_TERM_MIN_RADIUS; break; }
+    termination = tr_stop_before_step(T, iter, A.max_iters, gmax, A.gtol, A.min_radius);
+    if (termination) break;
     ++iter;
     // S J'J S (every 3x3 block summed by one lane in list order), right-hand side S J'r
     const int ntri = (n3 * (n3 + 1)) >> 1;
@@ -290,7 +249,7 @@ __global__ __launch_bounds__(WIN_WG) void k_window_solve(WinArgs A) {
     if (is_row) {
       const int dd = win_tri(tid, tid);
       const double hii = Hp[dd];
-      Hp[dd] = hii + (is_free ? fmin(fmax(hii, A.min_lm_diagonal), A.max_lm_diagonal) / radius : 1.0);
+      Hp[dd] = hii + (is_free ? fmin(fmax(hii, A.min_lm_diagonal), A.max_lm_diagonal) / T.radius : 1.0);
     }
     __syncthreads();
     // dense Cholesky by 3x3 block columns, right-looking; the right-hand side rides along as one more row (lane 255), so
@@ -393,42 +352,38 @@ __global__ __launch_bounds__(WIN_WG) void k_window_solve(WinArgs A) {
       }
     }
     const double model = block_sum_bcast(me, red);
-    if (lost || !isfinite(model) || !isfinite(step2) || !(model > 0.0)) {   // invalid step
-      if (++invalid_run >= 5) {
+    if (lost || !tr_step_usable(model, step2)) {   // invalid step
+      if (tr_invalid_step(T)) {
         termination = PGO_TERM_FAILURE;
-        --iter;
+        --iter;   // as pgo_batch::iterate: the failed iteration is not counted (pgo_handle counts it)
         break;
       }
-      radius /= decrease_factor;
-      decrease_factor *= 2.0;
-      prev_success = 0;
-      push(iter, -1, cost, 0.0, gmax, 0.0, 0.0, radius);
+      push(iter, -1, cost, 0.0, gmax, 0.0, 0.0, T.radius);
       continue;
     }
-    invalid_run = 0;
+    tr_valid_step(T);
     // the candidate: cost, and its Jacobian for the case that it is accepted
     double ccost = 0.0;
     bool jf = true;
     if (is_edge) win_edge_eval(cs + 3 * pa, cs + 3 * pb, dx, dy, dth, fl, A.phi, L, rc, Jc, ccost, jf);
     double cand_cost = block_sum_bcast(ccost, red);
-    if (!isfinite(cand_cost)) cand_cost = DMAX;
+    if (!isfinite(cand_cost)) cand_cost = TR_DBL_MAX;
     const double step_norm = sqrt(step2), cost_change = cost - cand_cost;
-    if (step_norm <= A.ptol * (x_norm + A.ptol) || fabs(cost_change) <= A.ftol * cost) {
-      termination = (step_norm <= A.ptol * (x_norm + A.ptol)) ? PGO_TERM_CONVERGENCE_PTOL : PGO_TERM_CONVERGENCE_FTOL;
-      push(iter, 0, cost, cost_change, gmax, step_norm, 0.0, radius);
+    termination = tr_tolerance_reached(step_norm, x_norm, A.ptol, cost_change, cost, A.ftol);
+    if (termination) {
+      push(iter, 0, cost, cost_change, gmax, step_norm, 0.0, T.radius);
       break;
     }
-    const double rho = (cand_cost >= DMAX) ? -DMAX : cost_change / model;
+    const double rho = tr_rho(cand_cost, cost_change, model);
     if (rho > A.min_relative_decrease) {   // HandleSuccessfulStep
-      const double t = 2.0 * rho - 1.0;
-      radius = fmin(A.max_radius, radius / fmax(1.0 / 3.0, 1.0 - t * t * t));
-      decrease_factor = 2.0;
-      prev_success = 1;
+      // the radius is updated BEFORE the bad-Jacobian test, whose record carries the new radius (pgo_handle updates it only
+      // after the accepted point has been re-linearised, and records the old radius on a failure there)
+      tr_accept(T, rho, A.max_radius);
       ++successful;
       const double bad_jac = block_max_bcast(jf ? 0.0 : 1.0, red);
       if (bad_jac > 0.0) {   // non-finite Jacobian at an accepted point (the asin' singularity)
         termination = PGO_TERM_FAILURE;
-        push(iter, 1, cost, cost_change, gmax, step_norm, rho, radius);
+        push(iter, 1, cost, cost_change, gmax, step_norm, rho, T.radius);
         break;
       }
       if (is_row) xs[tid] = cs[tid];
@@ -445,12 +400,10 @@ __global__ __launch_bounds__(WIN_WG) void k_window_solve(WinArgs A) {
       __syncthreads();
       gmax = block_max_bcast(is_free ? fabs(gv[tid]) : 0.0, red);
       x_norm = sqrt(block_sum_bcast(is_free ? xs[tid] * xs[tid] : 0.0, red));
-      push(iter, 1, cost, cost_change, gmax, step_norm, rho, radius);
+      push(iter, 1, cost, cost_change, gmax, step_norm, rho, T.radius);
     } else {   // HandleUnsuccessfulStep
-      radius /= decrease_factor;
-      decrease_factor *= 2.0;
-      prev_success = 0;
-      push(iter, 0, cand_cost, cost_change, gmax, step_norm, rho, radius);
+      tr_reject(T);
+      push(iter, 0, cand_cost, cost_change, gmax, step_norm, rho, T.radius);
     }
   }
 
