@@ -488,8 +488,21 @@ typedef struct pgo_covariance_options {
   int32_t max_iters;        /* 20000: PCG iterations per pass before PGO_ERR_NUMERIC                                   */
   int32_t poses_per_pass;   /* 8: columns per pass = 3 x this (1..16)                                                  */
   int32_t cross;            /* 0: out = n x 9 diagonal blocks; 1: out = the (3n x 3n) matrix of all blocks, row-major  */
-  int32_t _pad;
+  int32_t solver;           /* 0: PCG, as described above; 1: the handle's direct solve (below); else PGO_ERR_INVALID_ARG */
 } pgo_covariance_options;
+/* solver = 1 (pgo_pose_covariance and pgo_edge_gate alike) solves the same system A X = B with the factorisation a handle on the
+ * direct solve owns (pgo_handle_info.linear_solver == 2: chain + low rank, set up once per call at D'D = 0), up to 768 columns
+ * per pass -- the library's choice, fewer where the panels of a pass would exceed 512 MiB; poses_per_pass and max_iters are not
+ * read -- and iterative refinement against A: one step always, then the TRUE residual of every column; a column above rtol
+ * takes up to three more steps while the last one lowered its residual by 10 % or more; acceptance up to 1e-5 as above.
+ * Results, symmetrisation, status-1 candidates, constant endpoints, `cross`, report.columns, "the LM state is left as it was"
+ * and "two calls are bitwise equal" are those of solver = 0; a column's result is bitwise the same for every pass width
+ * and every place in a pass.  report.passes counts the direct passes, pcg_iters_max = pcg_iters_total = 0.
+ * PGO_ERR_UNSUPPORTED where the handle is not on the direct solve at the call (a PCG handle; a pgo_set_active mask that cuts
+ * the odometry chain, until pgo_set_active(h, NULL, NULL)) -- never a silent fallback to PCG -- besides the refusals above.
+ * PGO_ERR_NUMERIC names the pose or candidate whose residual stays above 1e-5 or is not finite: the odometry chain alone must
+ * be non-singular for this path (an odometry edge whose rows a redescending loss has zeroed makes it singular where J'J is
+ * not); solver = 0 still applies then.                                                                                   */
 typedef struct pgo_covariance_report {
   int32_t columns, passes, pcg_iters_max, pcg_iters_total;
   double  max_rel_residual;  /* max over columns of the TRUE ||S e - A x|| / ||S e|| (<= max(rtol, floor) on success)      */
@@ -669,6 +682,8 @@ int pgo_debug_normal_eq(pgo_t* h, double* g_or_null, double* hdiag_or_null);    
  *                        1 = that layout and its product kernel (k_spmv_1) on a graph of any size
  *   "cov_poses_per_pass" 1..16 = overrides pgo_covariance_options.poses_per_pass of every pgo_pose_covariance / pgo_edge_gate call (read per call;
  *                        the results agree with every value up to the solver tolerance)
+ *   "cov_direct_cols"    a multiple of 3 in 3..768 = columns per pass of pgo_pose_covariance / pgo_edge_gate with solver = 1 (read per
+ *                        call; any other value >= 0: PGO_ERR_INVALID_ARG from that call; the results are bitwise the same for every width)
  * Unknown name: PGO_ERR_INVALID_ARG.                                                                              */
 int pgo_debug_set_knob(const char* name, long long value);                        /* [host] */
 /* sharding plan of a graph over `world` ranks: for rank r, rows [lo, hi) and the

@@ -129,7 +129,7 @@ class KernelStats(C.Structure):
 class CovarianceOptions(C.Structure):
     """mirror of pgo_covariance_options (defaults: pgo_covariance_options_default)"""
     _fields_ = [("rtol", C.c_double), ("max_iters", C.c_int32), ("poses_per_pass", C.c_int32), ("cross", C.c_int32),
-                ("_pad", C.c_int32)]
+                ("solver", C.c_int32)]
 
     def __init__(self, **kw):
         super().__init__()

@@ -308,6 +308,47 @@ __global__ __launch_bounds__(WG) void k_cov_restart(CovCol* __restrict__ cs, con
   }
 }
 
+// ---- solver = 1 (the handle's direct solve): the column-major panels above meet the row-major panel T [n3][ldt] of the
+// chain sweeps (direct.hip.h: one lane per column) in two transposes through a 32 x 33 LDS tile.  Grid (ldt / 32,
+// n3 / 32 rounded up), block (32, 8).  Columns whose mask is 0 take no part in a step: their T is 0, their x is left alone.
+//   k_cov_to_panel     T[i][c] = r_c[i] for the columns c < m with mask, 0 elsewhere (the padding columns included)
+//   k_cov_from_panel   x_c[i] += T[i][c] for the columns c < m with mask
+template <int PGO_UNIT_ = 0>
+__global__ __launch_bounds__(256) void k_cov_to_panel(int64_t n3, int64_t ld, int m, const double* __restrict__ r, const uint8_t* __restrict__ mask,
+                                                      int64_t ldt, double* __restrict__ T) {
+  __shared__ double tile[32][33];
+  const int64_t i0 = (int64_t)blockIdx.y * 32;
+  const int c0 = blockIdx.x * 32;
+  for (int cc = threadIdx.y; cc < 32; cc += 8) {
+    const int c = c0 + cc;
+    const int64_t i = i0 + threadIdx.x;
+    tile[cc][threadIdx.x] = (c < m && i < n3 && mask[c]) ? r[c * ld + i] : 0.0;
+  }
+  __syncthreads();
+  for (int ii = threadIdx.y; ii < 32; ii += 8) {
+    const int64_t i = i0 + ii;
+    if (i < n3) T[i * ldt + c0 + threadIdx.x] = tile[threadIdx.x][ii];
+  }
+}
+
+template <int PGO_UNIT_ = 0>
+__global__ __launch_bounds__(256) void k_cov_from_panel(int64_t n3, int64_t ld, int m, const double* __restrict__ T, int64_t ldt,
+                                                        const uint8_t* __restrict__ mask, double* __restrict__ x) {
+  __shared__ double tile[32][33];
+  const int64_t i0 = (int64_t)blockIdx.y * 32;
+  const int c0 = blockIdx.x * 32;
+  for (int ii = threadIdx.y; ii < 32; ii += 8) {
+    const int64_t i = i0 + ii;
+    tile[ii][threadIdx.x] = i < n3 ? T[i * ldt + c0 + threadIdx.x] : 0.0;
+  }
+  __syncthreads();
+  for (int cc = threadIdx.y; cc < 32; cc += 8) {
+    const int c = c0 + cc;
+    const int64_t i = i0 + threadIdx.x;
+    if (c < m && i < n3 && mask[c]) x[c * ld + i] += tile[threadIdx.x][cc];
+  }
+}
+
 // out[c * n_out + j] = scale[rows_out[j]] * x_c[rows_out[j]]: the requested rows of Sigma's columns (Sigma = S X)
 template <int PGO_UNIT_ = 0>
 __global__ void k_cov_gather(int m, int64_t ld, const double* __restrict__ x, const double* __restrict__ scale, const int32_t* __restrict__ rows_out,

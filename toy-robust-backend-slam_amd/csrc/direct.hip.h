@@ -1238,6 +1238,173 @@ __global__ __launch_bounds__(256) void k_dlr_combine(const double* __restrict__ 
   }
 }
 
+// ---- many caller-chosen right-hand sides through the same factorisation (pgo_pose_covariance / pgo_edge_gate with
+// solver = 1, solver_covariance.hip): A X = B at D'D = 0,  X = X0 - Z N'(N V X0),  X0 = T^-1 B.  The columns live in a
+// row-major panel [3n][ld] (ld a multiple of 64, the padding columns zero), one lane per column in the sweeps as above.
+// The right-hand sides are PRE-FILLED into the panel (sparse columns the first time, the dense residuals of the
+// refinement afterwards), so the LM kernels above are left as they are: k_dlr_fwd_panel is k_dlr_fwd reading its
+// right-hand side from X in place, k_dlr_mid / _fix / _sep_* run unchanged on the panel.  Columns never mix and every
+// sum has a fixed order: a column's result does not depend on the width of the panel or its place in it.
+template <int PGO_UNIT_ = 0>   // (a template so that only the translation units that launch it carry it)
+__global__ __launch_bounds__(256) void k_dlr_fwd_panel(DlrColsArgs A) {
+  constexpr int CH = 64;
+  __shared__ double fb[CH * DLR_REC];
+  const int tid = threadIdx.x;
+  const int col = blockIdx.x * 256 + tid;
+  const int s = blockIdx.y;
+  const int i0 = s * A.seglen, i1 = min(A.n, i0 + A.seglen);
+  const bool act = col < A.ncols;
+  const int64_t ld = A.ld;
+  double* __restrict__ X = A.X + col;
+  double t0 = 0, t1 = 0, t2 = 0;
+  for (int c0 = i0; c0 < i1; c0 += CH) {
+    const int cnt = min(CH, i1 - c0);
+    __syncthreads();
+    for (int idx = tid; idx < cnt * DLR_REC; idx += 256) fb[idx] = A.fac[(int64_t)c0 * DLR_REC + idx];
+    __syncthreads();
+    for (int b0 = 0; b0 < cnt; b0 += 16) {   // 16 poses' right-hand sides requested together (as k_dlr_mid)
+      double rv[16][3];
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        const int i = c0 + min(b0 + u, cnt - 1);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) rv[u][c] = act ? X[(3 * (int64_t)i + c) * ld] : 0.0;
+      }
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        const int ii = b0 + u;
+        if (ii < cnt) {
+          const int i = c0 + ii;
+          const double* W = fb + ii * DLR_REC;
+          const double n0 = rv[u][0] - (W[0] * t0 + W[1] * t1 + W[2] * t2);
+          const double n1 = rv[u][1] - (W[3] * t0 + W[4] * t1 + W[5] * t2);
+          const double n2 = rv[u][2] - (W[6] * t0 + W[7] * t1 + W[8] * t2);
+          t0 = n0; t1 = n1; t2 = n2;
+          if (act) {
+            X[(3 * (int64_t)i) * ld] = t0;
+            X[(3 * (int64_t)i + 1) * ld] = t1;
+            X[(3 * (int64_t)i + 2) * ld] = t2;
+          }
+        }
+      }
+    }
+  }
+  if (act) {
+    double* e = A.E + (int64_t)s * 3 * ld + col;
+    e[0] = t0; e[ld] = t1; e[2 * ld] = t2;
+  }
+}
+
+// G = V X for the columns of a panel (k_dlr_vdot for many columns): row p of V per workgroup row, the lanes over the
+// columns (coalesced); rows K .. Kp-1 = 0.  grid (ld / 256 rounded up, Kp), block 256.
+template <int PGO_UNIT_ = 0>   // (a template so that only the translation units that launch it carry it)
+__global__ __launch_bounds__(256) void k_dlr_vdot_panel(DlrArgs A, const double* __restrict__ X, int xld, double* __restrict__ G) {
+  const int p = blockIdx.y;
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= xld) return;
+  double val = 0.0;
+  if (p < A.K) {
+    const int j = p / 3, k = p - 3 * j;
+    const int a = A.va[j], b = A.vb[j];
+    const double* v = A.vrec + (int64_t)j * DLR_V + 3 * k;
+    const double* xa = X + (3 * (int64_t)a) * xld + q;
+    const double* xb = X + (3 * (int64_t)b) * xld + q;
+    val = v[0] * xa[0] + v[1] * xa[xld] + v[2] * xa[2 * (int64_t)xld] + v[9] * xb[0] + v[10] * xb[xld] + v[11] * xb[2 * (int64_t)xld];
+  }
+  G[(int64_t)p * xld + q] = val;
+}
+
+// The dense products of that path on the fp64 matrix cores:  C = op(A) B  or  C -= op(A) B,  C [M][ldc] and B [K][ldb]
+// row-major panels (ldc a multiple of 64: whole column tiles), op(A) = A [M][lda] (TA = 0: Z, N) or A' with A [K][lda]
+// (TA = 1: N').  A workgroup of four wavefronts owns a 64 x 64 tile of C, a wavefront 32 x 32 of it as 2 x 2
+// v_mfma_f64_16x16x4_f64 tiles (operand layout: k_chol_panel); k advances in steps of 32 through LDS, the next tiles
+// requested into registers before the current ones are multiplied.  LDS layouts, both conflict-free for the one
+// ds_read_b64 per operand (banks per 32-lane half: cdna_hip_programming.md section 2): k-major [32][80] for B and
+// for A' (row stride 80 doubles = 32 banks apart for the two k of a half), row-major [64][34] for A, whose rows are
+// k-contiguous in memory (stride 34 doubles: the 16 rows x 2 k of a half fall on 32 distinct bank pairs).  Every
+// element of C is one fixed-order sum over k (no split over k, no atomics).
+//   tri = 0: all k in [0, K);  1: k < r0 + 64 (A lower triangular: N);  2: k >= r0 (A' upper triangular: N')
+//   With tri != 0 the 32 x 32 blocks of A above its block diagonal that a 64-wide tile still covers read as 0: k_chol_panel
+//   never writes them (k_tri_apply never read them), so nothing here depends on what that memory holds.
+//   entries of A with k >= kvalid read as 0 (the columns of Z beyond K hold other things)
+struct DlrGemmArgs {
+  const double* A;
+  const double* B;
+  double* C;
+  int64_t lda, ldb, ldc;
+  int32_t M, K;      // rows of C; extent of k, a multiple of 32
+  int32_t kvalid, tri, sub;
+};
+constexpr int GEMM_LDK = 80, GEMM_LDR = 34;
+
+template <int TA>
+__global__ __launch_bounds__(256) void k_dlr_gemm(DlrGemmArgs G) {
+  __shared__ double As[32 * GEMM_LDK];   // (>= 64 * GEMM_LDR)
+  __shared__ double Bs[32 * GEMM_LDK];
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  const int wr = w >> 1, wc = w & 1, mr = lane & 15, mq = lane >> 4;
+  const int r0 = blockIdx.y * 64;
+  const int64_t c0 = (int64_t)blockIdx.x * 64;
+  const int klo = G.tri == 2 ? r0 : 0;
+  const int khi = G.tri == 1 ? min(G.K, r0 + 64) : G.K;
+  double ra[8], rb[8];
+  auto request = [&](int k0) {
+#pragma unroll
+    for (int it = 0; it < 8; ++it) {
+      const int e = it * 256 + tid;
+      if (TA) {
+        const int k = e >> 6, r = e & 63;
+        const bool in_tri = G.tri != 2 || k0 + k >= ((r0 + r) & ~31);
+        ra[it] = (r0 + r < G.M && in_tri) ? G.A[(int64_t)(k0 + k) * G.lda + r0 + r] : 0.0;
+      } else {
+        const int r = e >> 5, k = e & 31;
+        const bool in_tri = G.tri != 1 || k0 + k < ((r0 + r) & ~31) + 32;
+        ra[it] = (r0 + r < G.M && k0 + k < G.kvalid && in_tri) ? G.A[(int64_t)(r0 + r) * G.lda + k0 + k] : 0.0;
+      }
+      const int kb = e >> 6, cb = e & 63;
+      rb[it] = G.B[(int64_t)(k0 + kb) * G.ldb + c0 + cb];
+    }
+  };
+  v4f64 m00 = {0.0, 0.0, 0.0, 0.0}, m01 = m00, m10 = m00, m11 = m00;
+  if (klo < khi) request(klo);
+  for (int k0 = klo; k0 < khi; k0 += 32) {
+    __syncthreads();   // the previous tiles have been read
+#pragma unroll
+    for (int it = 0; it < 8; ++it) {
+      const int e = it * 256 + tid;
+      if (TA) As[(e >> 6) * GEMM_LDK + (e & 63)] = ra[it];
+      else As[(e >> 5) * GEMM_LDR + (e & 31)] = ra[it];
+      Bs[(e >> 6) * GEMM_LDK + (e & 63)] = rb[it];
+    }
+    __syncthreads();
+    if (k0 + 32 < khi) request(k0 + 32);
+#pragma unroll
+    for (int kk = 0; kk < 32; kk += 4) {
+      const double a0 = TA ? As[(kk + mq) * GEMM_LDK + 32 * wr + mr] : As[(32 * wr + mr) * GEMM_LDR + kk + mq];
+      const double a1 = TA ? As[(kk + mq) * GEMM_LDK + 32 * wr + 16 + mr] : As[(32 * wr + 16 + mr) * GEMM_LDR + kk + mq];
+      const double b0 = Bs[(kk + mq) * GEMM_LDK + 32 * wc + mr], b1 = Bs[(kk + mq) * GEMM_LDK + 32 * wc + 16 + mr];
+      m00 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, m00, 0, 0, 0);
+      m01 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, m01, 0, 0, 0);
+      m10 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, m10, 0, 0, 0);
+      m11 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, m11, 0, 0, 0);
+    }
+  }
+  // tile (rt, ct), register g -> row 16 rt + mq + 4 g, column 16 ct + mr
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt) {
+      const int row = r0 + 32 * wr + 16 * rt + mq + 4 * g;
+      if (row < G.M) {
+        double* c = G.C + (int64_t)row * G.ldc + c0 + 32 * wc + mr;
+        const double v0 = rt ? m10[g] : m00[g], v1 = rt ? m11[g] : m01[g];
+        c[0] = G.sub ? c[0] - v0 : v0;
+        c[16] = G.sub ? c[16] - v1 : v1;
+      }
+    }
+  }
+}
+
 // r = b - Ap
 template <int PGO_UNIT_ = 0>   // (a template so that only the translation units that launch it carry it)
 __global__ void k_dlr_resid(int64_t n, const double* __restrict__ b, const double* __restrict__ ap, double* __restrict__ r) {

@@ -3,6 +3,8 @@
 // system (pgo_edge_gate: right-hand sides S J' of candidate edges, three columns each, P = J Sigma J' on the device).  The system is the undamped one of the LM
 // loop, A = S J'J S + I_fixed (k_prepare at radius = infinity), right-hand side S e_k, Sigma = S X.  The preconditioner is the
 // handle's own (one level + the coarse level where the handle has it), set up for D'D = 0 and applied column by column.
+// With pgo_covariance_options.solver = 1 the columns go through the handle's direct solve instead (Session::pass_direct):
+// its factorisation once per call at D'D = 0, up to 768 columns per pass, iterative refinement against the same A.
 #include <functional>
 
 #include "solver_handle.hip.h"
@@ -14,6 +16,10 @@ namespace {
 // (the double-precision floor of an ill-conditioned system: MIT's columns stop near 2e-7 at rtol 1e-10, INTEL with information
 // weighting near 1.5e-6)
 constexpr double COV_RES_FLOOR_MAX = 1e-5;
+// solver = 1: columns per pass at most, the memory the panels of a pass may take, refinement steps beyond the first
+constexpr int DIRECT_COLS_MAX = 768;
+constexpr int64_t DIRECT_PANEL_BYTES = (int64_t)512 << 20;
+constexpr int DIRECT_EXTRA_STEPS = 3;
 
 struct DevScratch {   // buffers of one call, freed on every return path
   std::vector<void*> p;
@@ -121,7 +127,7 @@ struct CoarseOn {
 // the undamped system at the current poses: linearisation (when the LM loop's is not current), METHOD 2's switch
 // elimination without damping, D'D = 0 and the preconditioner for it.  Afterwards the LM loop's own set-up is redone by its
 // next iteration from unchanged inputs (prepare_system; METHOD 2: refresh_switch_system), so its results do not change.
-int setup_system(pgo_handle* h) {
+int setup_system(pgo_handle* h, bool with_preconditioner) {
   if (!h->lin_valid) {   // (not for METHOD 2: refused earlier) Jacobi scales and J'J at the current poses, as pgo_lm_begin
     hipLaunchKernelGGL(dev::k_jacobi_scale<>, dim3(h->g_rows), dim3(dev::WG), 0, h->stream, h->hd, h->S.n_loc, h->S.lo, h->fixed_internal, 0, h->scale,
                        (const uint8_t*)h->fixed_mask);
@@ -146,7 +152,7 @@ int setup_system(pgo_handle* h) {
     h->sw_fresh = false;   // the next LM iteration re-assembles for its radius (refresh_switch_system)
   }
   if (st == PGO_OK) st = h->prepare_system();
-  if (st == PGO_OK && h->direct) st = h->prepare_preconditioner();   // (a handle on the direct solve does not set it up per iteration)
+  if (st == PGO_OK && h->direct && with_preconditioner) st = h->prepare_preconditioner();   // (a handle on the direct solve does not set it up per iteration)
   h->tr.radius = radius_saved;
   return st;
 }
@@ -168,6 +174,12 @@ struct Session {
   int g = 1, gs = 1, gp = 1;  // grids of the vector kernels, of k_spmm, and the larger of both
   DevScratch buf;
   double *X = nullptr, *R = nullptr, *Z = nullptr, *P = nullptr, *AP = nullptr, *part_a = nullptr, *part_b = nullptr;
+  // solver = 1: the factorisation's launch arguments, the row-major panel of the sweeps and its companions, the pass width
+  bool direct = false;
+  pgo_handle::DirectLaunch dl;
+  pgo_handle::DirectPanel panel = {};
+  double* part_c = nullptr;
+  int direct_cols = 0;
   dev::CovCol* cs = nullptr;
   uint8_t* rmask = nullptr;
   std::vector<dev::CovCol> hc;
@@ -185,8 +197,14 @@ struct Session {
     else pgo_covariance_options_default(&o);
     const long long kp = knob("cov_poses_per_pass");
     if (kp >= 0) o.poses_per_pass = (int32_t)kp;
-    if (!(o.rtol > 0.0) || !std::isfinite(o.rtol) || o.max_iters < 1 || o.poses_per_pass < 1 || o.poses_per_pass > dev::COV_MAX_COLS / 3)
+    if (o.solver != 0 && o.solver != 1) return fail(PGO_ERR_INVALID_ARG, fn + ": solver is 0 (PCG) or 1 (the handle's direct solve)");
+    direct = o.solver == 1;
+    if (!(o.rtol > 0.0) || !std::isfinite(o.rtol) || (!direct && (o.max_iters < 1 || o.poses_per_pass < 1 || o.poses_per_pass > dev::COV_MAX_COLS / 3)))
       return fail(PGO_ERR_INVALID_ARG, fn + ": rtol > 0, max_iters >= 1 and poses_per_pass in 1..16 required");
+    const long long kc = direct ? knob("cov_direct_cols") : -1;
+    if (kc >= 0 && (kc < 3 || kc > DIRECT_COLS_MAX || kc % 3 != 0))
+      return fail(PGO_ERR_INVALID_ARG, fn + ": the cov_direct_cols knob is a multiple of 3 in 3..768");
+    direct_cols = (int)kc;
     if ((h->comm && h->comm->world > 1) || h->co_multi) return fail(PGO_ERR_UNSUPPORTED, fn + ": one rank only");
     if (h->batch_mode) return fail(PGO_ERR_UNSUPPORTED, fn + ": not on batched handles");
     // information weighting: even the columns whose true residual reaches 1e-5 differ from a sparse direct inverse by ~1e-3 on
@@ -194,6 +212,9 @@ struct Session {
     if (h->info_mode) return fail(PGO_ERR_UNSUPPORTED, fn + ": not available with info_weighting = 1");
     if (!h->has_anchor())   // (opt.fixed_pose, or a pose made constant by pgo_set_active)
       return fail(PGO_ERR_UNSUPPORTED, fn + ": fixed_pose = -1 leaves the gauge free (J'J is singular)");
+    // solver = 1 never falls back: a PCG handle, or a handle that pgo_set_active took off the direct solve (a cut chain)
+    if (direct && !(h->direct && h->dl_ready))
+      return fail(PGO_ERR_UNSUPPORTED, fn + ": solver = 1 needs a handle on the direct solve (pgo_handle_info.linear_solver = 2)");
     N = h->S.n_poses;
     return PGO_OK;
   }
@@ -221,9 +242,11 @@ struct Session {
         if (!std::isfinite(x[3 * k]) || !std::isfinite(x[3 * k + 1]) || !std::isfinite(x[3 * k + 2]))
           return fail(PGO_ERR_NUMERIC, fn + ": pose " + std::to_string(caller(k)) + " is not finite");
     }
-    PGOC(coarse_for_covariance(h));
-    coarse_on.reset(new CoarseOn(h));
-    PGOC(setup_system(h));
+    if (!direct) {   // (the coarse level is the preconditioner's: not built for the direct solve)
+      PGOC(coarse_for_covariance(h));
+      coarse_on.reset(new CoarseOn(h));
+    }
+    PGOC(setup_system(h, !direct));
     n3 = 3 * N;
     ld = n3;
     g = std::min(std::max(1, (int)((n3 + dev::WG - 1) / dev::WG)), 1024);
@@ -242,13 +265,42 @@ struct Session {
     if (first < N)
       return fail(PGO_ERR_NUMERIC, fn + ": pose " + std::to_string(caller(first)) +
                                        " has a singular diagonal block in J'J (no edge constrains it, or a non-finite Jacobian)");
+    // the direct solve's factorisation of this system, once per call (its dense column: the gradient, not used).  What it
+    // overwrites (the dl_* buffers) every direct solve of the LM loop computes afresh.
+    if (direct) PGOC(h->direct_factor(h->gs, false, &dl));
     return PGO_OK;
+  }
+
+  // poses (pgo_pose_covariance) or candidates (pgo_edge_gate) per pass.  solver = 1: the library's choice, 3 x this <= 768
+  // columns, fewer where the panels of a pass would exceed 512 MiB; poses_per_pass is not read.
+  int per_pass() const {
+    if (!direct) return o.poses_per_pass;
+    if (direct_cols > 0) return direct_cols / 3;
+    const int64_t n3_ = 3 * N, g_ = std::max<int64_t>(1, std::min<int64_t>((n3_ + dev::WG - 1) / dev::WG, 1024));   // (= gp: g >= gs)
+    const int64_t per_col = (int64_t)sizeof(double) * (4 * n3_ + 6 * h->dl_nseg + h->dl_nU + 2 * h->dl_Kp + 3 * g_);
+    return (int)std::max<int64_t>(1, std::min<int64_t>(DIRECT_COLS_MAX, DIRECT_PANEL_BYTES / per_col) / 3);
   }
 
   // the panels of a pass of up to mcap columns
   int alloc(int mcap) {
     PGOC(buf.alloc(&X, mcap * ld));
     PGOC(buf.alloc(&R, mcap * ld));
+    if (direct) {
+      const int64_t ldt = ((int64_t)mcap + 63) / 64 * 64;
+      panel.ld = (int)ldt;
+      PGOC(buf.alloc(&AP, mcap * ld));
+      PGOC(buf.alloc(&panel.T, n3 * ldt));
+      PGOC(buf.alloc(&panel.E, (int64_t)h->dl_nseg * 3 * ldt));
+      PGOC(buf.alloc(&panel.E2, (int64_t)h->dl_nseg * 3 * ldt));
+      PGOC(buf.alloc(&panel.Wm, (int64_t)std::max(1, h->dl_nU) * ldt));
+      PGOC(buf.alloc(&panel.G, (int64_t)h->dl_Kp * ldt));
+      PGOC(buf.alloc(&panel.Y, (int64_t)h->dl_Kp * ldt));
+      PGOC(buf.alloc(&part_a, (int64_t)mcap * gp));
+      PGOC(buf.alloc(&part_b, (int64_t)mcap * gp));
+      PGOC(buf.alloc(&part_c, (int64_t)mcap * gp));
+      PGOC(buf.alloc(&rmask, mcap));
+      return PGO_OK;
+    }
     PGOC(buf.alloc(&Z, mcap * ld));
     PGOC(buf.alloc(&P, mcap * ld));
     PGOC(buf.alloc(&AP, mcap * ld));
@@ -261,10 +313,11 @@ struct Session {
   }
 
   int launch_rhs(int m, const PassRhs& B) {
+    double* p0 = direct ? AP : P;   // (solver = 1 has no search directions: the kernel's zeros go into the product's panel)
     if (B.rec)
-      hipLaunchKernelGGL(dev::k_cov_rhs<dev::RhsSparse>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, dev::RhsSparse{B.rec, B.cand, h->scale}, X, R, P, part_a);
+      hipLaunchKernelGGL(dev::k_cov_rhs<dev::RhsSparse>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, dev::RhsSparse{B.rec, B.cand, h->scale}, X, R, p0, part_a);
     else
-      hipLaunchKernelGGL(dev::k_cov_rhs<dev::RhsUnit>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, dev::RhsUnit{B.rows, h->scale}, X, R, P, part_a);
+      hipLaunchKernelGGL(dev::k_cov_rhs<dev::RhsUnit>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, dev::RhsUnit{B.rows, h->scale}, X, R, p0, part_a);
     return h->check_launch("k_cov_rhs");
   }
   int launch_resid(int m, const PassRhs& B) {
@@ -286,6 +339,7 @@ struct Session {
   // A X = B for the m columns of one pass (every one a non-zero right-hand side): start, PCG in chunks, the true residual,
   // residual replacement and restart.  who(c) names column c's pose or candidate in messages.  X holds the solution.
   int pass(int m, const PassRhs& B, const std::function<std::string(int)>& who) {
+    if (direct) return pass_direct(m, B, who);
     const int every = std::max(1, h->opt.pcg_check_every);
     // start: X = 0, R = B, Z = M^-1 R, P = Z
     std::vector<uint8_t> hdone((size_t)m, 0);   // columns known stopped at the latest host check: no preconditioner apply
@@ -389,6 +443,66 @@ struct Session {
     return PGO_OK;
   }
 
+  // The same, solver = 1:  X = A^-1 B by the handle's direct solve (direct_panel_solve) and iterative refinement against A
+  // (k_spmm):  one step always, then the TRUE residual of every column; a column above rtol takes another step, up to three
+  // more, while the last one lowered its residual by 10 % or more (the replacement rule of pass()); acceptance as there.
+  // A column decides from its own residual only, and a column that rests takes no part in a step (the mask).
+  int pass_direct(int m, const PassRhs& B, const std::function<std::string(int)>& who) {
+    std::vector<uint8_t> mask((size_t)m, 1);
+    const dim3 gt((unsigned)(panel.ld / 32), (unsigned)((n3 + 31) / 32)), bt(32, 8);
+    auto step = [&]() -> int {   // X += A^-1 R on the columns of rmask
+      hipLaunchKernelGGL(dev::k_cov_to_panel<>, gt, bt, 0, h->stream, n3, ld, m, (const double*)R, (const uint8_t*)rmask, (int64_t)panel.ld, panel.T);
+      PGOC(h->check_launch("k_cov_to_panel"));
+      PGOC(h->direct_panel_solve(dl, panel));
+      hipLaunchKernelGGL(dev::k_cov_from_panel<>, gt, bt, 0, h->stream, n3, ld, m, (const double*)panel.T, (int64_t)panel.ld, (const uint8_t*)rmask, X);
+      return h->check_launch("k_cov_from_panel");
+    };
+    auto sums = [&](const double* part, std::vector<double>* out) -> int {   // per column, the partials in fixed order
+      hpart.resize((size_t)m * g);
+      HIPC(hipMemcpyAsync(hpart.data(), part, hpart.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      PGOC(h->sync());
+      out->assign((size_t)m, 0.0);
+      for (int c = 0; c < m; ++c)
+        for (int b = 0; b < g; ++b) (*out)[c] += hpart[(size_t)c * g + b];
+      return PGO_OK;
+    };
+    std::vector<double> bb, rr, res((size_t)m, 0.0), res_prev((size_t)m, std::numeric_limits<double>::infinity());
+    HIPC(hipMemcpyAsync(rmask, mask.data(), (size_t)m, hipMemcpyHostToDevice, h->stream));
+    PGOC(launch_rhs(m, B));   // X = 0, R = B, |B|^2
+    PGOC(sums(part_a, &bb));
+    PGOC(step());
+    PGOC(spmm(h, m, ld, X, AP, part_c, gs));
+    for (int extra = 0;; ++extra) {
+      launch_replace(m, B);   // R = B - A X on the columns of mask, and their step
+      PGOC(h->check_launch("k_cov_replace"));
+      PGOC(step());
+      PGOC(spmm(h, m, ld, X, AP, part_c, gs));
+      PGOC(launch_resid(m, B));
+      PGOC(sums(part_b, &rr));
+      bool any = false;
+      for (int c = 0; c < m; ++c) {
+        res[c] = bb[c] > 0.0 ? std::sqrt(rr[c] / bb[c]) : 0.0;
+        mask[c] = 0;
+        if (res[c] <= o.rtol) continue;
+        if (extra < DIRECT_EXTRA_STEPS && res[c] <= 0.9 * res_prev[c]) {
+          mask[c] = 1;
+          any = true;
+        } else if (!(res[c] <= COV_RES_FLOOR_MAX)) {
+          char msg[260];
+          snprintf(msg, sizeof msg, ": the true residual of %s is %.3e relative after %d refinement steps of the direct solve (the odometry chain "
+                   "alone may be singular where J'J is not: solver = 0 still applies)", who(c).c_str(), res[c], extra + 1);
+          return fail(PGO_ERR_NUMERIC, fn + msg);
+        }
+      }
+      if (!any) break;
+      res_prev = res;
+      HIPC(hipMemcpyAsync(rmask, mask.data(), (size_t)m, hipMemcpyHostToDevice, h->stream));   // (read before the next sums() returns)
+    }
+    for (int c = 0; c < m; ++c) rel_max = std::max(rel_max, res[c]);
+    ++passes;
+    return PGO_OK;
+  }
+
   void fill(pgo_covariance_report* report, int32_t columns, double t0) const {
     if (!report) return;
     report->columns = columns;
@@ -431,7 +545,7 @@ int pgo_pose_covariance(pgo_t* h, int32_t n, const int32_t* poses, const pgo_cov
   PGOC(S.open());
 
   const int64_t ld = S.ld;
-  const int kpp = o.poses_per_pass;
+  const int kpp = S.per_pass();
   const int mcap = 3 * std::min<int64_t>(kpp, n);
   PGOC(S.alloc(mcap));
   double* gath;
@@ -563,7 +677,7 @@ int pgo_edge_gate(pgo_t* h, int32_t n, const int32_t* ia, const int32_t* ib, con
   plan.insert(plan.end(), rest.begin(), rest.end());
   HIPC(hipMemcpyAsync(d_cand, plan.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
   PGOC(h->sync());
-  const int kpp = S.o.poses_per_pass;
+  const int kpp = S.per_pass();
   if (n_solve > 0) PGOC(S.alloc(3 * std::min<int32_t>(kpp, n_solve)));
   for (int32_t j0 = 0; j0 < n_solve; j0 += kpp) {
     const int k = (int)std::min<int32_t>(kpp, n_solve - j0), m = 3 * k;
@@ -571,7 +685,7 @@ int pgo_edge_gate(pgo_t* h, int32_t n, const int32_t* ia, const int32_t* ib, con
     B.rec = rec;
     B.cand = d_cand + j0;
     PGOC(S.pass(m, B, [&](int c) { return "candidate " + std::to_string(plan[j0 + c / 3]); }));
-    hipLaunchKernelGGL(dev::k_gate_reduce<>, dim3(1), dim3(64), 0, h->stream, k, (const int32_t*)(d_cand + j0), (const dev::GateRec*)rec, (const double*)S.X,
+    hipLaunchKernelGGL(dev::k_gate_reduce<>, dim3((unsigned)((k + 63) / 64)), dim3(64), 0, h->stream, k, (const int32_t*)(d_cand + j0), (const dev::GateRec*)rec, (const double*)S.X,
                        S.ld, (const double*)h->scale, (const double*)d_info, d_out);
     PGOC(h->check_launch("k_gate_reduce"));
   }

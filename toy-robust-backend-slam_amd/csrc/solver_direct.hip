@@ -1,12 +1,13 @@
 // The direct linear solve for small chain-like graphs (kernels: direct.hip.h; choice and buffers: solver_create.hip).
 #include "solver_handle.hip.h"
 
-// (H + D'D) y = rhs by Woodbury on chain + low rank, then refine steps of iterative refinement against the assembled
-// matrix; leaves the true residual in r (the model-decrease identity of lm_iteration_tail reads it) and |r|^2, |rhs|^2 in
-// scal[8..9].  LM passes gs and dl_refine; pgo_debug_direct_solve any right-hand side and 0..3 steps.
-int pgo_handle::direct_enqueue(const double* rhs, int refine) {
+// The factorisation every solve starts with, for the system in hd / d2 (LM: the damped one; pgo_pose_covariance and
+// pgo_edge_gate with solver = 1: D'D = 0): the chain's block LDL' and prefix products, Z = T^-1 V' and t = T^-1 rhs
+// (the separators' columns and Schur complement with them), the capacitance matrix I + V Z with V t, its Cholesky
+// factor and explicit inverse.  L receives the argument blocks of the launches for what follows.
+int pgo_handle::direct_factor(const double* rhs, bool fine_prefix, DirectLaunch* L) {
   const int n = S.n_loc, K = dl_K, Kp = dl_Kp, nb = dl_Kp / 32;
-  dev::DlrArgs A;
+  dev::DlrArgs& A = L->A;
   A.n = n;
   A.m = dl_m;
   A.K = K;
@@ -41,12 +42,11 @@ int pgo_handle::direct_enqueue(const double* rhs, int refine) {
   PGOC(check_launch("k_dlr_factor"));
   hipLaunchKernelGGL(dev::k_dlr_prefix<>, dim3(1), dim3(128), 0, stream, (const double*)dl_fac, n, dl_nseg, dl_seglen, dl_pre);
   PGOC(check_launch("k_dlr_prefix"));
-  const bool one_launch = refine > 0 && dl_pre2 != nullptr;   // the refinement's single column: k_dlr_solve1
-  if (one_launch) {
+  if (fine_prefix) {   // the refinement's single column: k_dlr_solve1
     hipLaunchKernelGGL(dev::k_dlr_prefix<>, dim3(1), dim3(512), 0, stream, (const double*)dl_fac, n, dl_nseg2, dl_seglen2, dl_pre2);
     PGOC(check_launch("k_dlr_prefix (fine segments)"));
   }
-  dev::DlrColsArgs C;
+  dev::DlrColsArgs& C = L->C;
   C.fac = dl_fac;
   C.pre = dl_pre;
   C.n = n;
@@ -68,16 +68,9 @@ int pgo_handle::direct_enqueue(const double* rhs, int refine) {
   C.X = dl_Z;
   C.E = dl_E;
   C.E2 = dl_E2;
-  auto solve_columns = [&](const dev::DlrColsArgs& Q) -> int {
-    const dim3 grid((Q.ncols + 255) / 256, Q.nseg);
-    hipLaunchKernelGGL(dev::k_dlr_fwd<>, grid, dim3(256), 0, stream, Q);
-    hipLaunchKernelGGL(dev::k_dlr_mid<>, grid, dim3(256), 0, stream, Q);
-    hipLaunchKernelGGL(dev::k_dlr_fix<>, grid, dim3(256), 0, stream, Q);
-    return check_launch("k_dlr_fwd / _mid / _fix");
-  };
-  PGOC(solve_columns(C));
+  PGOC(direct_sweep(C));
   // the couplings at the separators (k_dlr_sep_*): Y = the U columns of this solve, R once per factorisation
-  dev::DlrSepArgs SA;
+  dev::DlrSepArgs& SA = L->SA;
   SA.nsep = dl_nsep;
   SA.nU = dl_nU;
   SA.n = n;
@@ -88,16 +81,6 @@ int pgo_handle::direct_enqueue(const double* rhs, int refine) {
   SA.Sinv = dl_R;
   SA.trec = dl_trec;
   SA.Wm = dl_Wm;
-  auto separator_fix = [&](double* X, int ld, int ncols) -> int {
-    if (dl_nsep == 0) return PGO_OK;
-    dev::DlrSepArgs Q = SA;
-    Q.X = X;
-    Q.ld = ld;
-    Q.ncols = ncols;
-    hipLaunchKernelGGL(dev::k_dlr_sep_w<>, dim3((ncols + 255) / 256), dim3(256), 0, stream, Q);
-    hipLaunchKernelGGL(dev::k_dlr_sep_apply<>, dim3((ncols + 255) / 256, (3 * n + 63) / 64), dim3(256), 0, stream, Q);
-    return check_launch("k_dlr_sep_w / _apply");
-  };
   if (dl_nsep > 0) {
     SA.X = dl_Z;
     SA.ld = dl_ld;
@@ -105,13 +88,98 @@ int pgo_handle::direct_enqueue(const double* rhs, int refine) {
     hipLaunchKernelGGL(dev::k_dlr_sep_system<>, dim3(1), dim3(256), 0, stream, SA);
     PGOC(check_launch("k_dlr_sep_system"));
   }
-  PGOC(separator_fix(dl_Z, dl_ld, K + 1));
+  PGOC(direct_separator_fix(SA, dl_Z, dl_ld, K + 1));
   hipLaunchKernelGGL(dev::k_dlr_cap<>, dim3((std::max(Kp, K + 1) + 255) / 256, Kp), dim3(256), 0, stream, A);
   PGOC(check_launch("k_dlr_cap"));
   for (int kb = 0; kb < nb; ++kb) {
     hipLaunchKernelGGL(dev::k_chol_panel<>, dim3(std::max(1, nb - 1)), dim3(dev::CHOL_THREADS), dev::CHOL_LDS_BYTES, stream, dl_cap, dl_nm, dl_dwork, Kp, nb, kb);
     PGOC(check_launch("k_chol_panel"));
   }
+  return PGO_OK;
+}
+
+// T^-1 on the columns of Q: the three sweeps (panel_rhs: the right-hand sides stand in Q.X -- k_dlr_fwd_panel)
+int pgo_handle::direct_sweep(const dev::DlrColsArgs& Q, bool panel_rhs) {
+  const dim3 grid((Q.ncols + 255) / 256, Q.nseg);
+  if (panel_rhs) hipLaunchKernelGGL(dev::k_dlr_fwd_panel<>, grid, dim3(256), 0, stream, Q);
+  else hipLaunchKernelGGL(dev::k_dlr_fwd<>, grid, dim3(256), 0, stream, Q);
+  hipLaunchKernelGGL(dev::k_dlr_mid<>, grid, dim3(256), 0, stream, Q);
+  hipLaunchKernelGGL(dev::k_dlr_fix<>, grid, dim3(256), 0, stream, Q);
+  return check_launch("k_dlr_fwd / _mid / _fix");
+}
+
+// the separators' correction of the columns X [3n][ld] (Y and R of the factorisation in SA)
+int pgo_handle::direct_separator_fix(const dev::DlrSepArgs& SA, double* X, int ld, int ncols) {
+  if (dl_nsep == 0) return PGO_OK;
+  dev::DlrSepArgs Q = SA;
+  Q.X = X;
+  Q.ld = ld;
+  Q.ncols = ncols;
+  hipLaunchKernelGGL(dev::k_dlr_sep_w<>, dim3((ncols + 255) / 256), dim3(256), 0, stream, Q);
+  hipLaunchKernelGGL(dev::k_dlr_sep_apply<>, dim3((ncols + 255) / 256, (3 * (int)S.n_loc + 63) / 64), dim3(256), 0, stream, Q);
+  return check_launch("k_dlr_sep_w / _apply");
+}
+
+// T <- (T + V'V)^-1 T for the P.ld columns of a panel, after direct_factor():  X0 = T^-1 B (sweeps on the pre-filled
+// panel, separators),  G = V X0,  W = N'(N G),  X = X0 - Z W  (the three products on the matrix cores: k_dlr_gemm)
+int pgo_handle::direct_panel_solve(const DirectLaunch& L, const DirectPanel& P) {
+  const int n = S.n_loc, K = dl_K, Kp = dl_Kp;
+  dev::DlrColsArgs C = L.C;
+  C.ncols = P.ld;
+  C.K = 0;
+  C.vec_col = -1;
+  C.ld = P.ld;
+  C.nsep = 0;   // (no U columns: Y and R of the factorisation are reused)
+  C.rhs_b = C.rhs_sub = nullptr;
+  C.X = P.T;
+  C.E = P.E;
+  C.E2 = P.E2;
+  PGOC(direct_sweep(C, true));
+  dev::DlrSepArgs SA = L.SA;
+  SA.Wm = P.Wm;
+  PGOC(direct_separator_fix(SA, P.T, P.ld, P.ld));
+  if (K == 0) return PGO_OK;
+  hipLaunchKernelGGL(dev::k_dlr_vdot_panel<>, dim3((P.ld + 255) / 256, Kp), dim3(256), 0, stream, L.A, (const double*)P.T, P.ld, P.G);
+  PGOC(check_launch("k_dlr_vdot_panel"));
+  dev::DlrGemmArgs Q;
+  Q.ldb = Q.ldc = P.ld;
+  Q.K = Q.kvalid = Kp;
+  const dim3 gk(P.ld / 64, (Kp + 63) / 64), gn(P.ld / 64, (3 * n + 63) / 64);
+  Q.A = dl_nm;   // Y = N G
+  Q.lda = Kp;
+  Q.B = P.G;
+  Q.C = P.Y;
+  Q.M = Kp;
+  Q.tri = 1;
+  Q.sub = 0;
+  hipLaunchKernelGGL(dev::k_dlr_gemm<0>, gk, dim3(256), 0, stream, Q);
+  Q.B = P.Y;     // W = N' Y (into G)
+  Q.C = P.G;
+  Q.tri = 2;
+  hipLaunchKernelGGL(dev::k_dlr_gemm<1>, gk, dim3(256), 0, stream, Q);
+  Q.A = dl_Z;    // X = X0 - Z W
+  Q.lda = dl_ld;
+  Q.B = P.G;
+  Q.C = P.T;
+  Q.M = 3 * n;
+  Q.kvalid = K;
+  Q.tri = 0;
+  Q.sub = 1;
+  hipLaunchKernelGGL(dev::k_dlr_gemm<0>, gn, dim3(256), 0, stream, Q);
+  return check_launch("k_dlr_gemm");
+}
+
+// (H + D'D) y = rhs by Woodbury on chain + low rank, then refine steps of iterative refinement against the assembled
+// matrix; leaves the true residual in r (the model-decrease identity of lm_iteration_tail reads it) and |r|^2, |rhs|^2 in
+// scal[8..9].  LM passes gs and dl_refine; pgo_debug_direct_solve any right-hand side and 0..3 steps.
+int pgo_handle::direct_enqueue(const double* rhs, int refine) {
+  const int n = S.n_loc, K = dl_K, Kp = dl_Kp, nb = dl_Kp / 32;
+  const bool one_launch = refine > 0 && dl_pre2 != nullptr;   // the refinement's single column: k_dlr_solve1
+  DirectLaunch L;
+  PGOC(direct_factor(rhs, one_launch, &L));
+  const dev::DlrArgs& A = L.A;
+  const dev::DlrColsArgs& C = L.C;
+  const dev::DlrSepArgs& SA = L.SA;
   auto capacitance_solve = [&]() -> int {  // cvec <- (L L')^-1 cvec = N' (N cvec)
     hipLaunchKernelGGL(dev::k_tri_apply<>, dim3(nb), dim3(256), 0, stream, (const double*)dl_nm, Kp, nb, (const double*)dl_cvec, dl_cy, 0);
     hipLaunchKernelGGL(dev::k_tri_apply<>, dim3(nb), dim3(256), 0, stream, (const double*)dl_nm, Kp, nb, (const double*)dl_cy, dl_cvec, 1);
@@ -159,8 +227,8 @@ int pgo_handle::direct_enqueue(const double* rhs, int refine) {
       C1.rhs_sub = ap;
       C1.X = dl_x1;
       C1.nsep = 0;   // (no U columns: Y and R of the main solve are reused)
-      PGOC(solve_columns(C1));
-      PGOC(separator_fix(dl_x1, 64, 1));
+      PGOC(direct_sweep(C1));
+      PGOC(direct_separator_fix(SA, dl_x1, 64, 1));
     }
     hipLaunchKernelGGL(dev::k_dlr_vdot<>, dim3((Kp + 255) / 256), dim3(256), 0, stream, A, (const double*)dl_x1, xld, 0, dl_cvec);
     PGOC(check_launch("k_dlr_vdot"));

@@ -520,6 +520,21 @@ struct pgo_handle {
   int direct_setup(int32_t N, bool switch_now = false);
   int direct_solve();
   int direct_enqueue(const double* rhs, int refine);
+  struct DirectLaunch {   // the argument blocks of a factorisation's launches, for the solves that follow it
+    dev::DlrArgs A;
+    dev::DlrColsArgs C;
+    dev::DlrSepArgs SA;
+  };
+  int direct_factor(const double* rhs, bool fine_prefix, DirectLaunch* L);
+  int direct_sweep(const dev::DlrColsArgs& Q, bool panel_rhs = false);
+  int direct_separator_fix(const dev::DlrSepArgs& SA, double* X, int ld, int ncols);
+  struct DirectPanel {   // ld columns at once (a multiple of 64): T [3n][ld] right-hand sides in, solutions out
+    double *T, *E, *E2;  // E, E2 [dl_nseg][3][ld]
+    double *Wm;          // [dl_nU][ld]
+    double *G, *Y;       // [dl_Kp][ld]
+    int ld;
+  };
+  int direct_panel_solve(const DirectLaunch& L, const DirectPanel& P);
   int factor_chain();
   int prepare_preconditioner();
   void fill_summary(pgo_summary* s) const;
