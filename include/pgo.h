@@ -554,6 +554,64 @@ int pgo_edge_gate(pgo_t* h, int32_t n, const int32_t* ia, const int32_t* ib, con
                   const double* info6_or_null /* n x 6 */, const pgo_covariance_options* opt_or_null,
                   pgo_edge_gate_result* out /* n */, pgo_covariance_report* report_or_null);                /* [gpu]  */
 
+/* ------------------------------------------------------- joint edge gate
+ * pgo_edge_gate judges every candidate on its own.  The layer managers judge theirs ONE AFTER THE OTHER, each on the estimate
+ * that already holds the edges accepted before it (SimpleLayerManagerV2::run, src/simple_layer_manager.cpp:74-126;
+ * should_split_layer, :173-211).  pgo_edge_gate_joint gives that sequential answer, linearised at the handle's CURRENT poses,
+ * from ONE covariance solve: with P = [J_j Sigma J_k'] the joint covariance of the predicted residuals of all n candidates
+ * (order 3n; Sigma, r_k, J_k as pgo_edge_gate defines them) and Omega_k = L_k L_k', the working state M <- P, rho <- r is
+ * walked in the CALLER'S ORDER, k = 0 .. n-1:
+ *   1. r_cond = rho_k, P_cond = M_kk; chi2_cond = rho_k' (M_kk + Omega_k^-1)^-1 rho_k and info_gain_cond =
+ *      1/2 logdet(I + Omega_k M_kk): pgo_gate_evaluate(rho_k, M_kk, Omega_k), the same statement (csrc/gate.h).
+ *   2. accepted = status 0 and (force[k] == 1, or force[k] == -1 and chi2_cond <= chi2_gate and info_gain_cond >=
+ *      min_info_gain).  force[k] == 0 rejects; force == NULL is -1 everywhere; a status-1 candidate is never accepted.
+ *   3. an accepted candidate conditions the rest on it (Gaussian conditioning, a block Cholesky step of P + Omega^-1 with a
+ *      3x3 pivot): C C' = I + L_k' M_kk L_k, y = C^-1 L_k' rho_k, and for i, j > k with B_i = M_ik L_k C^-T:
+ *      rho_i <- rho_i - B_i y, M_ij <- M_ij - B_i B_j'.  A rejected candidate changes nothing.
+ * Over the accepted set A the sums obey the chain rule: chi2_joint = r_A' (P_AA + Omega_A^-1)^-1 r_A, info_gain_joint =
+ * 1/2 logdet(I + Omega_A P_AA); with every candidate forced in both are independent of the order.  After A is accepted,
+ * M_kk = J_k (Lambda + sum_A J_a' Omega_a J_a)^-1 J_k' and rho_k = r_k + J_k delta, delta the Gauss-Newton step of the problem
+ * augmented by A: with Omega = I and the Trivial loss that is what pgo_edge_gate returns after pgo_set_active has made the
+ * edges of A residual blocks, at the same poses.  should_split_layer's question -- are the new edge and those already added
+ * mutually consistent -- is this call with force = 1 on the edges already added and -1 on the new one.
+ * - out[k] is bitwise what pgo_edge_gate returns for the same arguments and options (the same code path and pass plan).
+ * - P_full (3n x 3n row-major, or NULL) is P, stored symmetric as 1/2 (C + C'); its diagonal blocks are bitwise out[k].P.  The
+ *   rows and columns of a status-1 candidate and of one between two constant poses are exactly 0.  The blocks between candidates
+ *   of different passes are formed from the solved columns after every pass (six-term gathers): no further solve.
+ * - A candidate between two constant poses keeps P_cond = 0 and info_gain_cond = 0 exactly, chi2_cond = chi2 up to rounding;
+ *   accepted, it alters nothing.  A status-1 candidate: every double of its joint record NaN, accepted = 0.
+ * - chi2_joint and info_gain_joint: the sums of the accepted candidates' conditional numbers, in candidate order.
+ * - The elimination runs on the device in fixed order, without atomics: two calls are bitwise equal.  Duplicates are allowed
+ *   (Omega^-1 keeps every pivot positive definite).
+ * - solver = 0 / 1, the tolerance, report, "the LM state is left as it was": those of pgo_edge_gate.
+ * Errors: those of pgo_edge_gate; n > PGO_GATE_JOINT_MAX: PGO_ERR_UNSUPPORTED (split the set, or use pgo_edge_gate); a force
+ * entry outside {-1, 0, 1}, a chi2_gate or min_info_gain that is NaN: PGO_ERR_INVALID_ARG; a pivot I + L' M_kk L that is not
+ * positive definite: PGO_ERR_NUMERIC, pgo_last_error names the candidate.  n == 0 is PGO_OK with a zero summary.
+ * pgo_gate_joint_evaluate is the elimination alone on the host (the same statements, serial): r (3n), P (3n x 3n, read as
+ * given), status (n, 0 / 1) or NULL = all 0; it needs no GPU.                                                             */
+#define PGO_GATE_JOINT_MAX 256          /* candidates per call: P is of order <= 768, one pass of the direct solve */
+typedef struct pgo_gate_joint_options {
+  double chi2_gate;       /* 7.814727903251179 (chi-square, 3 dof, 0.95); +inf = no chi2 test */
+  double min_info_gain;   /* 0 */
+} pgo_gate_joint_options;
+typedef struct pgo_gate_joint_result {
+  double r_cond[3], P_cond[9];          /* rho_k and M_kk at the moment candidate k is decided; P_cond symmetric */
+  double chi2_cond, info_gain_cond;
+  int32_t accepted, status;             /* status as pgo_edge_gate_result: 1 = every double NaN, accepted = 0 */
+} pgo_gate_joint_result;
+typedef struct pgo_gate_joint_summary { int32_t n_accepted, _pad; double chi2_joint, info_gain_joint; } pgo_gate_joint_summary;
+void pgo_gate_joint_options_default(pgo_gate_joint_options*);                                   /* [host] */
+int  pgo_gate_joint_evaluate(int32_t n, const double* r /*3n*/, const double* P /*3n x 3n row-major, symmetric*/,
+                             const double* info6_or_null, const int32_t* status_or_null, const int8_t* force_or_null,
+                             const pgo_gate_joint_options* opt_or_null,
+                             pgo_gate_joint_result* joint, pgo_gate_joint_summary* sum);        /* [host] */
+int  pgo_edge_gate_joint(pgo_t* h, int32_t n, const int32_t* ia, const int32_t* ib, const double* meas_xyt,
+                         const double* info6_or_null, const int8_t* force_or_null,
+                         const pgo_gate_joint_options* jopt_or_null, const pgo_covariance_options* opt_or_null,
+                         pgo_edge_gate_result* out /* n: the independent records */, pgo_gate_joint_result* joint /* n */,
+                         double* P_full_or_null /* 3n x 3n */, pgo_gate_joint_summary* sum,
+                         pgo_covariance_report* report_or_null);                                /* [gpu] */
+
 /* ---------------------------------------------------------- window solves
  * The layer managers' most frequent ceres::Solve: the local window around a newly added loop edge
  * (SimpleLayerManagerV2::optimize_local_window, src/simple_layer_manager.cpp:500-565, window_size 20 at :222,243;
@@ -684,6 +742,8 @@ int pgo_debug_normal_eq(pgo_t* h, double* g_or_null, double* hdiag_or_null);    
  *                        the results agree with every value up to the solver tolerance)
  *   "cov_direct_cols"    a multiple of 3 in 3..768 = columns per pass of pgo_pose_covariance / pgo_edge_gate with solver = 1 (read per
  *                        call; any other value >= 0: PGO_ERR_INVALID_ARG from that call; the results are bitwise the same for every width)
+ *   "gate_joint_shape"   0 = pgo_edge_gate_joint runs its elimination as ONE launch of one workgroup instead of one launch per
+ *                        candidate with a grid of workgroups over the trailing rows (read per call; the results are bitwise the same)
  * Unknown name: PGO_ERR_INVALID_ARG.                                                                              */
 int pgo_debug_set_knob(const char* name, long long value);                        /* [host] */
 /* sharding plan of a graph over `world` ranks: for rank r, rows [lo, hi) and the

@@ -23,6 +23,7 @@ from . import _build
 __all__ = ["PgoError", "Options", "Summary", "IterRecord", "ReadG2O", "Graph", "Solver", "Batch", "Comm", "lib", "build",
            "HandleInfo", "synth_manhattan", "solve_batch", "shard_plan", "shard_halo", "pose_order", "set_knob", "KernelStats", "EXPORTS", "TERMINATION",
            "CovarianceOptions", "CovarianceReport", "Loss", "LOSS_TYPES", "active_plan", "EdgeGateResult", "gate_evaluate",
+           "GateJointOptions", "GateJointResult", "GateJointSummary", "gate_joint_evaluate", "GATE_JOINT_MAX",
            "window_plan", "WindowResult", "WINDOW_MAX_POSES", "WINDOW_MAX_EDGES", "WINDOW_MAX_ITERS"]
 
 EDGE_ODOMETRY, EDGE_CLOSURE, EDGE_BOGUS = 0, 1, 2
@@ -50,9 +51,11 @@ EXPORTS = [
     "pgo_loss_evaluate", "pgo_set_losses", "pgo_batch_set_losses",
     "pgo_set_active", "pgo_batch_set_active", "pgo_active_plan",
     "pgo_gate_evaluate", "pgo_edge_gate",
+    "pgo_gate_joint_options_default", "pgo_gate_joint_evaluate", "pgo_edge_gate_joint",
     "pgo_window_plan", "pgo_window_solve", "pgo_batch_window_solve",
 ]
 WINDOW_MAX_POSES, WINDOW_MAX_EDGES, WINDOW_MAX_ITERS = 64, 256, 32   # PGO_WINDOW_MAX_* (include/pgo.h)
+GATE_JOINT_MAX = 256   # PGO_GATE_JOINT_MAX
 LOSS_TYPES = {"trivial": 0, "huber": 1, "softlone": 2, "cauchy": 3, "arctan": 4, "tukey": 5}   # pgo_loss_type
 
 
@@ -189,6 +192,33 @@ class EdgeGateResult(C.Structure):
                 ("chi2_marginal", C.c_double), ("info_gain", C.c_double), ("status", C.c_int32), ("_pad", C.c_int32)]
 
 
+class GateJointOptions(C.Structure):
+    """mirror of pgo_gate_joint_options (defaults: pgo_gate_joint_options_default)"""
+    _fields_ = [("chi2_gate", C.c_double), ("min_info_gain", C.c_double)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().pgo_gate_joint_options_default(C.byref(self))
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError("unknown joint gate option " + k)
+            if v is not None:
+                setattr(self, k, v)
+
+
+class GateJointResult(C.Structure):
+    """mirror of pgo_gate_joint_result: one candidate of Solver.gate_joint / gate_joint_evaluate"""
+    _fields_ = [("r_cond", C.c_double * 3), ("P_cond", C.c_double * 9), ("chi2_cond", C.c_double), ("info_gain_cond", C.c_double),
+                ("accepted", C.c_int32), ("status", C.c_int32)]
+
+
+class GateJointSummary(C.Structure):
+    _fields_ = [("n_accepted", C.c_int32), ("_pad", C.c_int32), ("chi2_joint", C.c_double), ("info_gain_joint", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "_pad"}
+
+
 class WindowResult(C.Structure):
     """mirror of pgo_window_result: one window of Solver.window_solve / Batch.window_solve"""
     _fields_ = [("termination", C.c_int32), ("iterations", C.c_int32), ("successful_steps", C.c_int32),
@@ -312,6 +342,13 @@ def lib():
     L.pgo_gate_evaluate.argtypes = [dp, dp, dp, dp]
     L.pgo_edge_gate.argtypes = [vp, C.c_int32, ip, ip, dp, dp, C.POINTER(CovarianceOptions), C.POINTER(EdgeGateResult),
                                 C.POINTER(CovarianceReport)]
+    L.pgo_gate_joint_options_default.argtypes = [C.POINTER(GateJointOptions)]
+    L.pgo_gate_joint_options_default.restype = None
+    L.pgo_gate_joint_evaluate.argtypes = [C.c_int32, dp, dp, dp, ip, C.POINTER(C.c_int8), C.POINTER(GateJointOptions),
+                                          C.POINTER(GateJointResult), C.POINTER(GateJointSummary)]
+    L.pgo_edge_gate_joint.argtypes = [vp, C.c_int32, ip, ip, dp, dp, C.POINTER(C.c_int8), C.POINTER(GateJointOptions),
+                                      C.POINTER(CovarianceOptions), C.POINTER(EdgeGateResult), C.POINTER(GateJointResult), dp,
+                                      C.POINTER(GateJointSummary), C.POINTER(CovarianceReport)]
     L.pgo_window_plan.argtypes = [C.c_int32, C.c_int32, ip, ip, bp, C.c_int32, ip, C.c_int32, C.c_int32, ip, ip, C.c_int32, ip, ip, ip]
     L.pgo_window_solve.argtypes = [vp, C.c_int32, ip, ip, ip, ip, ip, C.c_int32, C.c_int32, dp, C.POINTER(WindowResult),
                                    C.POINTER(IterRecord)]
@@ -567,6 +604,44 @@ def gate_evaluate(r, P, info=None):
     return float(out[0]), float(out[1]), float(out[2])
 
 
+def _force_arg(force, n):
+    if force is None:
+        return None, None
+    f = np.ascontiguousarray(np.asarray(force, np.int64).reshape(-1).clip(-128, 127), np.int8)
+    if f.size != n:
+        raise ValueError("force: one entry per candidate (-1 = the tests, 0 = reject, 1 = accept)")
+    return f, f.ctypes.data_as(C.POINTER(C.c_int8))
+
+
+def _joint_dict(res, n, summ):
+    a = np.ctypeslib.as_array(res)[:n]
+    out = {"r_cond": a["r_cond"].copy(), "P_cond": a["P_cond"].reshape(n, 3, 3).copy(), "chi2_cond": a["chi2_cond"].copy(),
+           "info_gain_cond": a["info_gain_cond"].copy(), "accepted": a["accepted"].copy(), "status": a["status"].copy()}
+    out.update(summ.as_dict())
+    return out
+
+
+def gate_joint_evaluate(r, P, info=None, status=None, force=None, chi2_gate=None, min_info_gain=None):
+    """pgo_gate_joint_evaluate (host only), the elimination of Solver.gate_joint: candidates decided one after the other, in
+    the given order, on r (n, 3) and their joint covariance P (3n, 3n), each accepted one conditioning the rest.  info =
+    (n, 6) or None (the identity), status = (n) 0 / 1 or None, force = (n) in {-1, 0, 1} or None (-1: the two tests).
+    Returns a dict: r_cond (n, 3), P_cond (n, 3, 3), chi2_cond, info_gain_cond, accepted, status (n), and the summary
+    n_accepted, chi2_joint, info_gain_joint."""
+    r = np.ascontiguousarray(r, np.float64).reshape(-1)
+    n = r.size // 3
+    P = np.ascontiguousarray(P, np.float64).reshape(-1)
+    w = np.ascontiguousarray(info, np.float64).reshape(-1, 6) if info is not None else None
+    st = np.ascontiguousarray(np.asarray(status, np.int64).reshape(-1), np.int32) if status is not None else None
+    if r.size != 3 * n or P.size != 9 * n * n or (w is not None and w.shape[0] != n) or (st is not None and st.size != n):
+        raise ValueError("gate_joint_evaluate: r (n, 3), P (3n, 3n), info (n, 6) and status (n) required")
+    f, fp = _force_arg(force, n)
+    o = GateJointOptions(chi2_gate=chi2_gate, min_info_gain=min_info_gain)
+    res = (GateJointResult * max(n, 1))()
+    summ = GateJointSummary()
+    _check(lib().pgo_gate_joint_evaluate(n, _dp(r), _dp(P), _dp(w), _ip(st) if st is not None else None, fp, C.byref(o), res, C.byref(summ)))
+    return _joint_dict(res, n, summ)
+
+
 def set_knob(name: str, value: int = -1):
     """test hook (pgo_debug_set_knob): process-wide, read when a handle is created; value < 0 = library default"""
     _check(lib().pgo_debug_set_knob(name.encode(), int(value)))
@@ -811,11 +886,8 @@ class Solver:
         _check(lib().pgo_pose_covariance(self._h, n, _ip(idx), C.byref(o), _dp(out), C.byref(rep)))
         return out, rep.as_dict()
 
-    def gate(self, ia, ib, meas, info=None, **opts):
-        """pgo_edge_gate: candidate loop edges (ia[k], ib[k], meas[k], info[k]) against the current estimate -- they need
-        not be edges of the graph.  info = (n, 6) information entries or None (the identity).  Returns (dict of arrays
-        r (n, 3), J (n, 3, 6), P (n, 3, 3), chi2, chi2_marginal, info_gain, status (n), report dict); opts: the
-        CovarianceOptions fields (poses_per_pass = candidates per pass)."""
+    @staticmethod
+    def _gate_args(ia, ib, meas, info):
         ia = np.ascontiguousarray(np.asarray(ia, np.int64).reshape(-1), np.int32)
         ib = np.ascontiguousarray(np.asarray(ib, np.int64).reshape(-1), np.int32)
         n = ia.size
@@ -823,15 +895,47 @@ class Solver:
         w = np.ascontiguousarray(info, np.float64).reshape(-1, 6) if info is not None else None
         if ib.size != n or meas.shape[0] != n or (w is not None and w.shape[0] != n):
             raise ValueError("gate: ia, ib, meas and info must have one entry per candidate")
+        return n, ia, ib, meas, w
+
+    @staticmethod
+    def _gate_dict(res, n):
+        a = np.ctypeslib.as_array(res)[:n]
+        return {"r": a["r"].copy(), "J": a["J"].reshape(n, 3, 6).copy(), "P": a["P"].reshape(n, 3, 3).copy(),
+                "chi2": a["chi2"].copy(), "chi2_marginal": a["chi2_marginal"].copy(), "info_gain": a["info_gain"].copy(),
+                "status": a["status"].copy()}
+
+    def gate(self, ia, ib, meas, info=None, **opts):
+        """pgo_edge_gate: candidate loop edges (ia[k], ib[k], meas[k], info[k]) against the current estimate -- they need
+        not be edges of the graph.  info = (n, 6) information entries or None (the identity).  Returns (dict of arrays
+        r (n, 3), J (n, 3, 6), P (n, 3, 3), chi2, chi2_marginal, info_gain, status (n), report dict); opts: the
+        CovarianceOptions fields (poses_per_pass = candidates per pass)."""
+        n, ia, ib, meas, w = self._gate_args(ia, ib, meas, info)
         o = CovarianceOptions(**opts)
         res = (EdgeGateResult * max(n, 1))()
         rep = CovarianceReport()
         _check(lib().pgo_edge_gate(self._h, n, _ip(ia), _ip(ib), _dp(meas), _dp(w), C.byref(o), res, C.byref(rep)))
-        a = np.ctypeslib.as_array(res)[:n]
-        out = {"r": a["r"].copy(), "J": a["J"].reshape(n, 3, 6).copy(), "P": a["P"].reshape(n, 3, 3).copy(),
-               "chi2": a["chi2"].copy(), "chi2_marginal": a["chi2_marginal"].copy(), "info_gain": a["info_gain"].copy(),
-               "status": a["status"].copy()}
-        return out, rep.as_dict()
+        return self._gate_dict(res, n), rep.as_dict()
+
+    def gate_joint(self, ia, ib, meas, info=None, force=None, chi2_gate=None, min_info_gain=None, full=False, **cov_opts):
+        """pgo_edge_gate_joint: the candidates of Solver.gate judged ONE AFTER THE OTHER, in the given order, every accepted one
+        conditioning those after it (at most GATE_JOINT_MAX per call).  force = (n) in {-1, 0, 1} or None: -1 applies
+        chi2_cond <= chi2_gate and info_gain_cond >= min_info_gain, 0 rejects, 1 accepts.  Returns (out, joint, report): out
+        as Solver.gate returns it (bitwise), joint the dict of gate_joint_evaluate -- plus "P_full" (3n, 3n), the joint
+        covariance of the predicted residuals, with full=True; cov_opts: the CovarianceOptions fields."""
+        n, ia, ib, meas, w = self._gate_args(ia, ib, meas, info)
+        f, fp = _force_arg(force, n)
+        jo = GateJointOptions(chi2_gate=chi2_gate, min_info_gain=min_info_gain)
+        o = CovarianceOptions(**cov_opts)
+        res = (EdgeGateResult * max(n, 1))()
+        jres = (GateJointResult * max(n, 1))()
+        summ, rep = GateJointSummary(), CovarianceReport()
+        P_full = np.zeros((3 * n, 3 * n)) if full else None
+        _check(lib().pgo_edge_gate_joint(self._h, n, _ip(ia), _ip(ib), _dp(meas), _dp(w), fp, C.byref(jo), C.byref(o), res, jres,
+                                         _dp(P_full), C.byref(summ), C.byref(rep)))
+        joint = _joint_dict(jres, n, summ)
+        if full:
+            joint["P_full"] = P_full
+        return self._gate_dict(res, n), joint, rep.as_dict()
 
     def window_solve(self, windows, max_iters=2, commit=False, want_records=False):
         """pgo_window_solve: many small windows of the graph in one kernel launch, one workgroup per window (the layer

@@ -422,6 +422,28 @@ __global__ __launch_bounds__(WG) void k_gate_eval(int n, const int32_t* __restri
   flags[k] = R.status | (R.nonzero << 1);
 }
 
+// One 3x3 block of J Sigma J', unsymmetrised: P[a][c] = J_g[a] . (S x_c) over the six rows the Jacobian of g touches, x_c =
+// x + c ld the three solved columns of ONE candidate (g itself: a diagonal block, k_gate_reduce; another one: a cross block,
+// k_gate_cross).  x == nullptr: zeros.  Fixed-order sums.
+__device__ __forceinline__ void gate_block(const GateRec& g, const double* __restrict__ x, int64_t ld, const double* __restrict__ scale, double P[9]) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    double y[6];   // rows ra .. ra + 2, rb .. rb + 2 of column c of Sigma J'
+#pragma unroll
+    for (int d = 0; d < 6; ++d) {
+      const int64_t row = d < 3 ? g.ra + d : g.rb + d - 3;
+      y[d] = x ? scale[row] * x[(int64_t)c * ld + row] : 0.0;
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      double s = 0.0;
+#pragma unroll
+      for (int d = 0; d < 6; ++d) s += g.J[6 * a + d] * y[d];
+      P[3 * a + c] = s;
+    }
+  }
+}
+
 // One lane per candidate of a pass (record cand[j], columns 3 j .. 3 j + 2 of the panel x): the six rows of S X its
 // Jacobian touches, P = J (S X) symmetrised, the 3x3 algebra of gate.h, the result record out[cand[j]].  x == nullptr: the
 // candidates that took no columns (P = 0: both endpoints constant; status 1: every double NaN).  Fixed-order sums, no
@@ -446,22 +468,7 @@ __global__ void k_gate_reduce(int k, const int32_t* __restrict__ cand, const Gat
     return;
   }
   double P[9];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    double y[6];   // rows ra .. ra + 2, rb .. rb + 2 of column c of Sigma J'
-#pragma unroll
-    for (int d = 0; d < 6; ++d) {
-      const int64_t row = d < 3 ? g.ra + d : g.rb + d - 3;
-      y[d] = x ? scale[row] * x[(int64_t)(3 * j + c) * ld + row] : 0.0;
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      double s = 0.0;
-#pragma unroll
-      for (int d = 0; d < 6; ++d) s += g.J[6 * a + d] * y[d];
-      P[3 * a + c] = s;
-    }
-  }
+  gate_block(g, x ? x + (int64_t)3 * j * ld : nullptr, ld, scale, P);
 #pragma unroll
   for (int a = 0; a < 3; ++a)
 #pragma unroll
@@ -475,6 +482,102 @@ __global__ void k_gate_reduce(int k, const int32_t* __restrict__ cand, const Gat
   o.chi2_marginal = res[1];
   o.info_gain = res[2];
   out[q] = o;
+}
+
+// ---------------------------------------------------------------- pgo_edge_gate_joint
+// After every pass: the blocks of C = [J_q Sigma J_p'] (order W = 3n, the caller's candidate order) between EVERY candidate
+// with columns, q = all[0 .. n_all), and the k candidates of the pass, p = cand[j] with the columns 3 j .. 3 j + 2 of the
+// panel x.  One lane per pair, neighbours sharing the columns; every entry of C is written by one lane, once per call.
+template <int PGO_UNIT_ = 0>
+__global__ __launch_bounds__(WG) void k_gate_cross(int n_all, const int32_t* __restrict__ all, int k, const int32_t* __restrict__ cand,
+                                                   const GateRec* __restrict__ rec, const double* __restrict__ x, int64_t ld,
+                                                   const double* __restrict__ scale, int64_t W, double* __restrict__ C) {
+  const int t = blockIdx.x * WG + threadIdx.x;
+  if (t >= n_all * k) return;
+  const int j = t / n_all, q = all[t % n_all], p = cand[j];
+  double P[9];
+  gate_block(rec[q], x + (int64_t)3 * j * ld, ld, scale, P);
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) C[(3 * (int64_t)q + a) * W + 3 * p + c] = P[3 * a + c];
+}
+
+// P = 1/2 (C + C'), the diagonal as it stands: a diagonal block comes out bitwise as k_gate_reduce symmetrises its own
+template <int PGO_UNIT_ = 0>
+__global__ __launch_bounds__(WG) void k_gate_symmetrise(int64_t W, const double* __restrict__ C, double* __restrict__ P) {
+  const int64_t t = (int64_t)blockIdx.x * WG + threadIdx.x;
+  if (t >= W * W) return;
+  const int64_t i = t / W, j = t % W;
+  P[t] = i == j ? C[t] : 0.5 * (C[i * W + j] + C[j * W + i]);
+}
+
+// the working state of the elimination: rho <- r, the status of every candidate in the caller's order
+template <int PGO_UNIT_ = 0>
+__global__ __launch_bounds__(WG) void k_gate_joint_begin(int n, const GateRec* __restrict__ rec, double* __restrict__ rho, int32_t* __restrict__ status) {
+  const int q = blockIdx.x * WG + threadIdx.x;
+  if (q >= n) return;
+  for (int i = 0; i < 3; ++i) rho[3 * q + i] = rec[q].r[i];
+  status[q] = rec[q].status;
+}
+
+// The elimination of the joint gate (gate.h: gate_joint_decide, gate_pivot_row, gate_downdate), candidates k0 .. k1 - 1 in
+// order.  Every workgroup decides candidate k for itself from (rho_k, M_kk) -- the same numbers, the same decision -- and forms
+// all of B in LDS; workgroup 0 writes the record and downdates rho; the rows of the trailing matrix are dealt to the
+// workgroups in turn, GATE_JOINT_WG / 256 rows at a time, 256 lanes along a row.  A launch reads row / column block k and
+// writes only indices > k, so the workgroups of one launch never meet.  Two admissible shapes from this one body:
+//   one launch, ONE workgroup, k0 .. k1 = 0 .. n (the barrier at the end of a step orders it against the next);
+//   one launch per candidate (k1 = k0 + 1), any grid.
+// Never a grid of several workgroups with k1 > k0 + 1: there is no barrier across workgroups here.  No atomics; every sum in
+// fixed order, independent of the grid.
+constexpr int GATE_JOINT_WG = 1024;
+struct GateJointArgs {
+  int n, k0, k1;
+  double* M;      // (3n)^2 row-major, symmetric: P on entry
+  double* rho;    // 3n
+  const double* info6;   // n x 6 or nullptr
+  const int32_t* status;
+  const int8_t* force;   // n or nullptr
+  double chi2_gate, min_info_gain;
+  pgo_gate_joint_result* joint;
+};
+template <int PGO_UNIT_ = 0>
+__global__ __launch_bounds__(GATE_JOINT_WG) void k_gate_joint_step(GateJointArgs A) {
+  __shared__ double B[9 * PGO_GATE_JOINT_MAX];
+  __shared__ GatePivot piv;
+  __shared__ int go;
+  const int64_t W = 3 * (int64_t)A.n;
+  for (int k = A.k0; k < A.k1; ++k) {
+    if (threadIdx.x == 0) {
+      double Mkk[9], rk[3];
+      for (int a = 0; a < 3; ++a) {
+        rk[a] = A.rho[3 * k + a];
+        for (int b = 0; b < 3; ++b) Mkk[3 * a + b] = A.M[(3 * (int64_t)k + a) * W + 3 * k + b];
+      }
+      pgo_gate_joint_result o;
+      GatePivot v;
+      const int st = gate_joint_decide(rk, Mkk, A.info6 ? A.info6 + 6 * (int64_t)k : nullptr, A.status[k], A.force ? A.force[k] : -1, A.chi2_gate,
+                                       A.min_info_gain, &o, &v);
+      go = st == GATE_OK && o.accepted;
+      if (go) piv = v;
+      if (blockIdx.x == 0) A.joint[k] = o;
+    }
+    __syncthreads();
+    const int64_t lo = 3 * (int64_t)(k + 1);
+    if (go) {   // (the same for every lane of the workgroup)
+      for (int64_t p = lo + threadIdx.x; p < W; p += GATE_JOINT_WG) {
+        const double m[3] = {A.M[p * W + 3 * k], A.M[p * W + 3 * k + 1], A.M[p * W + 3 * k + 2]};
+        gate_pivot_row(piv, m, &B[3 * p]);
+      }
+      __syncthreads();
+      if (blockIdx.x == 0)
+        for (int64_t p = lo + threadIdx.x; p < W; p += GATE_JOINT_WG) A.rho[p] = gate_downdate(A.rho[p], &B[3 * p], piv.y);
+      const int lane = threadIdx.x % 256, rl = threadIdx.x / 256, RL = GATE_JOINT_WG / 256;
+      for (int64_t p = lo + (int64_t)blockIdx.x * RL + rl; p < W; p += (int64_t)gridDim.x * RL)
+        for (int64_t q = lo + lane; q < W; q += 256) A.M[p * W + q] = gate_downdate(A.M[p * W + q], &B[3 * p], &B[3 * q]);
+    }
+    __syncthreads();
+  }
 }
 
 }  // namespace dev

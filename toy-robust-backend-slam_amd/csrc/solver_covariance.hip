@@ -3,6 +3,8 @@
 // system (pgo_edge_gate: right-hand sides S J' of candidate edges, three columns each, P = J Sigma J' on the device).  The system is the undamped one of the LM
 // loop, A = S J'J S + I_fixed (k_prepare at radius = infinity), right-hand side S e_k, Sigma = S X.  The preconditioner is the
 // handle's own (one level + the coarse level where the handle has it), set up for D'D = 0 and applied column by column.
+// pgo_edge_gate_joint is the same call plus the joint covariance of all candidates from the solved columns (k_gate_cross after
+// every pass) and the sequential elimination on it (k_gate_joint_step, one launch per candidate).
 // With pgo_covariance_options.solver = 1 the columns go through the handle's direct solve instead (Session::pass_direct):
 // its factorisation once per call at D'D = 0, up to 768 columns per pass, iterative refinement against the same A.
 #include <functional>
@@ -617,26 +619,59 @@ int pgo_gate_evaluate(const double r[3], const double P[9], const double* info6_
   return PGO_OK;
 }
 
-int pgo_edge_gate(pgo_t* h, int32_t n, const int32_t* ia, const int32_t* ib, const double* meas_xyt, const double* info6_or_null,
-                  const pgo_covariance_options* opt_or_null, pgo_edge_gate_result* out, pgo_covariance_report* report) {
+}  // extern "C"
+
+namespace {
+
+bool info6_ok(const double* w) {
+  double l[6];
+  bool ok = true;
+  for (int c = 0; c < 6; ++c) ok = ok && std::isfinite(w[c]);
+  return ok && pgo::gate_chol3(w, l);
+}
+
+// what pgo_edge_gate_joint asks for beyond pgo_edge_gate
+struct JointCall {
+  const int8_t* force;
+  pgo_gate_joint_options o;
+  pgo_gate_joint_result* joint;
+  double* P_full;
+  pgo_gate_joint_summary* sum;
+};
+
+int joint_options(const std::string& fn, int32_t n, const int8_t* force, const pgo_gate_joint_options* opt_or_null, pgo_gate_joint_options* o) {
+  if (opt_or_null) *o = *opt_or_null;
+  else pgo_gate_joint_options_default(o);
+  if (std::isnan(o->chi2_gate) || std::isnan(o->min_info_gain)) return fail(PGO_ERR_INVALID_ARG, fn + ": chi2_gate or min_info_gain is NaN");
+  if (n > PGO_GATE_JOINT_MAX)
+    return fail(PGO_ERR_UNSUPPORTED, fn + ": " + std::to_string(n) + " candidates, at most " + std::to_string(PGO_GATE_JOINT_MAX) +
+                                         " per call (split the set, or use pgo_edge_gate)");
+  for (int32_t k = 0; force && k < n; ++k)
+    if (force[k] < -1 || force[k] > 1)
+      return fail(PGO_ERR_INVALID_ARG, fn + ": force[" + std::to_string(k) + "] = " + std::to_string((int)force[k]) + " is not -1, 0 or 1");
+  return PGO_OK;
+}
+
+int joint_not_pd(const std::string& fn, int k) {
+  return fail(PGO_ERR_NUMERIC, fn + ": the pivot I + L'ML of candidate " + std::to_string(k) + " is not positive definite (P is indefinite or not finite)");
+}
+
+// pgo_edge_gate (jc == nullptr) and pgo_edge_gate_joint: one code path, one pass plan
+int gate_call(const char* name, pgo_t* h, int32_t n, const int32_t* ia, const int32_t* ib, const double* meas_xyt, const double* info6_or_null,
+              const pgo_covariance_options* opt_or_null, pgo_edge_gate_result* out, pgo_covariance_report* report, const JointCall* jc) {
   const double t0 = wall_s();
-  if (!h) return fail(PGO_ERR_INVALID_ARG, "pgo_edge_gate: null handle");
-  if (n < 0 || (n > 0 && (!ia || !ib || !meas_xyt || !out))) return fail(PGO_ERR_INVALID_ARG, "pgo_edge_gate: bad argument");
-  Session S(h, "pgo_edge_gate");
+  const std::string fn(name);
+  if (!h) return fail(PGO_ERR_INVALID_ARG, fn + ": null handle");
+  if (n < 0 || (n > 0 && (!ia || !ib || !meas_xyt || !out))) return fail(PGO_ERR_INVALID_ARG, fn + ": bad argument");
+  Session S(h, name);
   PGOC(S.check(opt_or_null));
   const int64_t N = S.N;
   for (int32_t k = 0; k < n; ++k) {
     if (ia[k] < 0 || ia[k] >= N || ib[k] < 0 || ib[k] >= N)
-      return fail(PGO_ERR_INVALID_ARG, "pgo_edge_gate: candidate " + std::to_string(k) + " has a pose index out of range");
-    if (ia[k] == ib[k]) return fail(PGO_ERR_INVALID_ARG, "pgo_edge_gate: candidate " + std::to_string(k) + " joins pose " + std::to_string(ia[k]) + " to itself");
-    if (info6_or_null) {
-      const double* w = info6_or_null + 6 * (int64_t)k;
-      double l[6];
-      bool ok = true;
-      for (int c = 0; c < 6; ++c) ok = ok && std::isfinite(w[c]);
-      if (!ok || !pgo::gate_chol3(w, l))
-        return fail(PGO_ERR_INVALID_ARG, "pgo_edge_gate: the information matrix of candidate " + std::to_string(k) + " is not finite and positive definite");
-    }
+      return fail(PGO_ERR_INVALID_ARG, fn + ": candidate " + std::to_string(k) + " has a pose index out of range");
+    if (ia[k] == ib[k]) return fail(PGO_ERR_INVALID_ARG, fn + ": candidate " + std::to_string(k) + " joins pose " + std::to_string(ia[k]) + " to itself");
+    if (info6_or_null && !info6_ok(info6_or_null + 6 * (int64_t)k))
+      return fail(PGO_ERR_INVALID_ARG, fn + ": the information matrix of candidate " + std::to_string(k) + " is not finite and positive definite");
   }
   PGOC(S.need_switches());
   if (report) memset(report, 0, sizeof *report);
@@ -677,6 +712,24 @@ int pgo_edge_gate(pgo_t* h, int32_t n, const int32_t* ia, const int32_t* ib, con
   plan.insert(plan.end(), rest.begin(), rest.end());
   HIPC(hipMemcpyAsync(d_cand, plan.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
   PGOC(h->sync());
+  // the joint gate: C = [J_q Sigma J_p'] over all candidates (zero where a candidate takes no columns), the working state
+  const int64_t W = 3 * (int64_t)n;
+  double *d_C = nullptr, *d_M = nullptr, *d_rho = nullptr;
+  int32_t* d_status = nullptr;
+  int8_t* d_force = nullptr;
+  pgo_gate_joint_result* d_joint = nullptr;
+  if (jc) {
+    PGOC(S.buf.alloc(&d_C, W * W));
+    PGOC(S.buf.alloc(&d_M, W * W));
+    PGOC(S.buf.alloc(&d_rho, W));
+    PGOC(S.buf.alloc(&d_status, n));
+    PGOC(S.buf.alloc(&d_joint, n));
+    if (jc->force) {
+      PGOC(S.buf.alloc(&d_force, n));
+      HIPC(hipMemcpyAsync(d_force, jc->force, (size_t)n, hipMemcpyHostToDevice, h->stream));
+    }
+    HIPC(hipMemsetAsync(d_C, 0, (size_t)(W * W) * sizeof(double), h->stream));
+  }
   const int kpp = S.per_pass();
   if (n_solve > 0) PGOC(S.alloc(3 * std::min<int32_t>(kpp, n_solve)));
   for (int32_t j0 = 0; j0 < n_solve; j0 += kpp) {
@@ -688,6 +741,11 @@ int pgo_edge_gate(pgo_t* h, int32_t n, const int32_t* ia, const int32_t* ib, con
     hipLaunchKernelGGL(dev::k_gate_reduce<>, dim3((unsigned)((k + 63) / 64)), dim3(64), 0, h->stream, k, (const int32_t*)(d_cand + j0), (const dev::GateRec*)rec, (const double*)S.X,
                        S.ld, (const double*)h->scale, (const double*)d_info, d_out);
     PGOC(h->check_launch("k_gate_reduce"));
+    if (jc) {   // the blocks between this pass's candidates and all candidates with columns, from the columns just solved
+      hipLaunchKernelGGL(dev::k_gate_cross<>, dim3((unsigned)(((int64_t)n_solve * k + dev::WG - 1) / dev::WG)), dim3(dev::WG), 0, h->stream, (int)n_solve,
+                         (const int32_t*)d_cand, k, (const int32_t*)(d_cand + j0), (const dev::GateRec*)rec, (const double*)S.X, S.ld, (const double*)h->scale, W, d_C);
+      PGOC(h->check_launch("k_gate_cross"));
+    }
   }
   if (n > n_solve) {
     const int k = n - n_solve;
@@ -696,12 +754,106 @@ int pgo_edge_gate(pgo_t* h, int32_t n, const int32_t* ia, const int32_t* ib, con
     PGOC(h->check_launch("k_gate_reduce"));
   }
   HIPC(hipMemcpyAsync(out, d_out, (size_t)n * sizeof(pgo_edge_gate_result), hipMemcpyDeviceToHost, h->stream));
+  if (jc) {
+    // P = 1/2 (C + C'), then the elimination on it in place.  Shape: one launch per candidate, a grid of workgroups over the
+    // trailing rows (a kernel boundary between two candidates, no barrier across workgroups); the "gate_joint_shape" knob = 0
+    // walks all candidates in ONE launch of one workgroup instead -- measured 1.8 x slower at the cap with everything
+    // accepted ("Joint gate").
+    hipLaunchKernelGGL(dev::k_gate_symmetrise<>, dim3((unsigned)((W * W + dev::WG - 1) / dev::WG)), dim3(dev::WG), 0, h->stream, W, (const double*)d_C, d_M);
+    PGOC(h->check_launch("k_gate_symmetrise"));
+    if (jc->P_full) HIPC(hipMemcpyAsync(jc->P_full, d_M, (size_t)(W * W) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PGOC(h->sync());   // (the copy of P has left before the elimination overwrites it)
+    hipLaunchKernelGGL(dev::k_gate_joint_begin<>, dim3((unsigned)((n + dev::WG - 1) / dev::WG)), dim3(dev::WG), 0, h->stream, (int)n, (const dev::GateRec*)rec, d_rho,
+                       d_status);
+    PGOC(h->check_launch("k_gate_joint_begin"));
+    dev::GateJointArgs A;
+    A.n = n;
+    A.M = d_M;
+    A.rho = d_rho;
+    A.info6 = d_info;
+    A.status = d_status;
+    A.force = d_force;
+    A.chi2_gate = jc->o.chi2_gate;
+    A.min_info_gain = jc->o.min_info_gain;
+    A.joint = d_joint;
+    if (knob("gate_joint_shape") != 0) {
+      for (int32_t k = 0; k < n; ++k) {
+        A.k0 = k;
+        A.k1 = k + 1;
+        const int rows = 3 * (n - 1 - k), per_wg = 3 * (dev::GATE_JOINT_WG / 256);
+        hipLaunchKernelGGL(dev::k_gate_joint_step<>, dim3((unsigned)std::min(std::max(1, (rows + per_wg - 1) / per_wg), 64)), dim3(dev::GATE_JOINT_WG), 0, h->stream, A);
+      }
+    } else {
+      A.k0 = 0;
+      A.k1 = n;
+      hipLaunchKernelGGL(dev::k_gate_joint_step<>, dim3(1), dim3(dev::GATE_JOINT_WG), 0, h->stream, A);
+    }
+    PGOC(h->check_launch("k_gate_joint_step"));
+    HIPC(hipMemcpyAsync(jc->joint, d_joint, (size_t)n * sizeof(pgo_gate_joint_result), hipMemcpyDeviceToHost, h->stream));
+  }
   PGOC(h->sync());
   for (int32_t k = 0; k < n; ++k)
     if (out[k].status == 0 && !(std::isfinite(out[k].chi2_marginal) && std::isfinite(out[k].info_gain)))
-      return fail(PGO_ERR_NUMERIC, "pgo_edge_gate: I + L'PL of candidate " + std::to_string(k) + " is not positive definite");
+      return fail(PGO_ERR_NUMERIC, fn + ": I + L'PL of candidate " + std::to_string(k) + " is not positive definite");
+  if (jc) {
+    for (int32_t k = 0; k < n; ++k)
+      if (jc->joint[k].status == 0 && !(std::isfinite(jc->joint[k].chi2_cond) && std::isfinite(jc->joint[k].info_gain_cond))) return joint_not_pd(fn, k);
+    pgo::gate_joint_summarise(n, jc->joint, jc->sum);
+  }
   S.fill(report, 3 * n_solve, t0);
   return PGO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pgo_edge_gate(pgo_t* h, int32_t n, const int32_t* ia, const int32_t* ib, const double* meas_xyt, const double* info6_or_null,
+                  const pgo_covariance_options* opt_or_null, pgo_edge_gate_result* out, pgo_covariance_report* report) {
+  return gate_call("pgo_edge_gate", h, n, ia, ib, meas_xyt, info6_or_null, opt_or_null, out, report, nullptr);
+}
+
+void pgo_gate_joint_options_default(pgo_gate_joint_options* o) {
+  if (!o) return;
+  o->chi2_gate = 7.814727903251179;
+  o->min_info_gain = 0.0;
+}
+
+int pgo_gate_joint_evaluate(int32_t n, const double* r, const double* P, const double* info6_or_null, const int32_t* status_or_null,
+                            const int8_t* force_or_null, const pgo_gate_joint_options* opt_or_null, pgo_gate_joint_result* joint,
+                            pgo_gate_joint_summary* sum) {
+  const std::string fn = "pgo_gate_joint_evaluate";
+  if (n < 0 || !sum || (n > 0 && (!r || !P || !joint))) return fail(PGO_ERR_INVALID_ARG, fn + ": bad argument");
+  pgo_gate_joint_options o;
+  PGOC(joint_options(fn, n, force_or_null, opt_or_null, &o));
+  for (int32_t k = 0; k < n; ++k) {
+    if (status_or_null && status_or_null[k] != 0 && status_or_null[k] != 1) return fail(PGO_ERR_INVALID_ARG, fn + ": status[" + std::to_string(k) + "] is not 0 or 1");
+    if (info6_or_null && !info6_ok(info6_or_null + 6 * (int64_t)k))
+      return fail(PGO_ERR_INVALID_ARG, fn + ": the information matrix of candidate " + std::to_string(k) + " is not finite and positive definite");
+  }
+  const int64_t W = 3 * (int64_t)n;
+  std::vector<double> rho(r, r + W), M(P, P + W * W), B((size_t)std::max<int64_t>(3 * W, 1));
+  int bad = -1;
+  const int st = pgo::gate_joint_serial(n, rho.data(), M.data(), info6_or_null, status_or_null, force_or_null, o.chi2_gate, o.min_info_gain, joint, B.data(), &bad);
+  if (st != pgo::GATE_OK) return joint_not_pd(fn, bad);
+  pgo::gate_joint_summarise(n, joint, sum);
+  return PGO_OK;
+}
+
+int pgo_edge_gate_joint(pgo_t* h, int32_t n, const int32_t* ia, const int32_t* ib, const double* meas_xyt, const double* info6_or_null,
+                        const int8_t* force_or_null, const pgo_gate_joint_options* jopt_or_null, const pgo_covariance_options* opt_or_null,
+                        pgo_edge_gate_result* out, pgo_gate_joint_result* joint, double* P_full_or_null, pgo_gate_joint_summary* sum,
+                        pgo_covariance_report* report) {
+  const std::string fn = "pgo_edge_gate_joint";
+  if (n < 0 || !sum || (n > 0 && !joint)) return fail(PGO_ERR_INVALID_ARG, fn + ": bad argument");
+  JointCall jc;
+  jc.force = force_or_null;
+  jc.joint = joint;
+  jc.P_full = P_full_or_null;
+  jc.sum = sum;
+  PGOC(joint_options(fn, n, force_or_null, jopt_or_null, &jc.o));
+  memset(sum, 0, sizeof *sum);
+  return gate_call("pgo_edge_gate_joint", h, n, ia, ib, meas_xyt, info6_or_null, opt_or_null, out, report, &jc);
 }
 
 }  // extern "C"
