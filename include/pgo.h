@@ -683,6 +683,86 @@ int pgo_batch_window_solve(pgo_batch_t* b, int32_t n_windows, const int32_t* pro
                            const int32_t* anchor, int32_t max_iters, int32_t commit, double* poses_out,
                            pgo_window_result* results, pgo_iter_record* records_or_null);                           /* [gpu] */
 
+/* ---------------------------------------------------------------- scoring
+ * How good is a result?  Ground truth of the synthetic world, the trajectory error of an estimate against a reference (ATE and
+ * RPE, Sturm et al., "A Benchmark for the Evaluation of RGB-D SLAM Systems", IROS 2012), and what the robust machinery of
+ * METHOD 0 / 1 did to every edge.
+ *
+ * pgo_synth_manhattan_truth: the ground-truth poses of the graph pgo_synth_manhattan(n_poses, *, *, seed) builds, in the frame
+ * of pose 0: x = gx[i] - gx[0], y = gy[i] - gy[0], theta = wrap_pi(gh[i] pi/2) (gh[0] = 0).  The walk is the first consumer of the
+ * generator's PRNG: neither edges_per_pose nor outlier_frac influences it.  The truth is comparable with the dead-reckoned initial
+ * poses, which start at (0, 0, 0), and with any solve that keeps pose 0 constant, without alignment.
+ * PGO_ERR_INVALID_ARG: n_poses < 2, a null pointer.                                                                          */
+int pgo_synth_manhattan_truth(int32_t n_poses, uint64_t seed, double* out_xyt /* N x 3 */);     /* [host] */
+
+/* Trajectory error of an estimate P_i = (p_i, theta_i) against a reference Q_i = (q_i, psi_i), over the COUNTED poses: those with
+ * a non-zero mask byte (caller's numbering), all of them when the mask is NULL.
+ * - ATE.  e_i = R(phi) p_i + t - q_i; ate_rmse = sqrt(mean |e_i|^2), ate_mean = mean |e_i|, ate_max = max |e_i| at pose
+ *   ate_max_pose; rot_rmse / rot_max over |wrap(theta_i + phi - psi_i)|, wrap(a) = atan2(sin a, cos a).
+ * - Alignment.  align = 0: phi = 0, t = 0.  align = 1: the rigid least-squares fit of the estimate onto the reference (Horn,
+ *   no scale): centroids pbar, qbar over the counted poses; a = sum (p_i - pbar).(q_i - qbar), b = sum (p_i - pbar) x (q_i - qbar)
+ *   with the 2-D cross product px qy - py qx; phi = atan2(b, a), 0 when a = b = 0; t = qbar - R(phi) pbar.  The centred sums run in
+ *   a second pass after the centroids (coordinates reach +-250 m at a million poses).  (align_x, align_y, align_phi) = (t, phi).
+ * - RPE over the pairs (i, i + rpe_delta) whose two ends are counted: E_i = (Q_i^-1 Q_{i+d})^-1 (P_i^-1 P_{i+d}) in SE(2),
+ *   trans = |trans(E_i)|, rot = |angle(E_i)| wrapped as above; rpe_trans_rmse, rpe_trans_max (at pair rpe_max_pose = i),
+ *   rpe_rot_rmse, rpe_rot_max.  RPE is invariant to the alignment and is computed on the unaligned poses.  rpe_delta = 0: none.
+ * - Ties of a maximum go to the smallest index.  Nothing counted (no pose / no pair): every double of that group is 0, its index
+ *   -1, and the call returns PGO_OK.
+ * - per_pose (or NULL): n x 2 = (|e_i|, |wrap(theta_i + phi - psi_i)|), 0 for a pose that is not counted.
+ * - A counted pose that is not finite in either trajectory: PGO_ERR_NUMERIC, pgo_last_error names the smallest such pose, the
+ *   outputs are not defined.  A pose that is not counted may hold anything.
+ * - PGO_ERR_INVALID_ARG: a null pointer, n < 1, align outside {0, 1}, rpe_delta < 0.
+ * pgo_trajectory_error_eval is the serial evaluation on the host, in the caller's order.  pgo_trajectory_error scores the
+ * handle's CURRENT poses on the device (csrc/traj_error.h is the one statement of the formulas both run): workgroups of 256
+ * lanes over chunks of PGO_SCORE_POSES_PER_WG poses of the caller's numbering, per-chunk partials folded by one workgroup in
+ * fixed order, no atomics; at most three passes (centroids, centred moments, errors; the last alone for align = 0); one copy-out.
+ * Two calls are bitwise equal, a handle with pose_ordering 1 gives bitwise what one with 0 gives at the same poses, and the
+ * result does not depend on the grid.  It agrees with pgo_trajectory_error_eval up to the association of the sums.  The handle is
+ * left exactly as it was: a following pgo_lm_step gives bitwise the records and poses it gives without the call (the reference
+ * and the mask go through a staging buffer of the handle's own, grown on demand: repeated calls of one size allocate nothing).
+ * PGO_ERR_UNSUPPORTED: a communicator or PGO_FORCE_COLLECTIVES=1, a batched handle.  Nothing changes on error.              */
+#define PGO_SCORE_POSES_PER_WG 512
+typedef struct pgo_traj_options {
+  int32_t align;      /* 0 (default): compare as given; 1: rigid SE(2) least-squares alignment of the estimate onto the reference */
+  int32_t rpe_delta;  /* 1 (default): relative pose error over pairs (i, i + rpe_delta); 0 = none */
+} pgo_traj_options;
+typedef struct pgo_traj_error {
+  int32_t n_poses, n_pairs;            /* counted poses / pairs */
+  int32_t ate_max_pose, rpe_max_pose;  /* caller's numbering; -1 when nothing was counted; ties: the smallest index */
+  double  align_x, align_y, align_phi; /* the transform applied to the estimate (0, 0, 0 for align = 0) */
+  double  ate_rmse, ate_mean, ate_max; /* translation error, metres */
+  double  rot_rmse, rot_max;           /* |wrap(theta_est + phi - theta_ref)| */
+  double  rpe_trans_rmse, rpe_trans_max, rpe_rot_rmse, rpe_rot_max;
+} pgo_traj_error;
+void pgo_traj_options_default(pgo_traj_options*);                                              /* [host] */
+int  pgo_trajectory_error_eval(int32_t n, const double* est_xyt, const double* ref_xyt,
+                               const uint8_t* pose_mask_or_null, const pgo_traj_options* opt_or_null,
+                               pgo_traj_error* out, double* per_pose_or_null /* n x 2: trans, |rot| */); /* [host] */
+int  pgo_trajectory_error(pgo_t* h, const double* ref_xyt /* N x 3, caller's numbering */,
+                          const uint8_t* pose_mask_or_null, const pgo_traj_options* opt_or_null,
+                          pgo_traj_error* out, double* per_pose_or_null);                      /* [gpu] */
+
+/* What the robust machinery did to each edge, METHOD 0 and 1, at the handle's current poses or at poses_or_null: one record per
+ * edge in the caller's edge order.  With e the plain residual (ex, ey, asin(sin delta)) as K1 states it:
+ *   s_plain = |e|^2;  scale = psi = min(1, sqrt(2 phi / (phi + ex^2 + ey^2))) on the edges METHOD 1 applies DCS to (closure and
+ *   bogus), else exactly 1;  s = |scale e|^2;  rho1 = rho'(s) and cost = 1/2 rho(s) of the edge's loss class (pgo_set_losses;
+ *   Huber(huber_delta) by default);  weight = scale^2 rho1 -- what the plain squared residual counts for: weight * s_plain is
+ *   |r|^2 of pgo_eval's r with apply_loss != 0.  The sum of cost over the active edges is pgo_eval's cost.
+ * Inactive edges (pgo_set_active) are computed too, as pgo_edge_chi2 ignores the mask; `active` says which edges count.  A
+ * residual that is not finite gives NaN in every double of that record; it is not a call failure.  One lane per edge, no
+ * reduction: two calls are bitwise equal.  The handle is left exactly as it was.
+ * PGO_ERR_UNSUPPORTED: METHOD 2 (pgo_get_switches is its readout), info_weighting = 1 (the chi2 form of DCS is stated inside K1
+ * only), a communicator or PGO_FORCE_COLLECTIVES=1, a batched handle.  PGO_ERR_INVALID_ARG: a null pointer.                  */
+typedef struct pgo_edge_weight {
+  double  s_plain;  /* |e|^2 of the plain residual (ex, ey, asin(sin delta)), K1's statement */
+  double  scale;    /* DCS factor psi on the edges METHOD 1 applies it to, else 1 */
+  double  rho1;     /* rho'(s) of the block's loss class at s = scale^2 s_plain */
+  double  weight;   /* scale^2 rho1: what the plain squared residual counts for */
+  double  cost;     /* 1/2 rho(s) */
+  int32_t active, _pad;   /* the pgo_set_active mask */
+} pgo_edge_weight;
+int pgo_edge_weights(pgo_t* h, const double* poses_or_null, pgo_edge_weight* out /* E, caller's edge order */);   /* [gpu] */
+
 /* ------------------------------------------------ kernel-level entry points
  * Used by the parity tests and by bench.py's roofline leg: each launches exactly
  * one kind of kernel `reps` times on the handle's stream, brackets the launches
@@ -744,7 +824,9 @@ int pgo_debug_normal_eq(pgo_t* h, double* g_or_null, double* hdiag_or_null);    
  *                        call; any other value >= 0: PGO_ERR_INVALID_ARG from that call; the results are bitwise the same for every width)
  *   "gate_joint_shape"   0 = pgo_edge_gate_joint runs its elimination as ONE launch of one workgroup instead of one launch per
  *                        candidate with a grid of workgroups over the trailing rows (read per call; the results are bitwise the same)
- * Unknown name: PGO_ERR_INVALID_ARG.                                                                              */
+ *   "score_grid"         n > 0 = pgo_trajectory_error launches n workgroups over its chunks instead of one per chunk (read per
+ *                        call; the results are bitwise the same)
+ * Unknown name: PGO_ERR_INVALID_ARG.                                                                      */
 int pgo_debug_set_knob(const char* name, long long value);                        /* [host] */
 /* sharding plan of a graph over `world` ranks: for rank r, rows [lo, hi) and the
  * number of local edges / cut edges.  rows per rank = ceil(N / world) rounded up to a

@@ -24,7 +24,8 @@ __all__ = ["PgoError", "Options", "Summary", "IterRecord", "ReadG2O", "Graph", "
            "HandleInfo", "synth_manhattan", "solve_batch", "shard_plan", "shard_halo", "pose_order", "set_knob", "KernelStats", "EXPORTS", "TERMINATION",
            "CovarianceOptions", "CovarianceReport", "Loss", "LOSS_TYPES", "active_plan", "EdgeGateResult", "gate_evaluate",
            "GateJointOptions", "GateJointResult", "GateJointSummary", "gate_joint_evaluate", "GATE_JOINT_MAX",
-           "window_plan", "WindowResult", "WINDOW_MAX_POSES", "WINDOW_MAX_EDGES", "WINDOW_MAX_ITERS"]
+           "window_plan", "WindowResult", "WINDOW_MAX_POSES", "WINDOW_MAX_EDGES", "WINDOW_MAX_ITERS",
+           "synth_manhattan_truth", "trajectory_error", "TrajOptions", "TrajError", "EdgeWeight", "SCORE_POSES_PER_WG"]
 
 EDGE_ODOMETRY, EDGE_CLOSURE, EDGE_BOGUS = 0, 1, 2
 TERMINATION = {1: "CONVERGENCE_FTOL", 2: "CONVERGENCE_GTOL", 3: "CONVERGENCE_PTOL", 4: "NO_CONVERGENCE",
@@ -53,7 +54,9 @@ EXPORTS = [
     "pgo_gate_evaluate", "pgo_edge_gate",
     "pgo_gate_joint_options_default", "pgo_gate_joint_evaluate", "pgo_edge_gate_joint",
     "pgo_window_plan", "pgo_window_solve", "pgo_batch_window_solve",
+    "pgo_synth_manhattan_truth", "pgo_traj_options_default", "pgo_trajectory_error_eval", "pgo_trajectory_error", "pgo_edge_weights",
 ]
+SCORE_POSES_PER_WG = 512   # PGO_SCORE_POSES_PER_WG
 WINDOW_MAX_POSES, WINDOW_MAX_EDGES, WINDOW_MAX_ITERS = 64, 256, 32   # PGO_WINDOW_MAX_* (include/pgo.h)
 GATE_JOINT_MAX = 256   # PGO_GATE_JOINT_MAX
 LOSS_TYPES = {"trivial": 0, "huber": 1, "softlone": 2, "cauchy": 3, "arctan": 4, "tukey": 5}   # pgo_loss_type
@@ -230,6 +233,37 @@ class WindowResult(C.Structure):
         return d
 
 
+class TrajOptions(C.Structure):
+    """mirror of pgo_traj_options (defaults: pgo_traj_options_default)"""
+    _fields_ = [("align", C.c_int32), ("rpe_delta", C.c_int32)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().pgo_traj_options_default(C.byref(self))
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError("unknown trajectory-error option " + k)
+            setattr(self, k, int(v))
+
+
+class TrajError(C.Structure):
+    """mirror of pgo_traj_error: the result of trajectory_error / Solver.trajectory_error"""
+    _fields_ = [("n_poses", C.c_int32), ("n_pairs", C.c_int32), ("ate_max_pose", C.c_int32), ("rpe_max_pose", C.c_int32),
+                ("align_x", C.c_double), ("align_y", C.c_double), ("align_phi", C.c_double),
+                ("ate_rmse", C.c_double), ("ate_mean", C.c_double), ("ate_max", C.c_double),
+                ("rot_rmse", C.c_double), ("rot_max", C.c_double),
+                ("rpe_trans_rmse", C.c_double), ("rpe_trans_max", C.c_double), ("rpe_rot_rmse", C.c_double), ("rpe_rot_max", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class EdgeWeight(C.Structure):
+    """mirror of pgo_edge_weight: one edge of Solver.edge_weights"""
+    _fields_ = [("s_plain", C.c_double), ("scale", C.c_double), ("rho1", C.c_double), ("weight", C.c_double), ("cost", C.c_double),
+                ("active", C.c_int32), ("_pad", C.c_int32)]
+
+
 _LIB = None
 
 
@@ -354,6 +388,12 @@ def lib():
                                    C.POINTER(IterRecord)]
     L.pgo_batch_window_solve.argtypes = [vp, C.c_int32, ip, ip, ip, ip, ip, ip, C.c_int32, C.c_int32, dp, C.POINTER(WindowResult),
                                          C.POINTER(IterRecord)]
+    L.pgo_synth_manhattan_truth.argtypes = [C.c_int32, C.c_uint64, dp]
+    L.pgo_traj_options_default.argtypes = [C.POINTER(TrajOptions)]
+    L.pgo_traj_options_default.restype = None
+    L.pgo_trajectory_error_eval.argtypes = [C.c_int32, dp, dp, bp, C.POINTER(TrajOptions), C.POINTER(TrajError), dp]
+    L.pgo_trajectory_error.argtypes = [vp, dp, bp, C.POINTER(TrajOptions), C.POINTER(TrajError), dp]
+    L.pgo_edge_weights.argtypes = [vp, dp, C.POINTER(EdgeWeight)]
     _LIB = L
     return L
 
@@ -501,6 +541,35 @@ def synth_manhattan(n_poses: int, edges_per_pose: float = 4.0, outlier_frac: flo
     h = C.c_void_p()
     _check(lib().pgo_synth_manhattan(n_poses, edges_per_pose, outlier_frac, seed, C.byref(h)))
     return Graph(h)
+
+
+def synth_manhattan_truth(n_poses: int, seed: int = 20260410):
+    """pgo_synth_manhattan_truth (host only): the (n, 3) ground-truth poses of synth_manhattan(n_poses, *, *, seed), in the frame
+    of pose 0 -- comparable with the graph's dead-reckoned poses and with any solve that keeps pose 0 constant"""
+    out = np.zeros((max(int(n_poses), 0), 3))
+    _check(lib().pgo_synth_manhattan_truth(n_poses, seed, _dp(out)))
+    return out
+
+
+def _traj_call(fn, head, n, ref, mask, align, rpe_delta, per_pose):
+    ref = np.ascontiguousarray(ref, np.float64).reshape(-1, 3)
+    if len(ref) != n:
+        raise ValueError(f"trajectory_error: the reference has {len(ref)} poses, the estimate {n}")
+    m = _mask(mask, n, "mask")
+    o = TrajOptions(align=int(align), rpe_delta=int(rpe_delta))
+    out = TrajError()
+    pp = np.zeros((n, 2)) if per_pose else None
+    _check(fn(*head, _dp(ref), _bp(m) if m is not None else None, C.byref(o), C.byref(out), _dp(pp)))
+    return (out.as_dict(), pp) if per_pose else out.as_dict()
+
+
+def trajectory_error(est, ref, mask=None, align=False, rpe_delta=1, per_pose=False):
+    """pgo_trajectory_error_eval (host only): ATE / RPE of the (n, 3) estimate against the reference over the poses whose
+    mask entry is truthy (None: all).  align=True fits the estimate onto the reference first (rigid, no scale); RPE runs over
+    the pairs (i, i + rpe_delta), 0 = none.  Returns the dict of TrajError (and the (n, 2) per-pose array (trans, |rot|) with
+    per_pose=True)."""
+    est = np.ascontiguousarray(est, np.float64).reshape(-1, 3)
+    return _traj_call(lib().pgo_trajectory_error_eval, (len(est), _dp(est)), len(est), ref, mask, align, rpe_delta, per_pose)
 
 
 def shard_plan(n_poses, ia, ib, world, rank, row_align=1):
@@ -839,6 +908,21 @@ class Solver:
         s = Summary()
         _check(lib().pgo_solve(self._h, C.byref(s)))
         return s
+
+    def trajectory_error(self, ref, mask=None, align=False, rpe_delta=1, per_pose=False):
+        """pgo_trajectory_error: the handle's current poses scored against the (N, 3) reference on the device; arguments and
+        result as trajectory_error.  The handle is left as it was (it may run between lm_step slices)."""
+        return _traj_call(lib().pgo_trajectory_error, (self._h,), self.n_poses, ref, mask, align, rpe_delta, per_pose)
+
+    def edge_weights(self, poses=None):
+        """pgo_edge_weights (METHOD 0 / 1): what DCS and the loss did to each edge at the current poses (or at `poses`) -- a
+        structured array over the edges with the fields of EdgeWeight: s_plain, scale, rho1, weight, cost, active"""
+        p = np.ascontiguousarray(poses, np.float64) if poses is not None else None
+        if p is not None and p.size != 3 * self.n_poses:
+            raise ValueError("edge_weights: poses must be (n_poses, 3)")
+        res = (EdgeWeight * max(self.n_edges, 1))()
+        _check(lib().pgo_edge_weights(self._h, _dp(p), res))
+        return np.ctypeslib.as_array(res)[:self.n_edges].copy()
 
     def lm_begin(self):
         _check(lib().pgo_lm_begin(self._h))

@@ -190,13 +190,14 @@ static inline double wrap_pi(double a) {
   return a;
 }
 
-static int synth_manhattan(int32_t N, double edges_per_pose, double outlier_frac, uint64_t seed, Graph* g) {
-  if (N < 2) return fail(PGO_ERR_INVALID_ARG, "synth: need at least 2 poses");
-  SplitMix64 rng(seed);
-  const double sig_xy = 0.02, sig_t = 0.01;
-  // ground truth on the integer grid; heading in quarter turns
-  std::vector<int32_t> gx(N), gy(N), gh(N);
-  static const int dxs[4] = {1, 0, -1, 0}, dys[4] = {0, 1, 0, -1};
+static const int dxs[4] = {1, 0, -1, 0}, dys[4] = {0, 1, 0, -1};   // unit step of a heading, in quarter turns
+
+// The walk of the synthetic Manhattan world: ground truth on the integer grid, heading in quarter turns.  It is the FIRST
+// consumer of the generator's PRNG (synth_manhattan goes on with the same stream; pgo_synth_manhattan_truth stops here).
+static void synth_walk(int32_t N, SplitMix64& rng, std::vector<int32_t>& gx, std::vector<int32_t>& gy, std::vector<int32_t>& gh) {
+  gx.resize(N);
+  gy.resize(N);
+  gh.resize(N);
   // The world is a bounded square (a finite building): side ~ sqrt(N / 4), so that a cell is
   // revisited about four times and every pose finds earlier poses next to it.
   const int32_t side = std::max<int32_t>(8, (int32_t)std::ceil(std::sqrt((double)N / 4.0)));
@@ -224,6 +225,14 @@ static int synth_manhattan(int32_t N, double edges_per_pose, double outlier_frac
     }
     gh[i + 1] = h;
   }
+}
+
+static int synth_manhattan(int32_t N, double edges_per_pose, double outlier_frac, uint64_t seed, Graph* g) {
+  if (N < 2) return fail(PGO_ERR_INVALID_ARG, "synth: need at least 2 poses");
+  SplitMix64 rng(seed);
+  const double sig_xy = 0.02, sig_t = 0.01;
+  std::vector<int32_t> gx, gy, gh;
+  synth_walk(N, rng, gx, gy, gh);
   auto true_rel = [&](int32_t a, int32_t b, double out[3]) {
     double dx = (double)(gx[b] - gx[a]), dy = (double)(gy[b] - gy[a]);
     int ha = gh[a];
@@ -541,6 +550,20 @@ int pgo_write_g2o(const pgo_graph* pg, const char* path) {
   }
   bool bad = ferror(f);
   if (fclose(f) != 0 || bad) return fail(PGO_ERR_IO, std::string("write error on ") + path);
+  return PGO_OK;
+}
+
+int pgo_synth_manhattan_truth(int32_t n_poses, uint64_t seed, double* out_xyt) {
+  if (!out_xyt) return fail(PGO_ERR_INVALID_ARG, "pgo_synth_manhattan_truth: null argument");
+  if (n_poses < 2) return fail(PGO_ERR_INVALID_ARG, "synth: need at least 2 poses");
+  pgo::SplitMix64 rng(seed);
+  std::vector<int32_t> gx, gy, gh;
+  pgo::synth_walk(n_poses, rng, gx, gy, gh);
+  for (int32_t i = 0; i < n_poses; ++i) {   // the frame of pose 0 (gh[0] = 0: no rotation)
+    out_xyt[3 * (size_t)i] = (double)(gx[i] - gx[0]);
+    out_xyt[3 * (size_t)i + 1] = (double)(gy[i] - gy[0]);
+    out_xyt[3 * (size_t)i + 2] = pgo::wrap_pi((double)gh[i] * (M_PI / 2.0));
+  }
   return PGO_OK;
 }
 

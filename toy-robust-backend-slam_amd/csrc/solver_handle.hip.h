@@ -8,6 +8,7 @@
 //   solver_batch.hip    pgo_batch: many independent problems in one handle
 //   solver_abi.hip      the [gpu] part of the C-ABI, test hooks, debug / bench entry points
 //   solver_window.hip   pgo_window_solve: many tiny windows of the graph, one workgroup each (window.hip.h)
+//   solver_score.hip    pgo_trajectory_error, pgo_edge_weights: scoring a solve on the device (score.hip.h, traj_error.h)
 // Every kernel header declares its kernels `static`: a translation unit carries the kernels it launches.
 //
 // Replaces, for DCS-ceres/main.cpp METHOD 0/1 (paths relative to /root/reference/DCS-ceres):
@@ -507,6 +508,16 @@ struct pgo_handle {
   int window_solve(const char* who, int32_t n_windows, const int32_t* pose_ptr, const int32_t* pose_idx, const int32_t* edge_ptr,
                    const int32_t* edge_idx, const int32_t* anchor, int32_t max_iters, int32_t commit, double* poses_out,
                    pgo_window_result* results, pgo_iter_record* records);
+
+  // scoring (pgo_trajectory_error, pgo_edge_weights; solver_score.hip): score_in stages what a call uploads (the reference and
+  // the mask, or the caller's poses), score_work holds the partials and the outputs; both are grown on demand and kept
+  // (win_reserve).  score_perm / score_eorig: device copies of perm and of S.orig_edge, made at the first call that needs them.
+  void *score_in = nullptr, *score_work = nullptr;
+  int64_t score_in_cap = 0, score_work_cap = 0;
+  int32_t *score_perm = nullptr, *score_eorig = nullptr;
+  std::vector<uint8_t> score_host;   // host image of score_in
+  int trajectory_error(const double* ref, const uint8_t* mask, const pgo_traj_options* opt, pgo_traj_error* out, double* per_pose);
+  int edge_weights(const double* poses_or_null, pgo_edge_weight* out);
 
   int create(int32_t N, const double* poses_h, int32_t E, const int32_t* ia, const int32_t* ib, const double* meas,
              const double* info6, const uint8_t* kind);

@@ -1,5 +1,6 @@
 // Command-line front end with the reference's run contract (DCS-ceres/main.cpp:22-40, do_build.sh:10):
 //     ./main DATASET NUM_OUTLIER_LOOPS METHOD [--seed S] [--data DIR] [--save DIR] [--device D] [--precision P]
+//            [--loss NAME[:A]] [--loop-loss NAME[:A]] [--score FILE [--align]]
 // METHOD 0 = baseline, 1 = DCS, 2 = switchable constraints run on the MI355X backend; 3/4 are outside it (exit code 3).
 // Reads DIR/DATASET.g2o (default ../data, as the reference), writes init_/opt_ nodes+edges text files that
 // drawer/plot_results.py consumes (default ../save; unlike the reference the directory is created).
@@ -7,6 +8,7 @@
 
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <iostream>
 #include <string>
 #include <vector>
@@ -39,15 +41,24 @@ int main(int argc, char* argv[]) {
     std::cout << "Usage: " << argv[0] << " DATASET NUM_OUTLIER_LOOPS METHOD [--seed S] [--data DIR] [--save DIR] [--device D]\n"
               << "       [--precision P] [--loss NAME[:A]] [--loop-loss NAME[:A]]  (losses: trivial huber softlone cauchy arctan tukey;\n"
               << "       --loss sets every block's, default huber:0.01; --loop-loss overrides it on closure and bogus blocks)\n"
+              << "       [--score FILE [--align]]  (FILE: reference poses as writePoseGraph_nodes writes them, <index> <x> <y> <theta>; prints\n"
+              << "       the trajectory error of the result against it, --align after a rigid fit; a wrong pose count: exit code 2)\n"
               << "METHOD: 0=baseline, 1=DCS, 2=Switchable (3=Layer, 4=Simple Layer MCTS: not in this backend)\n"
               << "Example: " << argv[0] << " INTEL 50 1\n";
     return -1;
   }
-  std::string base = "../data", save = "../save", loss_spec = "huber:0.01", loop_spec;
+  std::string base = "../data", save = "../save", loss_spec = "huber:0.01", loop_spec, score_file;
   long long seed = -1;
-  int device = 0, precision = 0;
-  for (int i = 4; i + 1 < argc; i += 2) {
-    if (!strcmp(argv[i], "--seed")) seed = atoll(argv[i + 1]);
+  int device = 0, precision = 0, score_align = 0;
+  for (int i = 4; i < argc; i += 2) {
+    if (!strcmp(argv[i], "--align")) {   // (the one option without a value)
+      score_align = 1;
+      --i;
+      continue;
+    }
+    if (i + 1 >= argc) { std::cerr << "option " << argv[i] << " needs a value\n"; return -1; }
+    if (!strcmp(argv[i], "--score")) score_file = argv[i + 1];
+    else if (!strcmp(argv[i], "--seed")) seed = atoll(argv[i + 1]);
     else if (!strcmp(argv[i], "--data")) base = argv[i + 1];
     else if (!strcmp(argv[i], "--save")) save = argv[i + 1];
     else if (!strcmp(argv[i], "--device")) device = atoi(argv[i + 1]);
@@ -117,6 +128,25 @@ int main(int argc, char* argv[]) {
     g2o_manager.writePoseGraph_edges(save + "/opt_edges.txt");
     if (SC_ON) g2o_manager.writePoseGraph_switches(save + "/switches.txt", switch_priors, switch_variables);
     for (double* s : switch_variables) delete s;
+    if (!score_file.empty()) {   // the result (Node::p, optimised in place) against the reference poses of FILE
+      std::ifstream in(score_file);
+      if (!in) throw std::runtime_error("cannot open " + score_file);
+      std::vector<double> ref, est;
+      double idx, x, y, th;
+      while (in >> idx >> x >> y >> th) ref.insert(ref.end(), {x, y, th});
+      const size_t n = g2o_manager.nNodes.size();
+      if (!in.eof() || ref.size() != 3 * n)
+        throw std::runtime_error(score_file + ": " + std::to_string(ref.size() / 3) + " poses read, the graph has " + std::to_string(n));
+      for (Node* nd : g2o_manager.nNodes) est.insert(est.end(), nd->p, nd->p + 3);
+      pgo_traj_options topt;
+      pgo_traj_options_default(&topt);
+      topt.align = score_align;
+      pgo_traj_error te;
+      if (pgo_trajectory_error_eval((int32_t)n, est.data(), ref.data(), nullptr, &topt, &te, nullptr) != PGO_OK)
+        throw std::runtime_error(pgo_last_error());
+      std::cout << "score: ate_rmse " << te.ate_rmse << " ate_max " << te.ate_max << " rot_rmse " << te.rot_rmse << " rpe_trans_rmse "
+                << te.rpe_trans_rmse << " rpe_rot_rmse " << te.rpe_rot_rmse << (score_align ? " (aligned)" : "") << std::endl;
+    }
   } catch (const std::exception& e) {
     std::cerr << "error: " << e.what() << std::endl;
     return 2;
