@@ -763,6 +763,60 @@ typedef struct pgo_edge_weight {
 } pgo_edge_weight;
 int pgo_edge_weights(pgo_t* h, const double* poses_or_null, pgo_edge_weight* out /* E, caller's edge order */);   /* [gpu] */
 
+/* ---------------------------------------------------------------- hierarchical initialisation
+ * Start a large solve near its answer (HOG-Man style): collapse every `stride` consecutive poses onto a key pose, carry every
+ * other edge to the key poses along the odometry chain, solve that small graph exactly with a handle of its own, and spread the
+ * result back over the fine poses.  Caller's numbering throughout; csrc/coarsen.h is the one statement of the operators.
+ * - Sizes.  PGO_COARSEN_MIN_STRIDE <= S <= PGO_COARSEN_MAX_STRIDE; key pose k is fine pose kS, K = ceil(N / S) of them;
+ *   N <= S is PGO_ERR_INVALID_ARG.
+ * - Chain.  The pair (i, i + 1) is joined by its chain edge: the first edge between the two in the caller's order, in either
+ *   orientation -- the odometry chain of the direct solve.  Z_i is its measurement as a motion from i to i + 1 (inverted for an
+ *   edge stored as (i + 1, i)).  A pair without one: PGO_ERR_UNSUPPORTED, pgo_last_error names the first.
+ * - Composites.  C_i = Z_{kS} o ... o Z_{i-1} for kS < i < (k+1)S, C_{kS} = (0, 0, 0) exactly; Cend_k = C_{(k+1)S-1} o Z_{(k+1)S-1}
+ *   for k < K - 1.  Their angles are plain sums, not wrapped.
+ * - Coarse edges, in this order: the K - 1 composites (k, k + 1, Cend_k), kind PGO_EDGE_ODOMETRY, origin -1; then every fine
+ *   edge e = (a, b, m) that is not a chain edge and has a / S != b / S, in the caller's edge order, as
+ *   (a / S, b / S, C_a o m o C_b^-1) with orientation and kind kept and origin = e.  Theta of every coarse measurement is wrapped
+ *   with atan2(sin, cos).  Edges inside one segment are dropped; parallel coarse edges are not merged.
+ * - The coarse graph carries NO information matrices (unit information): propagating covariances through the composition is
+ *   out of scope.  The pgo_set_active mask is ignored, as pgo_edge_chi2 ignores it; origin lets the caller mask the coarse graph.
+ * - A measurement that is not finite: PGO_ERR_NUMERIC, pgo_last_error names the smallest such edge.
+ * - Prolongation of coarse poses X (K x 3), with t = (i - kS) / S: F_i = X_k o C_i; for k < K - 1, B_i = X_{k+1} o Cend_k^-1 o C_i
+ *   and P_i = ((1-t) F_x + t B_x, (1-t) F_y + t B_y, F_th + t wrap(B_th - F_th)); the last segment is forward only, P_i = F_i.
+ *   Key poses come back bitwise: P_{kS} = X_k.
+ * pgo_coarsen_plan is the serial statement on arrays (composites folded left to right): it fills n_coarse_poses, the coarse
+ * lists and, optionally, C (N x 3) and Cend ((K - 1) x 3).  A cap that is too small: the counts are still returned, the lists
+ * are not written, PGO_ERR_INVALID_ARG.  pgo_prolong_eval is the serial prolongation.
+ * pgo_coarsen does the same on a live handle, from the measurements it holds on the device, and returns a graph ready for
+ * pgo_create_from_graph (free it with pgo_graph_free) whose initial poses are the handle's CURRENT poses at the key poses;
+ * origin_or_null (origin_cap entries) receives the origin of every coarse edge, n_coarse_edges_or_null their number (also when
+ * the cap is too small: PGO_ERR_INVALID_ARG then).  One wavefront per segment scans the chain motions under SE(2)
+ * composition (up to 4 consecutive poses per lane folded serially, then a log-step scan over the lanes; the rotation is
+ * carried as (cos, sin), one sincos per motion); one lane per fine edge transports it, kept edges are compacted stably
+ * (per-chunk counts, one workgroup scans them, a second pass writes each edge to its slot); one copy-out.  No floating-point
+ * atomics: two calls are bitwise equal, a handle with pose_ordering 1 gives bitwise what one with 0 gives, and the grid plays
+ * no part; the result agrees with pgo_coarsen_plan up to the association of the compositions.  C and Cend of that stride stay
+ * on the device, in buffers of the handle's own, grown on demand and kept.  The handle is otherwise left exactly as it was: a
+ * following pgo_lm_step gives bitwise the records and poses it gives without the call.
+ * pgo_prolong writes the prolongation of coarse_xyt into the handle's poses on the device, as pgo_set_poses would (a solve
+ * begun with pgo_lm_begin is stale afterwards).  The resolved constant poses (opt.fixed_pose, and under pgo_set_active the
+ * poses it resolved to constant) are not moved.  Without a preceding pgo_coarsen of the same stride: PGO_ERR_INVALID_ARG.  A
+ * coarse pose that is not finite: PGO_ERR_NUMERIC.
+ * PGO_ERR_UNSUPPORTED ([gpu] calls): a communicator, PGO_FORCE_COLLECTIVES=1, a batched handle.  Any METHOD and info_weighting
+ * are fine: these are graph operations.  Nothing changes on error.                                                            */
+#define PGO_COARSEN_MIN_STRIDE 2
+#define PGO_COARSEN_MAX_STRIDE 256
+int pgo_coarsen_plan(int32_t n_poses, int32_t n_edges, const int32_t* ia, const int32_t* ib, const double* meas_xyt,
+                     const uint8_t* kind, int32_t stride, int32_t* n_coarse_poses_out,
+                     int32_t edge_cap, int32_t* coarse_ia, int32_t* coarse_ib, double* coarse_meas /* cap x 3 */,
+                     uint8_t* coarse_kind, int32_t* coarse_origin, int32_t* n_coarse_edges_out,
+                     double* C_or_null /* N x 3 */, double* Cend_or_null /* (K - 1) x 3 */);                     /* [host] */
+int pgo_prolong_eval(int32_t n_poses, int32_t stride, const double* C /* N x 3 */, const double* Cend /* (K - 1) x 3 */,
+                     const double* coarse_xyt /* K x 3 */, double* out_xyt /* N x 3 */);                         /* [host] */
+int pgo_coarsen(pgo_t* h, int32_t stride, pgo_graph** coarse_out, int32_t* origin_or_null, int32_t origin_cap,
+                int32_t* n_coarse_edges_or_null);                                                                /* [gpu] */
+int pgo_prolong(pgo_t* h, int32_t stride, const double* coarse_xyt /* K x 3 */);                                 /* [gpu] */
+
 /* ------------------------------------------------ kernel-level entry points
  * Used by the parity tests and by bench.py's roofline leg: each launches exactly
  * one kind of kernel `reps` times on the handle's stream, brackets the launches
@@ -826,7 +880,9 @@ int pgo_debug_normal_eq(pgo_t* h, double* g_or_null, double* hdiag_or_null);    
  *                        candidate with a grid of workgroups over the trailing rows (read per call; the results are bitwise the same)
  *   "score_grid"         n > 0 = pgo_trajectory_error launches n workgroups over its chunks instead of one per chunk (read per
  *                        call; the results are bitwise the same)
- * Unknown name: PGO_ERR_INVALID_ARG.                                                                      */
+ *   "coarsen_grid"       n > 0 = pgo_coarsen and pgo_prolong launch n workgroups over their segments, chunks and poses instead of
+ *                        one per unit of work (read per call; the results are bitwise the same)
+ * Unknown name: PGO_ERR_INVALID_ARG.                                                                     */
 int pgo_debug_set_knob(const char* name, long long value);                        /* [host] */
 /* sharding plan of a graph over `world` ranks: for rank r, rows [lo, hi) and the
  * number of local edges / cut edges.  rows per rank = ceil(N / world) rounded up to a

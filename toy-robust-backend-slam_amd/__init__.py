@@ -25,7 +25,8 @@ __all__ = ["PgoError", "Options", "Summary", "IterRecord", "ReadG2O", "Graph", "
            "CovarianceOptions", "CovarianceReport", "Loss", "LOSS_TYPES", "active_plan", "EdgeGateResult", "gate_evaluate",
            "GateJointOptions", "GateJointResult", "GateJointSummary", "gate_joint_evaluate", "GATE_JOINT_MAX",
            "window_plan", "WindowResult", "WINDOW_MAX_POSES", "WINDOW_MAX_EDGES", "WINDOW_MAX_ITERS",
-           "synth_manhattan_truth", "trajectory_error", "TrajOptions", "TrajError", "EdgeWeight", "SCORE_POSES_PER_WG"]
+           "synth_manhattan_truth", "trajectory_error", "TrajOptions", "TrajError", "EdgeWeight", "SCORE_POSES_PER_WG",
+           "coarsen_plan", "prolong_eval", "COARSEN_MIN_STRIDE", "COARSEN_MAX_STRIDE"]
 
 EDGE_ODOMETRY, EDGE_CLOSURE, EDGE_BOGUS = 0, 1, 2
 TERMINATION = {1: "CONVERGENCE_FTOL", 2: "CONVERGENCE_GTOL", 3: "CONVERGENCE_PTOL", 4: "NO_CONVERGENCE",
@@ -55,7 +56,9 @@ EXPORTS = [
     "pgo_gate_joint_options_default", "pgo_gate_joint_evaluate", "pgo_edge_gate_joint",
     "pgo_window_plan", "pgo_window_solve", "pgo_batch_window_solve",
     "pgo_synth_manhattan_truth", "pgo_traj_options_default", "pgo_trajectory_error_eval", "pgo_trajectory_error", "pgo_edge_weights",
+    "pgo_coarsen_plan", "pgo_prolong_eval", "pgo_coarsen", "pgo_prolong",
 ]
+COARSEN_MIN_STRIDE, COARSEN_MAX_STRIDE = 2, 256   # PGO_COARSEN_*_STRIDE (include/pgo.h)
 SCORE_POSES_PER_WG = 512   # PGO_SCORE_POSES_PER_WG
 WINDOW_MAX_POSES, WINDOW_MAX_EDGES, WINDOW_MAX_ITERS = 64, 256, 32   # PGO_WINDOW_MAX_* (include/pgo.h)
 GATE_JOINT_MAX = 256   # PGO_GATE_JOINT_MAX
@@ -394,6 +397,10 @@ def lib():
     L.pgo_trajectory_error_eval.argtypes = [C.c_int32, dp, dp, bp, C.POINTER(TrajOptions), C.POINTER(TrajError), dp]
     L.pgo_trajectory_error.argtypes = [vp, dp, bp, C.POINTER(TrajOptions), C.POINTER(TrajError), dp]
     L.pgo_edge_weights.argtypes = [vp, dp, C.POINTER(EdgeWeight)]
+    L.pgo_coarsen_plan.argtypes = [C.c_int32, C.c_int32, ip, ip, dp, bp, C.c_int32, ip, C.c_int32, ip, ip, dp, bp, ip, ip, dp, dp]
+    L.pgo_prolong_eval.argtypes = [C.c_int32, C.c_int32, dp, dp, dp, dp]
+    L.pgo_coarsen.argtypes = [vp, C.c_int32, C.POINTER(vp), ip, C.c_int32, ip]
+    L.pgo_prolong.argtypes = [vp, C.c_int32, dp]
     _LIB = L
     return L
 
@@ -629,6 +636,56 @@ def window_plan(n_poses, ia, ib, kind, focus_edges, radius, pose_cap=None, edge_
             e.n_poses, e.n_edges = npo.value, neo.value
             raise
     return po[:npo.value].copy(), eo[:neo.value].copy(), an.value
+
+
+def coarsen_plan(n_poses, ia, ib, meas, kind, stride, edge_cap=None, want_composites=True):
+    """pgo_coarsen_plan (host only), the serial statement of Solver.coarsen: key pose k = fine pose k * stride, the K - 1
+    composites of the odometry chain, then every other edge with its ends in two segments carried to the key poses.
+    Returns a dict: n_poses (K), ia, ib, meas (n, 3), kind, origin (-1 for a composite, else the fine edge) and, with
+    want_composites, C (n_poses, 3) and Cend (K - 1, 3) -- what prolong_eval takes.  edge_cap (default: no limit): a coarse
+    graph above it raises PgoError, whose n_poses / n_edges attributes carry the counts."""
+    ia = np.ascontiguousarray(ia, np.int32)
+    ib = np.ascontiguousarray(ib, np.int32)
+    meas = np.ascontiguousarray(meas, np.float64).reshape(-1, 3)
+    kind = np.ascontiguousarray(kind, np.uint8)
+    if not (len(ia) == len(ib) == len(kind) == len(meas)):
+        raise ValueError("coarsen_plan: ia, ib, meas and kind must have one entry per edge")
+    cap = len(ia) if edge_cap is None else int(edge_cap)
+    m = max(cap, 1)
+    cia, cib, cm, ck, co = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros((m, 3)), np.zeros(m, np.uint8), np.zeros(m, np.int32)
+    nK, nE = C.c_int32(-1), C.c_int32(-1)
+    Cc = np.zeros((max(int(n_poses), 1), 3)) if want_composites else None
+    Ce = np.zeros((max(int(n_poses), 1), 3)) if want_composites else None
+    st = lib().pgo_coarsen_plan(n_poses, len(ia), _ip(ia), _ip(ib), _dp(meas), _bp(kind), int(stride), C.byref(nK), cap, _ip(cia),
+                                _ip(cib), _dp(cm), _bp(ck), _ip(co), C.byref(nE), _dp(Cc), _dp(Ce))
+    if st != 0:
+        try:
+            _check(st)
+        except PgoError as e:
+            e.n_poses, e.n_edges = nK.value, nE.value
+            raise
+    n, K = nE.value, nK.value
+    out = {"n_poses": K, "ia": cia[:n].copy(), "ib": cib[:n].copy(), "meas": cm[:n].copy(), "kind": ck[:n].copy(),
+           "origin": co[:n].copy()}
+    if want_composites:
+        out["C"], out["Cend"] = Cc[:int(n_poses)], Ce[:K - 1].copy()
+    return out
+
+
+def prolong_eval(n_poses, stride, C_, Cend, coarse_poses):
+    """pgo_prolong_eval (host only): the coarse poses (K, 3) spread over the fine poses with the composites of coarsen_plan;
+    key poses come back bitwise"""
+    Cc = np.ascontiguousarray(C_, np.float64).reshape(-1, 3)
+    Ce = np.ascontiguousarray(Cend, np.float64).reshape(-1, 3)
+    X = np.ascontiguousarray(coarse_poses, np.float64).reshape(-1, 3)
+    n, s = int(n_poses), int(stride)
+    if COARSEN_MIN_STRIDE <= s <= COARSEN_MAX_STRIDE and n > s:   # (sizes the library refuses are left to it)
+        K = (n + s - 1) // s
+        if len(Cc) != n or len(Ce) != K - 1 or len(X) != K:
+            raise ValueError(f"prolong_eval: C must be ({n}, 3), Cend ({K - 1}, 3) and the coarse poses ({K}, 3)")
+    out = np.zeros((max(n, 0), 3))
+    _check(lib().pgo_prolong_eval(n, s, _dp(Cc), _dp(Ce), _dp(X), _dp(out)))
+    return out
 
 
 def _window_args(windows, with_problem):
@@ -923,6 +980,44 @@ class Solver:
         res = (EdgeWeight * max(self.n_edges, 1))()
         _check(lib().pgo_edge_weights(self._h, _dp(p), res))
         return np.ctypeslib.as_array(res)[:self.n_edges].copy()
+
+    def coarsen(self, stride: int):
+        """pgo_coarsen: the coarse graph of the handle's measurements at `stride` (see coarsen_plan), with the handle's current
+        poses at the key poses as its initial poses.  Returns (Graph, origin): origin[e] = the fine edge behind coarse edge e,
+        -1 for a composite of the odometry chain.  The handle keeps the composites of this stride for prolong and is
+        otherwise left as it was."""
+        g = C.c_void_p()
+        origin = np.zeros(max(self.n_edges, 1), np.int32)   # (a coarse graph never has more edges than the fine one)
+        n = C.c_int32(-1)
+        _check(lib().pgo_coarsen(self._h, int(stride), C.byref(g), _ip(origin), self.n_edges, C.byref(n)))
+        return Graph(g), origin[:n.value].copy()
+
+    def prolong(self, stride: int, coarse_poses):
+        """pgo_prolong: the coarse poses (K, 3) spread over the handle's poses on the device along the composites that
+        coarsen(stride) left; constant poses are not moved.  A solve begun with lm_begin is stale afterwards."""
+        X = np.ascontiguousarray(coarse_poses, np.float64).reshape(-1, 3)
+        s = int(stride)
+        if s >= 1 and len(X) != (self.n_poses + s - 1) // s:
+            raise ValueError(f"prolong: {len(X)} coarse poses, expected {(self.n_poses + s - 1) // s}")
+        _check(lib().pgo_prolong(self._h, s, _dp(X)))
+
+    def initialize_hierarchical(self, stride: int, coarse_options: "Options | None" = None, device: int = 0) -> Summary:
+        """coarsen -> a solver on the coarse graph -> solve -> prolong: the handle's poses start the fine solve near the answer
+        of the coarse one.  coarse_options (default: the handle's method, pcg_rtol 1e-10 -- the exact mode --, everything else
+        left to the library; a fixed pose that is a key pose stays the fixed pose).  Returns the coarse solve's Summary."""
+        s = int(stride)
+        graph, _ = self.coarsen(s)
+        if coarse_options is None:
+            f = int(self.options.fixed_pose)
+            coarse_options = Options(method=int(self.options.method), pcg_rtol=1e-10,
+                                     fixed_pose=(f if f < 0 else (f // s if f % s == 0 else 0)))
+        coarse = Solver(graph, coarse_options, device=device)
+        try:
+            summary = coarse.solve()
+            self.prolong(s, coarse.poses())
+        finally:
+            coarse.close()
+        return summary
 
     def lm_begin(self):
         _check(lib().pgo_lm_begin(self._h))

@@ -97,6 +97,20 @@ constexpr int ORDER_SEGMENT = 64;
 int cached_pose_order(int32_t n_poses, int32_t n_edges, const int32_t* ia, const int32_t* ib, int32_t segment,
                       std::vector<int32_t>* perm);
 
+// The odometry chain of a graph (the direct solve's tridiagonal part, the composites of pgo_coarsen): chain[i] = the first edge,
+// in the order given, that joins poses i and i + 1 in either orientation; -1 where there is none (always at i = N - 1).
+// Returns the first i < N - 1 without one, or -1.
+inline int32_t pick_chain_edges(int32_t n_poses, int64_t n_edges, const int32_t* ia, const int32_t* ib, std::vector<int32_t>* chain) {
+  chain->assign((size_t)(n_poses > 0 ? n_poses : 0), -1);
+  for (int64_t e = 0; e < n_edges; ++e) {
+    const int32_t lo_p = ia[e] < ib[e] ? ia[e] : ib[e], hi_p = ia[e] < ib[e] ? ib[e] : ia[e];
+    if (hi_p == lo_p + 1 && (*chain)[lo_p] < 0) (*chain)[lo_p] = (int32_t)e;
+  }
+  for (int32_t i = 0; i + 1 < n_poses; ++i)
+    if ((*chain)[i] < 0) return i;
+  return -1;
+}
+
 // poses per block of the block-Jacobi preconditioner for an option value (0 = auto)
 inline int resolve_block_poses(int opt_value, int32_t n_poses) {
   int b = opt_value;

@@ -1,0 +1,285 @@
+// Hierarchical initialisation (include/pgo.h, "hierarchical initialisation"): pgo_coarsen and pgo_prolong -- the host halves --
+// and the serial host statement of the same operators, pgo_coarsen_plan and pgo_prolong_eval (coarsen.h).  The measurements stay
+// where they are, in the handle's local edge order; the host builds, once per handle, the tables that let the kernels of
+// coarsen.hip.h walk the caller's numbering, and one copy-out ends pgo_coarsen.  pgo_coarsen touches neither the LM state, the
+// record buffer nor the poses; pgo_prolong writes the poses as pgo_set_poses does.
+#include "solver_handle.hip.h"
+#include "coarsen.hip.h"
+
+namespace {
+int64_t up16(int64_t b) { return (b + 15) / 16 * 16; }
+
+int check_sizes(const std::string& who, int64_t N, int32_t stride) {
+  if (stride < PGO_COARSEN_MIN_STRIDE || stride > PGO_COARSEN_MAX_STRIDE)
+    return fail(PGO_ERR_INVALID_ARG, who + ": stride must be " + std::to_string(PGO_COARSEN_MIN_STRIDE) + ".." + std::to_string(PGO_COARSEN_MAX_STRIDE));
+  if (N <= stride) return fail(PGO_ERR_INVALID_ARG, who + ": " + std::to_string(N) + " poses give one key pose at stride " + std::to_string(stride) + " (n_poses must exceed the stride)");
+  return PGO_OK;
+}
+int no_chain(const std::string& who, int32_t gap) {
+  return fail(PGO_ERR_UNSUPPORTED, who + ": poses " + std::to_string(gap) + " and " + std::to_string(gap + 1) + " are not joined by an edge");
+}
+int not_finite(const std::string& who, int64_t e) {
+  return fail(PGO_ERR_NUMERIC, who + ": the measurement of edge " + std::to_string(e) + " is not finite");
+}
+// is caller's edge e kept on the coarse graph?  (not a chain edge, ends in two segments)
+inline bool kept(const std::vector<int32_t>& chain, const int32_t* ia, const int32_t* ib, int64_t e, int32_t S) {
+  const int32_t lo_p = std::min(ia[e], ib[e]);
+  if (std::max(ia[e], ib[e]) == lo_p + 1 && chain[lo_p] == (int32_t)e) return false;
+  return ia[e] / S != ib[e] / S;
+}
+}  // namespace
+
+// the tables in the caller's numbering, once per handle
+int pgo_handle::coarsen_tables(const char* who) {
+  if (cs_ready) return PGO_OK;
+  const int64_t N = S.n_poses, EL = S.n_edges_local, E = n_edges_total;   // (one rank: every edge is local)
+  if (EL != E) return fail(PGO_ERR_UNSUPPORTED, std::string(who) + ": one rank only");
+  std::vector<int32_t> inv;   // internal position -> caller's pose
+  if (!perm.empty()) {
+    inv.resize((size_t)N);
+    for (int64_t i = 0; i < N; ++i) inv[perm[i]] = (int32_t)i;
+  }
+  std::vector<int32_t> ea((size_t)E), eb((size_t)E), loc((size_t)E), chain;
+  std::vector<uint8_t> kd((size_t)E);
+  int64_t bad = -1;
+  for (int64_t k = 0; k < EL; ++k) {
+    const int64_t e = S.orig_edge[k];
+    ea[e] = inv.empty() ? S.ia[k] : inv[S.ia[k]];
+    eb[e] = inv.empty() ? S.ib[k] : inv[S.ib[k]];
+    loc[e] = (int32_t)k;
+    kd[e] = kind_local[k];
+    if (!pgo::coarsen_finite3(S.mx[k], S.my[k], S.mt[k]) && (bad < 0 || e < bad)) bad = e;
+  }
+  if (bad >= 0) return not_finite(who, bad);
+  const int32_t gap = pgo::pick_chain_edges((int32_t)N, E, ea.data(), eb.data(), &chain);
+  if (gap >= 0) return no_chain(who, gap);
+  std::vector<int32_t> tab((size_t)(N + 3 * E) + (size_t)((E + 3) / 4), 0);
+  for (int64_t i = 0; i + 1 < N; ++i) {
+    const int32_t e = chain[i];
+    tab[i] = (loc[e] << 1) | (ea[e] != (int32_t)i ? 1 : 0);
+    loc[e] = -1;
+  }
+  memcpy(tab.data() + N, ea.data(), (size_t)E * 4);
+  memcpy(tab.data() + N + E, eb.data(), (size_t)E * 4);
+  memcpy(tab.data() + N + 2 * E, loc.data(), (size_t)E * 4);
+  memcpy(tab.data() + N + 3 * E, kd.data(), (size_t)E);
+  if (!cs_tab) PGOC(dalloc(&cs_tab, (int64_t)tab.size()));
+  if (!perm.empty() && !score_perm) {
+    PGOC(dalloc(&score_perm, N));
+    PGOC(upload(score_perm, perm));
+  }
+  PGOC(upload(cs_tab, tab));
+  PGOC(sync());   // (`tab` dies with this scope)
+  cs_ea_h.swap(ea);
+  cs_eb_h.swap(eb);
+  cs_loc_h.swap(loc);
+  cs_ready = true;
+  return PGO_OK;
+}
+
+int pgo_handle::coarsen(int32_t stride, pgo_graph** coarse_out, int32_t* origin, int32_t origin_cap, int32_t* n_coarse_edges) {
+  const char* who = "pgo_coarsen";
+  if (comm || force_collectives) return fail(PGO_ERR_UNSUPPORTED, std::string(who) + ": one rank without a communicator only");
+  if (batch_mode) return fail(PGO_ERR_UNSUPPORTED, std::string(who) + ": not on a batched handle");
+  if (!coarse_out) return fail(PGO_ERR_INVALID_ARG, std::string(who) + ": null pointer");
+  const int64_t N = S.n_poses, E = n_edges_total;
+  PGOC(check_sizes(who, N, stride));
+  const long long grid_knob = knob("coarsen_grid");
+  HIPC(hipSetDevice(device));
+  PGOC(coarsen_tables(who));
+  const int64_t K = (N + stride - 1) / stride;
+  int64_t Ec = K - 1;
+  for (int64_t e = 0; e < E; ++e) Ec += cs_loc_h[e] >= 0 && cs_ea_h[e] / stride != cs_eb_h[e] / stride;
+  if (n_coarse_edges) *n_coarse_edges = (int32_t)Ec;
+  if (origin && origin_cap < Ec)
+    return fail(PGO_ERR_INVALID_ARG, std::string(who) + ": the coarse graph has " + std::to_string(Ec) + " edges, origin holds " + std::to_string(origin_cap));
+  // ---- buffers, before anything is enqueued: comp = C | Cend;  work = cnt | off | key poses | meas | ia | ib | origin | kind
+  const int64_t nc = (E + dev::COARSEN_CHUNK - 1) / dev::COARSEN_CHUNK;
+  const int64_t c_end = 3 * N * 8, c_all = c_end + 3 * (K - 1) * 8;
+  const int64_t w_cnt = 0, w_off = w_cnt + nc * 4, w_key = up16(w_off + nc * 4), w_meas = w_key + 3 * K * 8, w_ia = w_meas + 3 * Ec * 8,
+                w_ib = w_ia + Ec * 4, w_org = w_ib + Ec * 4, w_kind = w_org + Ec * 4, w_all = w_kind + up16(Ec);
+  PGOC(win_reserve(&cs_comp, &cs_comp_cap, c_all));
+  PGOC(win_reserve(&cs_work, &cs_work_cap, w_all));
+  std::unique_ptr<pgo_graph> G(new pgo_graph);
+  cs_host.resize((size_t)(w_all - w_key));
+  cs_stride = 0;   // (C and Cend are being rewritten)
+  char* wk = static_cast<char*>(cs_work);
+  dev::CoarsenArgs A;
+  A.mx = e_mx;
+  A.my = e_my;
+  A.mt = e_mt;
+  A.poses = poses;
+  A.perm = perm.empty() ? nullptr : score_perm;
+  A.chain = cs_tab;
+  A.ea = cs_tab + N;
+  A.eb = cs_tab + N + E;
+  A.eloc = cs_tab + N + 2 * E;
+  A.ekind = reinterpret_cast<const uint8_t*>(cs_tab + N + 3 * E);
+  A.n = (int32_t)N;
+  A.n_edges = (int32_t)E;
+  A.stride = stride;
+  A.n_key = (int32_t)K;
+  A.n_chunks = (int32_t)nc;
+  A._pad = 0;
+  A.C = reinterpret_cast<double*>(cs_comp);
+  A.Cend = reinterpret_cast<double*>(static_cast<char*>(cs_comp) + c_end);
+  A.cnt = reinterpret_cast<int32_t*>(wk + w_cnt);
+  A.off = reinterpret_cast<int32_t*>(wk + w_off);
+  A.o_key = reinterpret_cast<double*>(wk + w_key);
+  A.o_meas = reinterpret_cast<double*>(wk + w_meas);
+  A.o_ia = reinterpret_cast<int32_t*>(wk + w_ia);
+  A.o_ib = reinterpret_cast<int32_t*>(wk + w_ib);
+  A.o_origin = reinterpret_cast<int32_t*>(wk + w_org);
+  A.o_kind = reinterpret_cast<uint8_t*>(wk + w_kind);
+  auto grid_for = [&](int64_t units) { return (int)(grid_knob > 0 ? std::min<long long>(grid_knob, 65535) : std::min<int64_t>(std::max<int64_t>(units, 1), 65535)); };
+  const int g_seg = grid_for((K + dev::WG / 64 - 1) / (dev::WG / 64)), g_chunk = grid_for(nc);
+  switch ((stride + 63) / 64) {
+    case 1: hipLaunchKernelGGL(dev::k_chain_compose<1>, dim3(g_seg), dim3(dev::WG), 0, stream, A); break;
+    case 2: hipLaunchKernelGGL(dev::k_chain_compose<2>, dim3(g_seg), dim3(dev::WG), 0, stream, A); break;
+    case 3: hipLaunchKernelGGL(dev::k_chain_compose<3>, dim3(g_seg), dim3(dev::WG), 0, stream, A); break;
+    default: hipLaunchKernelGGL(dev::k_chain_compose<4>, dim3(g_seg), dim3(dev::WG), 0, stream, A); break;
+  }
+  PGOC(check_launch("k_chain_compose"));
+  hipLaunchKernelGGL(dev::k_coarsen_count<>, dim3(g_chunk), dim3(dev::WG), 0, stream, A);
+  PGOC(check_launch("k_coarsen_count"));
+  hipLaunchKernelGGL(dev::k_coarsen_scan<>, dim3(1), dim3(dev::WG), 0, stream, A);
+  PGOC(check_launch("k_coarsen_scan"));
+  hipLaunchKernelGGL(dev::k_coarsen_edges<>, dim3(g_chunk), dim3(dev::WG), 0, stream, A);
+  PGOC(check_launch("k_coarsen_edges"));
+  // ---- one copy-out
+  HIPC(hipMemcpyAsync(cs_host.data(), wk + w_key, (size_t)(w_all - w_key), hipMemcpyDeviceToHost, stream));
+  PGOC(sync());
+  cs_stride = stride;
+  const char* hb = reinterpret_cast<const char*>(cs_host.data()) - w_key;
+  pgo::Graph& g = G->g;
+  g.pose_id.resize((size_t)K);
+  for (int64_t k = 0; k < K; ++k) g.pose_id[k] = (int32_t)k;
+  const double* hk = reinterpret_cast<const double*>(hb + w_key);
+  const double* hm = reinterpret_cast<const double*>(hb + w_meas);
+  const int32_t *ha = reinterpret_cast<const int32_t*>(hb + w_ia), *hbb = reinterpret_cast<const int32_t*>(hb + w_ib),
+                *ho = reinterpret_cast<const int32_t*>(hb + w_org);
+  const uint8_t* hkd = reinterpret_cast<const uint8_t*>(hb + w_kind);
+  g.pose.assign(hk, hk + 3 * K);
+  g.ea.assign(ha, ha + Ec);
+  g.eb.assign(hbb, hbb + Ec);
+  g.meas.assign(hm, hm + 3 * Ec);
+  g.kind.assign(hkd, hkd + Ec);
+  g.info.resize((size_t)(6 * Ec));   // (unit information: covariances are not propagated through the composition)
+  for (int64_t e = 0; e < Ec; ++e) {
+    double* q = &g.info[(size_t)(6 * e)];
+    q[0] = q[3] = q[5] = 1.0;
+    q[1] = q[2] = q[4] = 0.0;
+    g.n_kind[g.kind[e] <= 2 ? g.kind[e] : 2]++;
+  }
+  if (origin) memcpy(origin, ho, (size_t)Ec * 4);
+  *coarse_out = G.release();
+  return PGO_OK;
+}
+
+int pgo_handle::prolong(int32_t stride, const double* X) {
+  const char* who = "pgo_prolong";
+  if (comm || force_collectives) return fail(PGO_ERR_UNSUPPORTED, std::string(who) + ": one rank without a communicator only");
+  if (batch_mode) return fail(PGO_ERR_UNSUPPORTED, std::string(who) + ": not on a batched handle");
+  if (!X) return fail(PGO_ERR_INVALID_ARG, std::string(who) + ": null pointer");
+  const int64_t N = S.n_poses;
+  PGOC(check_sizes(who, N, stride));
+  if (cs_stride != stride)
+    return fail(PGO_ERR_INVALID_ARG, std::string(who) + ": no composites of stride " + std::to_string(stride) + " (call pgo_coarsen with this stride first)");
+  const int64_t K = (N + stride - 1) / stride;
+  for (int64_t k = 0; k < K; ++k)
+    if (!pgo::coarsen_finite3(X[3 * k], X[3 * k + 1], X[3 * k + 2]))
+      return fail(PGO_ERR_NUMERIC, std::string(who) + ": coarse pose " + std::to_string(k) + " is not finite");
+  const long long grid_knob = knob("coarsen_grid");
+  HIPC(hipSetDevice(device));
+  PGOC(win_reserve(&cs_work, &cs_work_cap, 3 * K * 8));
+  HIPC(hipMemcpyAsync(cs_work, X, (size_t)(3 * K * 8), hipMemcpyHostToDevice, stream));
+  dev::ProlongArgs A;
+  A.X = static_cast<const double*>(cs_work);
+  A.C = static_cast<const double*>(cs_comp);
+  A.Cend = reinterpret_cast<const double*>(static_cast<char*>(cs_comp) + 3 * N * 8);
+  A.perm = perm.empty() ? nullptr : score_perm;
+  A.constant = fixed_mask;
+  A.poses = poses;
+  A.n = (int32_t)N;
+  A.stride = stride;
+  A.n_key = (int32_t)K;
+  A.fixed_internal = fixed_internal;
+  const int grid = (int)(grid_knob > 0 ? std::min<long long>(grid_knob, 65535) : std::min<int64_t>((N + dev::WG - 1) / dev::WG, 65535));
+  hipLaunchKernelGGL(dev::k_prolong<>, dim3(grid), dim3(dev::WG), 0, stream, A);
+  PGOC(check_launch("k_prolong"));
+  lin_valid = false;   // as pgo_set_poses: the running solve (if any) is stale
+  lm_active = false;
+  return sync();   // (the caller's X may die after the call)
+}
+
+extern "C" {
+
+int pgo_coarsen_plan(int32_t n_poses, int32_t n_edges, const int32_t* ia, const int32_t* ib, const double* meas, const uint8_t* kind,
+                     int32_t stride, int32_t* n_coarse_poses, int32_t edge_cap, int32_t* cia, int32_t* cib, double* cmeas,
+                     uint8_t* ckind, int32_t* corigin, int32_t* n_coarse_edges, double* C_or_null, double* Cend_or_null) {
+  const std::string who = "pgo_coarsen_plan";
+  if (n_poses < 0 || n_edges < 0 || (n_edges && (!ia || !ib || !meas || !kind)) || !n_coarse_poses || !n_coarse_edges || edge_cap < 0 ||
+      (edge_cap && (!cia || !cib || !cmeas || !ckind || !corigin)))
+    return fail(PGO_ERR_INVALID_ARG, who + ": bad argument");
+  PGOC(check_sizes(who, n_poses, stride));
+  const int64_t N = n_poses, E = n_edges, S = stride, K = (N + S - 1) / S;
+  for (int64_t e = 0; e < E; ++e)
+    if (ia[e] < 0 || ia[e] >= N || ib[e] < 0 || ib[e] >= N) return fail(PGO_ERR_INVALID_ARG, who + ": edge " + std::to_string(e) + ": endpoint out of range");
+  for (int64_t e = 0; e < E; ++e)
+    if (!pgo::coarsen_finite3(meas[3 * e], meas[3 * e + 1], meas[3 * e + 2])) return not_finite(who, e);
+  std::vector<int32_t> chain;
+  const int32_t gap = pgo::pick_chain_edges(n_poses, E, ia, ib, &chain);
+  if (gap >= 0) return no_chain(who, gap);
+  int64_t Ec = K - 1;
+  for (int64_t e = 0; e < E; ++e) Ec += kept(chain, ia, ib, e, stride);
+  *n_coarse_poses = (int32_t)K;
+  *n_coarse_edges = (int32_t)Ec;
+  if (Ec > edge_cap)
+    return fail(PGO_ERR_INVALID_ARG, who + ": the coarse graph has " + std::to_string(Ec) + " edges, the lists hold " + std::to_string(edge_cap));
+  std::vector<double> Cv((size_t)(3 * N)), Ce((size_t)(3 * std::max<int64_t>(K - 1, 1)));
+  pgo::coarsen_composites_serial(N, S, chain.data(), ia, meas, Cv.data(), Ce.data());
+  for (int64_t k = 0; k + 1 < K; ++k) {
+    cia[k] = (int32_t)k;
+    cib[k] = (int32_t)k + 1;
+    cmeas[3 * k] = Ce[3 * k];
+    cmeas[3 * k + 1] = Ce[3 * k + 1];
+    cmeas[3 * k + 2] = pgo::coarsen_wrap(Ce[3 * k + 2]);
+    ckind[k] = PGO_EDGE_ODOMETRY;
+    corigin[k] = -1;
+  }
+  int64_t slot = K - 1;
+  for (int64_t e = 0; e < E; ++e) {
+    if (!kept(chain, ia, ib, e, stride)) continue;
+    const double *ca = &Cv[(size_t)(3 * ia[e])], *cb = &Cv[(size_t)(3 * ib[e])];
+    pgo::coarsen_transport(pgo::se2_make(ca[0], ca[1], ca[2]), meas[3 * e], meas[3 * e + 1], meas[3 * e + 2], pgo::se2_make(cb[0], cb[1], cb[2]),
+                           cmeas + 3 * slot);
+    cia[slot] = ia[e] / stride;
+    cib[slot] = ib[e] / stride;
+    ckind[slot] = kind[e];
+    corigin[slot] = (int32_t)e;
+    ++slot;
+  }
+  if (C_or_null) memcpy(C_or_null, Cv.data(), (size_t)(3 * N) * 8);
+  if (Cend_or_null) memcpy(Cend_or_null, Ce.data(), (size_t)(3 * (K - 1)) * 8);
+  return PGO_OK;
+}
+
+int pgo_prolong_eval(int32_t n_poses, int32_t stride, const double* C, const double* Cend, const double* coarse_xyt, double* out_xyt) {
+  const std::string who = "pgo_prolong_eval";
+  if (n_poses < 0 || !C || !Cend || !coarse_xyt || !out_xyt) return fail(PGO_ERR_INVALID_ARG, who + ": bad argument");
+  PGOC(check_sizes(who, n_poses, stride));
+  pgo::coarsen_prolong_serial(n_poses, stride, C, Cend, coarse_xyt, out_xyt);
+  return PGO_OK;
+}
+
+int pgo_coarsen(pgo_t* h, int32_t stride, pgo_graph** coarse_out, int32_t* origin_or_null, int32_t origin_cap, int32_t* n_coarse_edges_or_null) {
+  if (!h) return fail(PGO_ERR_INVALID_ARG, "pgo_coarsen: null handle");
+  return h->coarsen(stride, coarse_out, origin_or_null, origin_cap, n_coarse_edges_or_null);
+}
+
+int pgo_prolong(pgo_t* h, int32_t stride, const double* coarse_xyt) {
+  if (!h) return fail(PGO_ERR_INVALID_ARG, "pgo_prolong: null handle");
+  return h->prolong(stride, coarse_xyt);
+}
+
+}  // extern "C"

@@ -620,19 +620,16 @@ int pgo_handle::direct_setup(int32_t N, bool switch_now) {
   if (!perm.empty()) return no("the internal pose ordering is on");
   if (N < 2 || N > DIRECT_MAX_POSES) return no("2 .. " + std::to_string(DIRECT_MAX_POSES) + " poses");
   const int64_t EL = S.n_edges_local;
-  std::vector<int32_t> chain((size_t)N, -1), lr, va, vb;
+  std::vector<int32_t> chain, lr, va, vb;
+  const int32_t gap = pgo::pick_chain_edges(N, EL, S.ia.data(), S.ib.data(), &chain);
+  if (gap >= 0) return no("poses " + std::to_string(gap) + " and " + std::to_string(gap + 1) + " are not joined by an edge");
   for (int64_t e = 0; e < EL; ++e) {
-    const int32_t lo_p = std::min(S.ia[e], S.ib[e]), hi_p = std::max(S.ia[e], S.ib[e]);
-    if (hi_p == lo_p + 1 && chain[lo_p] < 0) {
-      chain[lo_p] = (int32_t)e;
-    } else {
-      lr.push_back((int32_t)e);
-      va.push_back(S.ia[e]);
-      vb.push_back(S.ib[e]);
-    }
+    const int32_t lo_p = std::min(S.ia[e], S.ib[e]);
+    if (std::max(S.ia[e], S.ib[e]) == lo_p + 1 && chain[lo_p] == (int32_t)e) continue;
+    lr.push_back((int32_t)e);
+    va.push_back(S.ia[e]);
+    vb.push_back(S.ib[e]);
   }
-  for (int32_t i = 0; i + 1 < N; ++i)
-    if (chain[i] < 0) return no("poses " + std::to_string(i) + " and " + std::to_string(i + 1) + " are not joined by an edge");
   dl_m = (int)lr.size();
   dl_K = 3 * dl_m;
   if (want == 0 && dl_K > DIRECT_AUTO_RANK) {

@@ -9,6 +9,7 @@
 //   solver_abi.hip      the [gpu] part of the C-ABI, test hooks, debug / bench entry points
 //   solver_window.hip   pgo_window_solve: many tiny windows of the graph, one workgroup each (window.hip.h)
 //   solver_score.hip    pgo_trajectory_error, pgo_edge_weights: scoring a solve on the device (score.hip.h, traj_error.h)
+//   solver_coarsen.hip  pgo_coarsen, pgo_prolong: a coarse graph along the odometry chain and back (coarsen.hip.h, coarsen.h)
 // Every kernel header declares its kernels `static`: a translation unit carries the kernels it launches.
 //
 // Replaces, for DCS-ceres/main.cpp METHOD 0/1 (paths relative to /root/reference/DCS-ceres):
@@ -518,6 +519,21 @@ struct pgo_handle {
   std::vector<uint8_t> score_host;   // host image of score_in
   int trajectory_error(const double* ref, const uint8_t* mask, const pgo_traj_options* opt, pgo_traj_error* out, double* per_pose);
   int edge_weights(const double* poses_or_null, pgo_edge_weight* out);
+
+  // hierarchical initialisation (pgo_coarsen, pgo_prolong; solver_coarsen.hip).  The tables in the caller's numbering are built
+  // at the first call and kept: cs_tab = chain [N] | endpoints a [E] | b [E] | local edge [E] (-1: a chain edge) | kind bytes [E].
+  // cs_comp holds C (N x 3) and Cend of stride cs_stride (0: none yet), cs_work the scan scratch and the outputs of a call (or the
+  // coarse poses pgo_prolong uploads); both are grown on demand and kept (win_reserve).  The device copy of perm is score_perm.
+  bool cs_ready = false;
+  std::vector<int32_t> cs_ea_h, cs_eb_h, cs_loc_h;
+  int32_t* cs_tab = nullptr;
+  void *cs_comp = nullptr, *cs_work = nullptr;
+  int64_t cs_comp_cap = 0, cs_work_cap = 0;
+  int32_t cs_stride = 0;
+  std::vector<uint8_t> cs_host;   // host image of a call's outputs
+  int coarsen_tables(const char* who);
+  int coarsen(int32_t stride, pgo_graph** coarse_out, int32_t* origin, int32_t origin_cap, int32_t* n_coarse_edges);
+  int prolong(int32_t stride, const double* coarse_xyt);
 
   int create(int32_t N, const double* poses_h, int32_t E, const int32_t* ia, const int32_t* ib, const double* meas,
              const double* info6, const uint8_t* kind);

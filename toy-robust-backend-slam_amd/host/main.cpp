@@ -1,6 +1,6 @@
 // Command-line front end with the reference's run contract (DCS-ceres/main.cpp:22-40, do_build.sh:10):
 //     ./main DATASET NUM_OUTLIER_LOOPS METHOD [--seed S] [--data DIR] [--save DIR] [--device D] [--precision P]
-//            [--loss NAME[:A]] [--loop-loss NAME[:A]] [--score FILE [--align]]
+//            [--loss NAME[:A]] [--loop-loss NAME[:A]] [--score FILE [--align]] [--init-stride S]
 // METHOD 0 = baseline, 1 = DCS, 2 = switchable constraints run on the MI355X backend; 3/4 are outside it (exit code 3).
 // Reads DIR/DATASET.g2o (default ../data, as the reference), writes init_/opt_ nodes+edges text files that
 // drawer/plot_results.py consumes (default ../save; unlike the reference the directory is created).
@@ -43,13 +43,14 @@ int main(int argc, char* argv[]) {
               << "       --loss sets every block's, default huber:0.01; --loop-loss overrides it on closure and bogus blocks)\n"
               << "       [--score FILE [--align]]  (FILE: reference poses as writePoseGraph_nodes writes them, <index> <x> <y> <theta>; prints\n"
               << "       the trajectory error of the result against it, --align after a rigid fit; a wrong pose count: exit code 2)\n"
+              << "       [--init-stride S]  (2..256: start the solve from the prolonged solution of the graph coarsened at stride S)\n"
               << "METHOD: 0=baseline, 1=DCS, 2=Switchable (3=Layer, 4=Simple Layer MCTS: not in this backend)\n"
               << "Example: " << argv[0] << " INTEL 50 1\n";
     return -1;
   }
   std::string base = "../data", save = "../save", loss_spec = "huber:0.01", loop_spec, score_file;
   long long seed = -1;
-  int device = 0, precision = 0, score_align = 0;
+  int device = 0, precision = 0, score_align = 0, init_stride = 0;
   for (int i = 4; i < argc; i += 2) {
     if (!strcmp(argv[i], "--align")) {   // (the one option without a value)
       score_align = 1;
@@ -65,6 +66,7 @@ int main(int argc, char* argv[]) {
     else if (!strcmp(argv[i], "--precision")) precision = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "--loss")) loss_spec = argv[i + 1];
     else if (!strcmp(argv[i], "--loop-loss")) loop_spec = argv[i + 1];
+    else if (!strcmp(argv[i], "--init-stride")) init_stride = atoi(argv[i + 1]);
     else { std::cerr << "unknown option " << argv[i] << "\n"; return -1; }
   }
   std::unique_ptr<pgo::LossFunction> loss_function, loop_loss;
@@ -121,6 +123,15 @@ int main(int argc, char* argv[]) {
     options.linear_solver_type = pgo::SPARSE_NORMAL_CHOLESKY;
     options.device = device;
     pgo::Solver::Summary summary;
+    if (init_stride != 0) {   // hierarchical initialisation: the parameter blocks start at the coarse graph's prolonged solution
+      pgo::Solver::Options coarse_options;
+      coarse_options.device = device;
+      pgo::Solver::Summary coarse;
+      pgo::InitializeHierarchical(&problem, init_stride, coarse_options, &coarse);
+      std::cout << "init-stride " << init_stride << ": coarse graph of " << coarse.num_parameter_blocks << " poses and " << coarse.num_residual_blocks
+                << " edges, cost " << coarse.s.initial_cost << " -> " << coarse.s.final_cost << " in " << coarse.s.iterations << " iterations"
+                << std::endl;
+    }
     pgo::Solve(options, &problem, &summary);
     std::cout << summary.FullReport() << std::endl;
 

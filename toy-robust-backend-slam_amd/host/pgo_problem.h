@@ -270,6 +270,49 @@ struct SolverAccess {
     const int st = pgo_solve(h, &sum->s);
     Finish(pr, h, st, sum);
   }
+  // Hierarchical initialisation (include/pgo.h): the problem's graph coarsened at `stride`, the coarse graph solved exactly (the
+  // problem's METHOD, pcg_rtol 1e-10, everything else left to the library; a constant block that is a key pose stays the
+  // constant one), the result prolonged and written into the caller's parameter blocks in place -- the start of the Solve
+  // that follows.  Constant blocks are not moved.
+  static void InitializeHierarchical(const Solver::Options& opt, Problem* pr, int stride, Solver::Summary* coarse_sum) {
+    pgo_t* h = Prepare(opt, pr);
+    pgo_graph* cg = nullptr;
+    pgo_t* ch = nullptr;
+    int st = pgo_coarsen(h, stride, &cg, nullptr, 0, nullptr);
+    Solver::Summary local;
+    Solver::Summary* cs = coarse_sum ? coarse_sum : &local;
+    if (st == PGO_OK) {
+      pgo_options o;
+      pgo_options_default(&o);
+      o.method = pr->any_sc_ ? 2 : (pr->any_dcs_ ? 1 : 0);
+      o.pcg_rtol = 1e-10;
+      o.fixed_pose = pr->fixed_ < 0 ? pr->fixed_ : (pr->fixed_ % stride == 0 ? pr->fixed_ / stride : 0);
+      st = pgo_create_from_graph(&ch, cg, &o, nullptr, opt.device);
+    }
+    if (st == PGO_OK) st = pgo_solve(ch, &cs->s);
+    std::vector<double> X;
+    if (st == PGO_OK) {
+      X.resize((size_t)3 * pgo_graph_num_poses(cg));
+      st = pgo_get_poses(ch, X.data());
+    }
+    if (st == PGO_OK) {
+      cs->iterations.resize((size_t)pgo_num_iter_records(ch));
+      st = pgo_get_iter_records(ch, cs->iterations.data(), (int32_t)cs->iterations.size());
+      cs->num_parameter_blocks = pgo_graph_num_poses(cg);
+      cs->num_residual_blocks = pgo_graph_num_edges(cg);
+    }
+    if (st == PGO_OK) st = pgo_prolong(h, stride, X.data());
+    const std::string msg = st != PGO_OK ? std::string(pgo_last_error()) : std::string();
+    if (ch) pgo_destroy(ch);
+    pgo_graph_free(cg);
+    const int32_t N = (int32_t)pr->ptr_.size();
+    std::vector<double> poses((size_t)3 * N);
+    if (st == PGO_OK) st = pgo_get_poses(h, poses.data());
+    pgo_destroy(h);
+    if (st != PGO_OK) throw std::runtime_error(std::string("pgo: ") + pgo_strerror(st) + ": " + (msg.empty() ? pgo_last_error() : msg));
+    for (int32_t i = 0; i < N; ++i)
+      for (int k = 0; k < 3; ++k) pr->ptr_[i][k] = poses[3 * (size_t)i + k];
+  }
   // The layer managers' pattern (src/simple_layer_manager.cpp:457-622: one ceres::Solve per candidate layer / window).
   // ONE batched handle (pgo_batch_*: a workgroup per problem, per-problem LM state on one launch sequence) when every
   // problem uses the same plain / DCS functor, loss and anchor index; else a pool of host threads over ordinary handles.
@@ -365,6 +408,12 @@ struct SolverAccess {
 };
 
 inline void Solve(const Solver::Options& opt, Problem* problem, Solver::Summary* summary) { SolverAccess::Solve(opt, problem, summary); }
+// the parameter blocks moved, in place, to the prolonged solution of the problem's coarse graph at `stride` (pgo_coarsen ->
+// solve -> pgo_prolong); call Solve next.  coarse_summary (or nullptr) receives the coarse solve's summary
+inline void InitializeHierarchical(Problem* problem, int stride, const Solver::Options& opt = Solver::Options(),
+                                   Solver::Summary* coarse_summary = nullptr) {
+  SolverAccess::InitializeHierarchical(opt, problem, stride, coarse_summary);
+}
 // many independent problems at once; summaries->size() == problems.size() afterwards
 inline void SolveBatch(const Solver::Options& opt, const std::vector<Problem*>& problems, std::vector<Solver::Summary>* summaries,
                        int max_concurrency = 8) {
