@@ -852,7 +852,11 @@ int pgo_debug_system_spmv(pgo_t* h, const double* x, double* y, double* d2_or_nu
  * for a null pointer, refine_steps outside -1 .. 3 or a handle without pgo_lm_begin.                                    */
 int pgo_debug_direct_solve(pgo_t* h, const double* b_3n, int32_t refine_steps, double* y_3n);   /* [gpu] */
 /* normal-equation pieces at the current point, caller's pose order (world == 1):
- * g: 3N gradient J'r (unscaled), hdiag: N x 9 diagonal 3x3 blocks of J'J         */
+ * g: 3N gradient J'r (unscaled), hdiag: N x 9 diagonal 3x3 blocks of J'J; 0 on the constant pose.  The call re-evaluates the
+ * residuals at the current poses, resets the pose scales to 1 and ends the solve begun with pgo_lm_begin.
+ * METHOD 2: the REDUCED pose system, not the joint one -- g = P'(r - gamma j) and the diagonal blocks of P'(I - c j j')P, P the
+ * pose columns of the Jacobian at the current poses and switches, j = d e / d s per robust edge, with the c and gamma of the
+ * handle's last assembly (k_switch_prepare: the switches eliminated for the radius of that assembly, their Jacobi scales kept). */
 int pgo_debug_normal_eq(pgo_t* h, double* g_or_null, double* hdiag_or_null);      /* [gpu] */
 /* Test hooks -- for tests/ only, not part of the drop-in surface.  Process-wide knobs read by pgo_create* (handles
  * created afterwards); value < 0 restores the library's default.  The library reads NO environment variable other than
