@@ -763,6 +763,95 @@ typedef struct pgo_edge_weight {
 } pgo_edge_weight;
 int pgo_edge_weights(pgo_t* h, const double* poses_or_null, pgo_edge_weight* out /* E, caller's edge order */);   /* [gpu] */
 
+/* ---------------------------------------------------------------- edge weight plane
+ * A scalar weight w in [0, 1] per edge on a live handle, between the binary mask of pgo_set_active and the loss classes: with
+ * a plane set, an edge counts w 1/2 rho(s) in the cost, and its residual and Jacobian rows are scaled by sqrt(w rho'(s)), s
+ * being what K1 computes today (after DCS).  The plane is part of the problem like the mask: pgo_eval applies it with and
+ * without apply_loss.  w = 0 gives exactly-zero rows and zero cost (as Tukey beyond its bound); the edge stays a residual
+ * block, so a zero-weight odometry edge does not cut the direct solve's chain -- the rows are zero and a direct solve that
+ * fails on them is redone by PCG (pgo_handle_info.direct_fallbacks).  Inactive edges stay exactly as pgo_set_active left them.
+ * - A handle with a plane runs K1's general instantiation (as one with an edge mask does); the default instantiations do not
+ *   read the plane.  pgo_set_edge_weights(h, NULL) restores the handle: a pgo_solve after it gives bitwise what a fresh
+ *   handle gives.
+ * - A solve begun with pgo_lm_begin becomes stale, as after pgo_set_losses.  pgo_set_losses and pgo_set_active leave the
+ *   weights alone, in either call order.
+ * - pgo_pose_covariance, pgo_edge_gate and pgo_edge_gate_joint consume K1's records: they see the WEIGHTED problem.
+ *   pgo_edge_weights (scoring) reports weight = w scale^2 rho1 and cost = w 1/2 rho(s): weight * s_plain stays |r|^2 of
+ *   pgo_eval's r, and the sum of cost over the active edges stays pgo_eval's cost.
+ * - pgo_window_solve returns PGO_ERR_UNSUPPORTED while a plane is set (its kernel evaluates the edges itself).
+ * - pgo_get_edge_weights: the plane in the caller's edge order; all ones when none is set.
+ * Errors: PGO_ERR_INVALID_ARG for a weight that is not finite or outside [0, 1] (pgo_last_error names the first such edge) or a
+ * null handle / output; PGO_ERR_UNSUPPORTED for METHOD 2, info_weighting = 1, a communicator or PGO_FORCE_COLLECTIVES=1, a
+ * batched handle.  Nothing changes on error.                                                                                  */
+int pgo_set_edge_weights(pgo_t* h, const double* w_or_null /* E, caller's edge order */);   /* [gpu] */
+int pgo_get_edge_weights(pgo_t* h, double* w_out /* E */);                                  /* [gpu] */
+
+/* ---------------------------------------------------------------- graduated non-convexity
+ * GNC with the truncated-least-squares surrogate (Yang, Antonante, Tzoumas, Carlone, RA-L 2020) on the weight plane: start from
+ * the convex all-edges-in problem and tighten a per-edge weight round by round.  csrc/gnc.h is the one statement:
+ *   gnc_mu0(c2, rmax2) = c2 / (2 rmax2 - c2)                       (valid for 2 rmax2 > c2)
+ *   gnc_tls_weight(c2, mu, s) = 1 for s <= mu / (mu + 1) c2;  0 for s >= (mu + 1) / mu c2;  else sqrt(c2 mu (mu + 1) / s) - mu
+ * with c2 = cbar^2 and s = the s_plain of pgo_edge_weights: the plain |e|^2 as K1 states it, before DCS or any loss.  A
+ * non-finite s gives weight 0.  pgo_gnc_weight_eval evaluates n weights on the host (cbar finite and > 0, mu finite and > 0,
+ * else PGO_ERR_INVALID_ARG).
+ *
+ * pgo_gnc_update, at the handle's current poses: every SELECTED edge -- the active edges (pgo_set_active) with kind !=
+ * PGO_EDGE_ODOMETRY, or the active edges with a non-zero byte in select (E bytes, caller's order) -- gets the weight
+ * gnc_tls_weight(cbar^2, mu, s) in the handle's plane, which is allocated at all ones at its first use; every other edge keeps
+ * its weight.  mu <= 0 measures only: no weight is touched (and no plane is created).  out (may be NULL) receives, over the
+ * selected edges and with the weights the call leaves: n_selected; s_max, the largest finite s (-1: none); weighted_sum = sum w s
+ * over the finite s; n_nonbinary, the edges with 0 < w < 1; n_zero, those with w = 0; n_nonfinite, those whose s is not finite.
+ * One lane per edge of the caller's numbering, per-workgroup partials folded by one workgroup in fixed order, no atomics: two
+ * calls are bitwise equal, and neither the launch grid nor the internal pose ordering plays a part.  With mu > 0 a solve begun
+ * with pgo_lm_begin becomes stale.
+ *
+ * pgo_gnc_solve, METHOD 0, from the handle's current poses, under the handle's own options and loss:
+ *   1. every selected weight <- 1; rmax2 = s_max there.
+ *   2. 2 rmax2 <= cbar^2: one solve of final_iters LM iterations, rounds = 0, done.
+ *   3. mu = gnc_mu0(cbar^2, rmax2).
+ *   4. a round: pgo_lm_begin and up to inner_iters LM iterations; pgo_gnc_update at the new poses with mu; the round's record
+ *      {mu, weighted_cost = 1/2 weighted_sum, n_nonbinary, n_zero, lm_iterations, lm_termination}; stop when n_nonbinary == 0 and
+ *      this is not the first round, else mu *= mu_factor.
+ *   5. after the stop, or after max_rounds rounds (hit_max_rounds = 1), one solve of final_iters with the weights as they stand.
+ * (An LM solve also ends at the handle's own max_iters, whichever is smaller.)  The weights stay on the handle: for
+ * pgo_get_edge_weights, for the covariances and the gates, for further solves; pgo_set_edge_weights(h, NULL) drops them.  An
+ * inner solve that ends with PGO_TERM_FAILURE ends the call with PGO_ERR_NUMERIC; the poses are those of the last good round.
+ * rounds_or_null receives the first rounds_cap records.
+ * Errors: PGO_ERR_INVALID_ARG for a cbar that is not finite and > 0, mu_factor not finite or <= 1, inner_iters / final_iters /
+ * max_rounds < 1, a NaN mu, a null handle, and for pgo_gnc_solve a handle that is not METHOD 0; PGO_ERR_UNSUPPORTED as
+ * pgo_set_edge_weights.  Nothing changes on those errors.                                                                     */
+typedef struct pgo_gnc_stats {
+  double  s_max;          /* largest finite s over the selected edges; -1 when there is none */
+  double  weighted_sum;   /* sum of w s over the selected edges with a finite s */
+  int32_t n_selected, n_nonbinary, n_zero, n_nonfinite;
+} pgo_gnc_stats;
+typedef struct pgo_gnc_options {
+  double  cbar;           /* no default: finite and > 0 -- the residual norm above which an edge is an outlier */
+  double  mu_factor;      /* 1.4 */
+  int32_t inner_iters;    /* 5 */
+  int32_t final_iters;    /* 50 */
+  int32_t max_rounds;     /* 100 */
+  int32_t _pad;
+  const uint8_t* select;  /* NULL: the active edges with kind != PGO_EDGE_ODOMETRY; else E bytes, caller's order */
+} pgo_gnc_options;
+typedef struct pgo_gnc_round {
+  double  mu, weighted_cost;
+  int32_t n_nonbinary, n_zero, lm_iterations, lm_termination;
+  double  seconds;        /* the round's wall time: inner solve + update */
+} pgo_gnc_round;
+typedef struct pgo_gnc_summary {
+  int32_t rounds, hit_max_rounds;
+  int32_t n_selected, n_zero;       /* selected edges; those at weight 0 when the call returns */
+  double  rmax2, mu0, mu_last;      /* mu0 = mu_last = 0 when rounds == 0 */
+  double  seconds_total;
+  pgo_summary final_solve;          /* the solve of step 2 / 5 */
+} pgo_gnc_summary;
+void pgo_gnc_options_default(pgo_gnc_options*);   /* cbar = 0: the caller must set it */                          /* [host] */
+int  pgo_gnc_weight_eval(double cbar, double mu, int32_t n, const double* s, double* w_out);                      /* [host] */
+int  pgo_gnc_update(pgo_t* h, double cbar, double mu, const uint8_t* select_or_null, pgo_gnc_stats* out_or_null); /* [gpu] */
+int  pgo_gnc_solve(pgo_t* h, const pgo_gnc_options* opt, pgo_gnc_summary* summary_or_null,
+                   pgo_gnc_round* rounds_or_null, int32_t rounds_cap);                                            /* [gpu] */
+
 /* ---------------------------------------------------------------- hierarchical initialisation
  * Start a large solve near its answer (HOG-Man style): collapse every `stride` consecutive poses onto a key pose, carry every
  * other edge to the key poses along the odometry chain, solve that small graph exactly with a handle of its own, and spread the
@@ -886,6 +975,8 @@ int pgo_debug_normal_eq(pgo_t* h, double* g_or_null, double* hdiag_or_null);    
  *                        call; the results are bitwise the same)
  *   "coarsen_grid"       n > 0 = pgo_coarsen and pgo_prolong launch n workgroups over their segments, chunks and poses instead of
  *                        one per unit of work (read per call; the results are bitwise the same)
+ *   "gnc_grid"           n > 0 = pgo_gnc_update (and pgo_gnc_solve through it) launches n workgroups over its chunks of 256 edges
+ *                        instead of one per chunk (read per call; the results are bitwise the same)
  * Unknown name: PGO_ERR_INVALID_ARG.                                                                     */
 int pgo_debug_set_knob(const char* name, long long value);                        /* [host] */
 /* sharding plan of a graph over `world` ranks: for rank r, rows [lo, hi) and the

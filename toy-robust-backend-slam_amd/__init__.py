@@ -26,7 +26,8 @@ __all__ = ["PgoError", "Options", "Summary", "IterRecord", "ReadG2O", "Graph", "
            "GateJointOptions", "GateJointResult", "GateJointSummary", "gate_joint_evaluate", "GATE_JOINT_MAX",
            "window_plan", "WindowResult", "WINDOW_MAX_POSES", "WINDOW_MAX_EDGES", "WINDOW_MAX_ITERS",
            "synth_manhattan_truth", "trajectory_error", "TrajOptions", "TrajError", "EdgeWeight", "SCORE_POSES_PER_WG",
-           "coarsen_plan", "prolong_eval", "COARSEN_MIN_STRIDE", "COARSEN_MAX_STRIDE"]
+           "coarsen_plan", "prolong_eval", "COARSEN_MIN_STRIDE", "COARSEN_MAX_STRIDE",
+           "gnc_weight_eval", "GncStats", "GncOptions", "GncRound", "GncSummary"]
 
 EDGE_ODOMETRY, EDGE_CLOSURE, EDGE_BOGUS = 0, 1, 2
 TERMINATION = {1: "CONVERGENCE_FTOL", 2: "CONVERGENCE_GTOL", 3: "CONVERGENCE_PTOL", 4: "NO_CONVERGENCE",
@@ -57,6 +58,7 @@ EXPORTS = [
     "pgo_window_plan", "pgo_window_solve", "pgo_batch_window_solve",
     "pgo_synth_manhattan_truth", "pgo_traj_options_default", "pgo_trajectory_error_eval", "pgo_trajectory_error", "pgo_edge_weights",
     "pgo_coarsen_plan", "pgo_prolong_eval", "pgo_coarsen", "pgo_prolong",
+    "pgo_set_edge_weights", "pgo_get_edge_weights", "pgo_gnc_options_default", "pgo_gnc_weight_eval", "pgo_gnc_update", "pgo_gnc_solve",
 ]
 COARSEN_MIN_STRIDE, COARSEN_MAX_STRIDE = 2, 256   # PGO_COARSEN_*_STRIDE (include/pgo.h)
 SCORE_POSES_PER_WG = 512   # PGO_SCORE_POSES_PER_WG
@@ -267,6 +269,49 @@ class EdgeWeight(C.Structure):
                 ("active", C.c_int32), ("_pad", C.c_int32)]
 
 
+class GncStats(C.Structure):
+    """mirror of pgo_gnc_stats: what Solver.gnc_update measured over the selected edges"""
+    _fields_ = [("s_max", C.c_double), ("weighted_sum", C.c_double), ("n_selected", C.c_int32), ("n_nonbinary", C.c_int32),
+                ("n_zero", C.c_int32), ("n_nonfinite", C.c_int32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class GncOptions(C.Structure):
+    """mirror of pgo_gnc_options (defaults: pgo_gnc_options_default; cbar has none)"""
+    _fields_ = [("cbar", C.c_double), ("mu_factor", C.c_double), ("inner_iters", C.c_int32), ("final_iters", C.c_int32),
+                ("max_rounds", C.c_int32), ("_pad", C.c_int32), ("select", C.POINTER(C.c_uint8))]
+
+    def __init__(self, cbar, **kw):
+        super().__init__()
+        lib().pgo_gnc_options_default(C.byref(self))
+        self.cbar = float(cbar)
+        for k, v in kw.items():
+            if k not in ("mu_factor", "inner_iters", "final_iters", "max_rounds"):
+                raise TypeError("unknown gnc option " + k)
+            setattr(self, k, v)
+
+
+class GncRound(C.Structure):
+    _fields_ = [("mu", C.c_double), ("weighted_cost", C.c_double), ("n_nonbinary", C.c_int32), ("n_zero", C.c_int32),
+                ("lm_iterations", C.c_int32), ("lm_termination", C.c_int32), ("seconds", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class GncSummary(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("hit_max_rounds", C.c_int32), ("n_selected", C.c_int32), ("n_zero", C.c_int32),
+                ("rmax2", C.c_double), ("mu0", C.c_double), ("mu_last", C.c_double), ("seconds_total", C.c_double),
+                ("final_solve", Summary)]
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_ if n != "final_solve"}
+        d["final_solve"] = self.final_solve.as_dict()
+        return d
+
+
 _LIB = None
 
 
@@ -401,6 +446,13 @@ def lib():
     L.pgo_prolong_eval.argtypes = [C.c_int32, C.c_int32, dp, dp, dp, dp]
     L.pgo_coarsen.argtypes = [vp, C.c_int32, C.POINTER(vp), ip, C.c_int32, ip]
     L.pgo_prolong.argtypes = [vp, C.c_int32, dp]
+    L.pgo_set_edge_weights.argtypes = [vp, dp]
+    L.pgo_get_edge_weights.argtypes = [vp, dp]
+    L.pgo_gnc_options_default.argtypes = [C.POINTER(GncOptions)]
+    L.pgo_gnc_options_default.restype = None
+    L.pgo_gnc_weight_eval.argtypes = [C.c_double, C.c_double, C.c_int32, dp, dp]
+    L.pgo_gnc_update.argtypes = [vp, C.c_double, C.c_double, bp, C.POINTER(GncStats)]
+    L.pgo_gnc_solve.argtypes = [vp, C.POINTER(GncOptions), C.POINTER(GncSummary), C.POINTER(GncRound), C.c_int32]
     _LIB = L
     return L
 
@@ -577,6 +629,15 @@ def trajectory_error(est, ref, mask=None, align=False, rpe_delta=1, per_pose=Fal
     per_pose=True)."""
     est = np.ascontiguousarray(est, np.float64).reshape(-1, 3)
     return _traj_call(lib().pgo_trajectory_error_eval, (len(est), _dp(est)), len(est), ref, mask, align, rpe_delta, per_pose)
+
+
+def gnc_weight_eval(cbar, mu, s):
+    """pgo_gnc_weight_eval (host only): the GNC-TLS weights gnc_tls_weight(cbar^2, mu, s) of csrc/gnc.h for an array of plain
+    squared residuals s; a non-finite s gives 0"""
+    s = np.ascontiguousarray(s, np.float64)
+    out = np.zeros(s.shape)
+    _check(lib().pgo_gnc_weight_eval(float(cbar), float(mu), s.size, _dp(s.reshape(-1)), _dp(out.reshape(-1))))
+    return out
 
 
 def shard_plan(n_poses, ia, ib, world, rank, row_align=1):
@@ -980,6 +1041,46 @@ class Solver:
         res = (EdgeWeight * max(self.n_edges, 1))()
         _check(lib().pgo_edge_weights(self._h, _dp(p), res))
         return np.ctypeslib.as_array(res)[:self.n_edges].copy()
+
+    def set_edge_weights(self, w=None):
+        """pgo_set_edge_weights: a weight in [0, 1] per edge (caller's order) -- the edge counts w 1/2 rho(s), its rows are
+        scaled by sqrt(w rho'(s)); None drops the plane and restores the handle.  A solve begun with lm_begin is stale
+        afterwards."""
+        if w is None:
+            _check(lib().pgo_set_edge_weights(self._h, None))
+            return
+        a = np.ascontiguousarray(w, np.float64).reshape(-1)
+        if a.size != self.n_edges:
+            raise ValueError(f"set_edge_weights: {a.size} entries for {self.n_edges} edges")
+        _check(lib().pgo_set_edge_weights(self._h, _dp(a)))
+
+    def get_edge_weights(self):
+        """pgo_get_edge_weights: the plane in the caller's edge order (all ones when none is set)"""
+        out = np.zeros(self.n_edges)
+        _check(lib().pgo_get_edge_weights(self._h, _dp(out)))
+        return out
+
+    def gnc_update(self, cbar, mu, select=None):
+        """pgo_gnc_update at the current poses: the selected edges (default: the active edges with kind != 0; else a mask over
+        the edges) get the GNC-TLS weight for (cbar, mu); mu <= 0 measures only.  Returns the dict of GncStats."""
+        m = _mask(select, self.n_edges, "select")
+        st = GncStats()
+        _check(lib().pgo_gnc_update(self._h, float(cbar), float(mu), _bp(m) if m is not None else None, C.byref(st)))
+        return st.as_dict()
+
+    def gnc_solve(self, cbar, select=None, **opts):
+        """pgo_gnc_solve (METHOD 0): graduated non-convexity with the TLS surrogate from the current poses; opts: mu_factor,
+        inner_iters, final_iters, max_rounds.  Returns (summary dict, list of round dicts); the weights stay on the handle
+        (get_edge_weights)."""
+        o = GncOptions(cbar, **opts)
+        m = _mask(select, self.n_edges, "select")
+        if m is not None:
+            o.select = _bp(m)
+        cap = max(int(o.max_rounds), 1)
+        rounds = (GncRound * cap)()
+        summ = GncSummary()
+        _check(lib().pgo_gnc_solve(self._h, C.byref(o), C.byref(summ), rounds, cap))
+        return summ.as_dict(), [rounds[k].as_dict() for k in range(min(summ.rounds, cap))]
 
     def coarsen(self, stride: int):
         """pgo_coarsen: the coarse graph of the handle's measurements at `stride` (see coarsen_plan), with the handle's current

@@ -217,6 +217,9 @@ struct EdgeArgs {
   // batched handles: cost of every edge (NaN where the residual or Jacobian is not finite), summed per problem by
   // k_prob_reduce; nullptr otherwise
   double* cost_out;
+  // pgo_set_edge_weights: a weight in [0, 1] per local edge -- the edge counts w 1/2 rho(s), its rows are scaled by
+  // sqrt(w rho'(s)); nullptr when no plane is set.  Read by k_edge_eval<*, *, true> only (a handle with a plane runs those).
+  const double* w;
   // pgo_set_losses: the loss of each class (k_edge_eval<*, *, true>); four named fields, not an array: a lane-dependent
   // index into an array argument is lowered through scratch
   LossClass loss0, loss1, loss2, loss3;
@@ -275,6 +278,11 @@ __global__ __launch_bounds__(WG) void k_edge_eval(EdgeArgs A, double* __restrict
     const int a = A.ia[e], b = A.ib[e];
     const double dx = A.mx[e], dy = A.my[e], dth = A.mt[e];
     const unsigned fl = A.flags[e];
+    // the weight plane (pgo_set_edge_weights), loaded with the edge's other streams: the lane needs it only after the loss
+    double wq = 1.0;
+    if constexpr (LOSSES) {
+      if (A.w) wq = A.w[e];
+    }
     const double x1 = A.poses[3 * (int64_t)a], y1 = A.poses[3 * (int64_t)a + 1], t1 = A.poses[3 * (int64_t)a + 2];
     const double x2 = A.poses[3 * (int64_t)b], y2 = A.poses[3 * (int64_t)b + 1], t2 = A.poses[3 * (int64_t)b + 2];
     double ex, ey, sind, J[18];
@@ -334,6 +342,10 @@ __global__ __launch_bounds__(WG) void k_edge_eval(EdgeArgs A, double* __restrict
       loss_rho(pick_loss(A.loss0, A.loss1, A.loss2, A.loss3, (fl >> 2) & 3u), s, rho);
       rho0 = rho[0];
       if (A.apply_loss) sc = sqrt(rho[1]);
+      if (A.w) {   // the weight plane: part of the problem like the mask, so with and without apply_loss; w = 0: exactly-zero rows
+        sc *= sqrt(wq);
+        rho0 *= wq;
+      }
     } else if (A.huber_delta > 0.0) {  // ceres::HuberLoss(a): b = a^2
       const double bq = A.huber_delta * A.huber_delta;
       if (s > bq) {

@@ -375,6 +375,11 @@ __global__ __launch_bounds__(WG) void k_edge_weights(EdgeArgs A, int32_t dcs, co
     W.rho1 = rho[1];
     W.weight = W.scale * W.scale * rho[1];
     W.cost = 0.5 * rho[0];
+    if (A.w) {   // pgo_set_edge_weights: the edge counts w times that (weight * s_plain stays |r|^2 of pgo_eval's r)
+      const double w = A.w[e];
+      W.weight *= w;
+      W.cost *= w;
+    }
     if (!isfinite(s)) W.s_plain = W.scale = W.rho1 = W.weight = W.cost = __builtin_nan("");
     W.active = (fl & EDGE_INACTIVE) ? 0 : 1;
     W._pad = 0;

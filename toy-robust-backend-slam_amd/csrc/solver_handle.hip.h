@@ -10,6 +10,7 @@
 //   solver_window.hip   pgo_window_solve: many tiny windows of the graph, one workgroup each (window.hip.h)
 //   solver_score.hip    pgo_trajectory_error, pgo_edge_weights: scoring a solve on the device (score.hip.h, traj_error.h)
 //   solver_coarsen.hip  pgo_coarsen, pgo_prolong: a coarse graph along the odometry chain and back (coarsen.hip.h, coarsen.h)
+//   solver_gnc.hip      pgo_set_edge_weights, pgo_gnc_update, pgo_gnc_solve: the edge weight plane and GNC-TLS (gnc.hip.h, gnc.h)
 // Every kernel header declares its kernels `static`: a translation unit carries the kernels it launches.
 //
 // Replaces, for DCS-ceres/main.cpp METHOD 0/1 (paths relative to /root/reference/DCS-ceres):
@@ -356,6 +357,7 @@ struct pgo_handle {
     A.loss1 = loss_cls[1];
     A.loss2 = loss_cls[2];
     A.loss3 = loss_cls[3];
+    A.w = w_set ? e_w : nullptr;
     return A;
   }
   // robust losses (pgo_set_losses): the loss of each class; an edge's class sits in bits 2-3 of its flags byte
@@ -383,6 +385,21 @@ struct pgo_handle {
   bool has_anchor() const { return fixed_internal >= 0 || act_anchor; }
   void coarse_dead_list(std::vector<int32_t>* dead) const;
   int set_active(const uint8_t* edge_active, const uint8_t* pose_constant);
+  // edge weights (pgo_set_edge_weights) and graduated non-convexity (pgo_gnc_update, pgo_gnc_solve; solver_gnc.hip, gnc.hip.h,
+  // gnc.h): one double in [0, 1] per local edge.  The plane is allocated at its first use and kept; while one is in force K1 runs
+  // its LOSSES instantiations, which read it.  gnc_buf holds a call's select bytes, the per-workgroup partials and the folded
+  // statistics (made at the first call and kept, win_reserve), and the caller's edge -> local edge table of k_gnc_update.
+  double* e_w = nullptr;
+  bool w_set = false;
+  void* gnc_buf = nullptr;
+  int64_t gnc_buf_cap = 0;
+  double* gnc_x = nullptr;   // pgo_gnc_solve: the poses a round started from (allocated at the first call, kept)
+  int weights_supported(const char* who) const;   // the refusals the weight plane and GNC share
+  int weights_alloc();                            // the plane, before anything changes
+  int set_edge_weights(const double* w_or_null);
+  int get_edge_weights(double* w_out);
+  int gnc_update(double cbar, double mu, const uint8_t* select_or_null, bool reset_selected, pgo_gnc_stats* out);
+  int gnc_solve(const pgo_gnc_options* o, pgo_gnc_summary* summary, pgo_gnc_round* rounds, int32_t rounds_cap);
   dev::SwitchArrays switch_arrays() const {
     dev::SwitchArrays W;
     W.flags = e_flags;

@@ -53,7 +53,8 @@ int pgo_handle::share_gather_vector(double* full) {
 
 void pgo_handle::launch_eval(const double* x, const double* sw_vals, int apply_loss, bool with_jac) {
   dev::EdgeArgs A = edge_args(x, sw_vals, apply_loss);
-  if (loss_general || act_edges) {   // per-class losses (pgo_set_losses) or an edge mask (pgo_set_active): the general instantiation
+  if (loss_general || act_edges || w_set) {   // per-class losses (pgo_set_losses), an edge mask (pgo_set_active) or a weight plane
+                                              // (pgo_set_edge_weights): the general instantiation
     if (info_mode) {
       if (with_jac) hipLaunchKernelGGL((dev::k_edge_eval<true, true, true>), dim3(g_edge), dim3(dev::WG), 0, stream, A, jr, part[5], bad);
       else hipLaunchKernelGGL((dev::k_edge_eval<false, true, true>), dim3(g_edge), dim3(dev::WG), 0, stream, A, jr, part[5], bad);

@@ -30,6 +30,8 @@ int pgo_handle::window_solve(const char* who, int32_t nw, const int32_t* pose_pt
   if (opt.method != 0 && opt.method != 1) return fail(PGO_ERR_UNSUPPORTED, W + "METHOD 0 and 1 only");
   if (opt.info_weighting || info_mode) return fail(PGO_ERR_UNSUPPORTED, W + "info_weighting is not supported");
   if (comm || force_collectives) return fail(PGO_ERR_UNSUPPORTED, W + "one rank without a communicator only");
+  if (w_set)   // (k_window_solve evaluates the edges itself and does not read the plane)
+    return fail(PGO_ERR_UNSUPPORTED, W + "not while edge weights are set (pgo_set_edge_weights(h, NULL) first)");
   if (nw < 0) return fail(PGO_ERR_INVALID_ARG, W + "n_windows < 0");
   if (nw == 0) return PGO_OK;
   if (!pose_ptr || !pose_idx || !edge_ptr || !edge_idx || !anchor || !results) return fail(PGO_ERR_INVALID_ARG, W + "null pointer");

@@ -1,11 +1,12 @@
 // Command-line front end with the reference's run contract (DCS-ceres/main.cpp:22-40, do_build.sh:10):
 //     ./main DATASET NUM_OUTLIER_LOOPS METHOD [--seed S] [--data DIR] [--save DIR] [--device D] [--precision P]
-//            [--loss NAME[:A]] [--loop-loss NAME[:A]] [--score FILE [--align]] [--init-stride S]
+//            [--loss NAME[:A]] [--loop-loss NAME[:A]] [--score FILE [--align]] [--init-stride S] [--gnc CBAR [--gnc-inner K]]
 // METHOD 0 = baseline, 1 = DCS, 2 = switchable constraints run on the MI355X backend; 3/4 are outside it (exit code 3).
 // Reads DIR/DATASET.g2o (default ../data, as the reference), writes init_/opt_ nodes+edges text files that
 // drawer/plot_results.py consumes (default ../save; unlike the reference the directory is created).
 #include <sys/stat.h>
 
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -44,13 +45,18 @@ int main(int argc, char* argv[]) {
               << "       [--score FILE [--align]]  (FILE: reference poses as writePoseGraph_nodes writes them, <index> <x> <y> <theta>; prints\n"
               << "       the trajectory error of the result against it, --align after a rigid fit; a wrong pose count: exit code 2)\n"
               << "       [--init-stride S]  (2..256: start the solve from the prolonged solution of the graph coarsened at stride S)\n"
+              << "       [--gnc CBAR [--gnc-inner K]]  (METHOD 0 only: graduated non-convexity with the TLS surrogate over the closure and bogus\n"
+              << "       blocks, CBAR = the residual norm above which a block is an outlier, K LM iterations per round, default 5; prints the\n"
+              << "       rounds and writes weights.txt, one weight per edge in the order of the edges files)\n"
               << "METHOD: 0=baseline, 1=DCS, 2=Switchable (3=Layer, 4=Simple Layer MCTS: not in this backend)\n"
               << "Example: " << argv[0] << " INTEL 50 1\n";
     return -1;
   }
   std::string base = "../data", save = "../save", loss_spec = "huber:0.01", loop_spec, score_file;
   long long seed = -1;
-  int device = 0, precision = 0, score_align = 0, init_stride = 0;
+  int device = 0, precision = 0, score_align = 0, init_stride = 0, gnc_inner = 5;
+  double gnc_cbar = 0.0;
+  bool gnc_on = false;
   for (int i = 4; i < argc; i += 2) {
     if (!strcmp(argv[i], "--align")) {   // (the one option without a value)
       score_align = 1;
@@ -67,6 +73,8 @@ int main(int argc, char* argv[]) {
     else if (!strcmp(argv[i], "--loss")) loss_spec = argv[i + 1];
     else if (!strcmp(argv[i], "--loop-loss")) loop_spec = argv[i + 1];
     else if (!strcmp(argv[i], "--init-stride")) init_stride = atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "--gnc")) { gnc_on = true; gnc_cbar = atof(argv[i + 1]); }
+    else if (!strcmp(argv[i], "--gnc-inner")) gnc_inner = atoi(argv[i + 1]);
     else { std::cerr << "unknown option " << argv[i] << "\n"; return -1; }
   }
   std::unique_ptr<pgo::LossFunction> loss_function, loop_loss;
@@ -82,6 +90,10 @@ int main(int argc, char* argv[]) {
   if (method < 0 || method > 2) {
     std::cerr << "METHOD " << method << " is not part of the MI355X backend (METHOD 0, 1 and 2 only)\n";
     return 3;
+  }
+  if (gnc_on && method != 0) {
+    std::cerr << "--gnc runs on METHOD 0 only (the weights take the place of DCS / the switches)\n";
+    return -1;
   }
   try {
     std::cout << "Start Reading PoseGraph\n";
@@ -132,7 +144,31 @@ int main(int argc, char* argv[]) {
                 << " edges, cost " << coarse.s.initial_cost << " -> " << coarse.s.final_cost << " in " << coarse.s.iterations << " iterations"
                 << std::endl;
     }
-    pgo::Solve(options, &problem, &summary);
+    if (gnc_on) {   // graduated non-convexity over the closure and bogus blocks (added after the odometry blocks, above)
+      pgo::GncOptions gnc;
+      gnc.cbar = gnc_cbar;
+      gnc.inner_iterations = gnc_inner;
+      const size_t n_odo = g2o_manager.nEdgesOdometry.size(), n_all = (size_t)problem.NumResidualBlocks();
+      gnc.select.assign(n_all, 1);
+      std::fill(gnc.select.begin(), gnc.select.begin() + (long)n_odo, (uint8_t)0);
+      pgo::GncSummary gs;
+      options.minimizer_progress_to_stdout = false;
+      pgo::SolveGnc(options, gnc, &problem, &gs);
+      std::cout << "gnc: cbar " << gnc_cbar << ", " << gs.g.n_selected << " selected blocks, rmax2 " << gs.g.rmax2 << ", mu0 " << gs.g.mu0 << "\n";
+      for (size_t k = 0; k < gs.rounds.size(); ++k)
+        std::cout << "gnc round " << k + 1 << ": mu " << gs.rounds[k].mu << " weighted_cost " << gs.rounds[k].weighted_cost << " nonbinary "
+                  << gs.rounds[k].n_nonbinary << " zero " << gs.rounds[k].n_zero << " lm_iterations " << gs.rounds[k].lm_iterations
+                  << " lm_termination " << gs.rounds[k].lm_termination << "\n";
+      std::cout << "gnc: " << gs.g.rounds << " rounds" << (gs.g.hit_max_rounds ? " (max_rounds reached)" : "") << ", " << gs.g.n_zero
+                << " blocks at weight 0" << std::endl;
+      summary = gs.final_solve;
+      std::ofstream wf(save + "/weights.txt");
+      wf.precision(17);
+      for (double w : gs.weights) wf << w << "\n";
+      if (!wf) throw std::runtime_error("cannot write " + save + "/weights.txt");
+    } else {
+      pgo::Solve(options, &problem, &summary);
+    }
     std::cout << summary.FullReport() << std::endl;
 
     g2o_manager.writePoseGraph_nodes(save + "/opt_nodes.txt", precision);

@@ -172,6 +172,23 @@ struct Summary {
 };
 }  // namespace Solver
 
+// Graduated non-convexity with the TLS surrogate (include/pgo.h, "graduated non-convexity"; pgo_gnc_solve) around the
+// problem's solves.  The problem must be a METHOD 0 one (no DCS, no switchable blocks).
+struct GncOptions {
+  double cbar = 0.0;                 // no default: the residual norm above which a block is an outlier
+  double mu_factor = 1.4;
+  int inner_iterations = 5, final_iterations = 50, max_rounds = 100;
+  // one byte per residual block, in the order the blocks were added: non-zero = the block takes part.  Empty: the blocks the
+  // problem classifies as other than kind 0 (odometry) -- in a METHOD 0 problem every block is kind 0, so name the loops here
+  std::vector<uint8_t> select;
+};
+struct GncSummary {
+  pgo_gnc_summary g{};
+  std::vector<pgo_gnc_round> rounds;
+  std::vector<double> weights;       // per residual block, after the call
+  Solver::Summary final_solve;       // the last solve's summary and iteration records
+};
+
 struct SolverAccess {
   static void check(int st) {
     if (st != PGO_OK) throw std::runtime_error(std::string("pgo: ") + pgo_strerror(st) + ": " + pgo_last_error());
@@ -269,6 +286,26 @@ struct SolverAccess {
     pgo_t* h = Prepare(opt, pr);
     const int st = pgo_solve(h, &sum->s);
     Finish(pr, h, st, sum);
+  }
+  static void SolveGnc(const Solver::Options& opt, const GncOptions& gnc, Problem* pr, GncSummary* sum) {
+    const size_t E = pr->ia_.size();
+    if (!gnc.select.empty() && gnc.select.size() != E) throw std::invalid_argument("GncOptions::select: one byte per residual block");
+    pgo_t* h = Prepare(opt, pr);
+    pgo_gnc_options o;
+    pgo_gnc_options_default(&o);
+    o.cbar = gnc.cbar;
+    o.mu_factor = gnc.mu_factor;
+    o.inner_iters = gnc.inner_iterations;
+    o.final_iters = gnc.final_iterations;
+    o.max_rounds = gnc.max_rounds;
+    o.select = gnc.select.empty() ? nullptr : gnc.select.data();
+    sum->rounds.assign((size_t)(gnc.max_rounds > 0 ? gnc.max_rounds : 0), pgo_gnc_round());
+    int st = pgo_gnc_solve(h, &o, &sum->g, sum->rounds.data(), (int32_t)sum->rounds.size());
+    sum->rounds.resize((size_t)(st == PGO_OK ? sum->g.rounds : 0));
+    sum->weights.assign(E, 1.0);
+    if (st == PGO_OK && E > 0) st = pgo_get_edge_weights(h, sum->weights.data());
+    sum->final_solve.s = sum->g.final_solve;
+    Finish(pr, h, st, &sum->final_solve);
   }
   // Hierarchical initialisation (include/pgo.h): the problem's graph coarsened at `stride`, the coarse graph solved exactly (the
   // problem's METHOD, pcg_rtol 1e-10, everything else left to the library; a constant block that is a key pose stays the
@@ -413,6 +450,10 @@ inline void Solve(const Solver::Options& opt, Problem* problem, Solver::Summary*
 inline void InitializeHierarchical(Problem* problem, int stride, const Solver::Options& opt = Solver::Options(),
                                    Solver::Summary* coarse_summary = nullptr) {
   SolverAccess::InitializeHierarchical(opt, problem, stride, coarse_summary);
+}
+// Solve with graduated non-convexity: the parameter blocks end at the final solve's poses, summary->weights at the weights
+inline void SolveGnc(const Solver::Options& opt, const GncOptions& gnc, Problem* problem, GncSummary* summary) {
+  SolverAccess::SolveGnc(opt, gnc, problem, summary);
 }
 // many independent problems at once; summaries->size() == problems.size() afterwards
 inline void SolveBatch(const Solver::Options& opt, const std::vector<Problem*>& problems, std::vector<Solver::Summary>* summaries,
