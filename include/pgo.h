@@ -852,6 +852,76 @@ int  pgo_gnc_update(pgo_t* h, double cbar, double mu, const uint8_t* select_or_n
 int  pgo_gnc_solve(pgo_t* h, const pgo_gnc_options* opt, pgo_gnc_summary* summary_or_null,
                    pgo_gnc_round* rounds_or_null, int32_t rounds_cap);                                            /* [gpu] */
 
+/* ---------------------------------------------------------------- loop support (odometry cycle consistency)
+ * Judge loop edges WITHOUT looking at the estimate: two loop closures taken a few steps apart must close a 4-cycle through the
+ * odometry between their ends (the pairwise check of PCM / RRR, restricted to neighbours along the chain, where the odometry
+ * path is short and the test is sharp).  Caller's numbering throughout; csrc/loop_support.h is the one statement.
+ * - Chain.  As pgo_coarsen: the pair (i, i + 1) is joined by the first edge between the two in the caller's order, in either
+ *   orientation; Z_i is its motion from i to i + 1.  A pair without one: PGO_ERR_UNSUPPORTED, pgo_last_error names the first.
+ * - Trajectory.  T_0 = (0, 0, 0), T_{i+1} = T_i o Z_i (angles plain sums, not wrapped); O(p, q) = T_p^-1 o T_q.
+ * - Selected loops.  An edge that is not a chain edge and either select == NULL and kind != PGO_EDGE_ODOMETRY, or its byte in
+ *   select (E bytes, caller's order) is non-zero.  A chain edge named by select is simply not selected.  The pgo_set_active mask
+ *   plays no part (as in pgo_edge_chi2 and pgo_coarsen): this is the test that decides what to activate.
+ * - Canonical form of the loop e = (a, b, m): lo = min(a, b), hi = max(a, b), M_e = m if a < b, else m^-1.
+ * - Neighbours.  f is a neighbour of e when f is selected, f != e as an edge index (duplicates of e count),
+ *   |lo_e - lo_f| <= window and |hi_e - hi_f| <= window.
+ * - Cycle error of the pair: Err = M_e o O(hi_e, hi_f) o M_f^-1 o O(lo_f, lo_e).  With L = |lo_e - lo_f| + |hi_e - hi_f|,
+ *     q(e, f) = max((Err.x^2 + Err.y^2) / (tol_xy^2 (2 + L)), wrap(Err.th)^2 / (tol_th^2 (2 + L)));
+ *   the pair is consistent iff q <= 1; a q that is not finite is not consistent.
+ * - Every edge gets one `struct pgo_loop_support` record, in the caller's order; an edge that is not selected gets
+ *   {selected 0, n_pairs 0, n_consistent 0, best -1, q_min -1}.  The totals run over the selected edges.
+ * - Errors.  A selected or chain measurement that is not finite: PGO_ERR_NUMERIC, pgo_last_error names the smallest such edge.
+ *   PGO_ERR_INVALID_ARG: window outside 1 .. PGO_LOOP_SUPPORT_MAX_WINDOW, tol_xy or tol_th not finite or not > 0,
+ *   min_support < 1, a null pointer, n_poses < 2, an endpoint out of range.
+ * - Defaults: window 32, tol_xy 0.1, tol_th 0.05, min_support 1, apply 0.  The tolerances are five times the per-step odometry
+ *   noise of pgo_synth_manhattan (0.02 m, 0.01 rad): they are the allowance per sqrt(step) of odometry in the cycle.  A REAL
+ *   DATASET NEEDS THE CALLER'S OWN VALUES, from its odometry's noise.
+ * pgo_loop_support_plan is the serial statement on arrays: T folded left to right (T_or_null receives it, N x 3); the
+ * neighbours may be scanned in any order -- the counts and the minimum (ties to the smallest edge index) do not depend on it.
+ * pgo_loop_support runs the same statement on the measurements the handle holds on the device.  T is a three-level scan (one
+ * wavefront per segment of 256 poses folds and scans its chain motions, one workgroup scans the segment ends, one lane per
+ * pose composes the two), the selected loops are sorted by (lo, edge index) on the host at the first call for a selection and
+ * kept with a first[] array over the poses, so that a loop's candidates are one contiguous range of the table, and
+ * k_loop_support takes one loop per lane in that order.  No atomics, fixed trees: two calls are bitwise equal, a handle with
+ * pose_ordering 1 gives bitwise what one with 0 gives, and the grid plays no part; the result agrees with the plan up to the
+ * association of the compositions in T.
+ * With opt.apply != 0 every selected edge gets the weight 1 if n_consistent >= min_support, else 0, in the handle's edge weight
+ * plane (created at all ones at its first use; every other edge keeps its weight -- as pgo_gnc_update); a solve begun with
+ * pgo_lm_begin is stale afterwards, and the refusals are those of pgo_set_edge_weights.  With apply == 0 any METHOD and
+ * info_weighting are fine, no plane is created and the handle is left exactly as it was: a following pgo_lm_step gives
+ * bitwise the records and poses it gives without the call.
+ * PGO_ERR_UNSUPPORTED: a communicator, PGO_FORCE_COLLECTIVES=1, a batched handle.  Nothing changes on error.                 */
+#define PGO_LOOP_SUPPORT_MAX_WINDOW 256
+typedef struct pgo_loop_support_options {
+  int32_t window;         /* 32 */
+  int32_t min_support;    /* 1 */
+  int32_t apply;          /* 0 */
+  int32_t _pad;
+  double  tol_xy;         /* 0.1 */
+  double  tol_th;         /* 0.05 */
+} pgo_loop_support_options;
+struct pgo_loop_support {   /* (a tag only: the name is also the [gpu] call's; pgo_loop_support_record is its typedef) */
+  int32_t selected;       /* 0 or 1 */
+  int32_t n_pairs;        /* number of neighbours */
+  int32_t n_consistent;   /* number of consistent neighbours */
+  int32_t best;           /* edge index of the neighbour with the smallest finite q (ties: the smallest index); -1 if none */
+  double  q_min;          /* that q; -1 if none */
+};
+typedef struct pgo_loop_support pgo_loop_support_record;
+typedef struct pgo_loop_support_stats {
+  int64_t n_pairs_total;
+  int32_t n_selected;
+  int32_t n_supported;    /* selected edges with n_consistent >= min_support */
+  int32_t max_pairs;
+  int32_t _pad;
+} pgo_loop_support_stats;
+void pgo_loop_support_options_default(pgo_loop_support_options*);                                                 /* [host] */
+int  pgo_loop_support_plan(int32_t n_poses, int32_t n_edges, const int32_t* ia, const int32_t* ib, const double* meas_xyt,
+                           const uint8_t* kind, const uint8_t* select_or_null, const pgo_loop_support_options* opt,
+                           pgo_loop_support_record* out /* E */, pgo_loop_support_stats* stats, double* T_or_null /* N x 3 */); /* [host] */
+int  pgo_loop_support(pgo_t* h, const pgo_loop_support_options* opt, const uint8_t* select_or_null,
+                      pgo_loop_support_record* out_or_null /* E */, pgo_loop_support_stats* stats_or_null);               /* [gpu] */
+
 /* ---------------------------------------------------------------- hierarchical initialisation
  * Start a large solve near its answer (HOG-Man style): collapse every `stride` consecutive poses onto a key pose, carry every
  * other edge to the key poses along the odometry chain, solve that small graph exactly with a handle of its own, and spread the
@@ -977,6 +1047,9 @@ int pgo_debug_normal_eq(pgo_t* h, double* g_or_null, double* hdiag_or_null);    
  *                        one per unit of work (read per call; the results are bitwise the same)
  *   "gnc_grid"           n > 0 = pgo_gnc_update (and pgo_gnc_solve through it) launches n workgroups over its chunks of 256 edges
  *                        instead of one per chunk (read per call; the results are bitwise the same)
+ *   "support_grid"       n > 0 = pgo_loop_support launches n workgroups over its segments, poses, loops and chunks of 256 edges
+ *                        instead of one per unit of work (read per call; the trajectory is computed at a handle's first call; the
+ *                        results are bitwise the same)
  * Unknown name: PGO_ERR_INVALID_ARG.                                                                     */
 int pgo_debug_set_knob(const char* name, long long value);                        /* [host] */
 /* sharding plan of a graph over `world` ranks: for rank r, rows [lo, hi) and the

@@ -27,7 +27,8 @@ __all__ = ["PgoError", "Options", "Summary", "IterRecord", "ReadG2O", "Graph", "
            "window_plan", "WindowResult", "WINDOW_MAX_POSES", "WINDOW_MAX_EDGES", "WINDOW_MAX_ITERS",
            "synth_manhattan_truth", "trajectory_error", "TrajOptions", "TrajError", "EdgeWeight", "SCORE_POSES_PER_WG",
            "coarsen_plan", "prolong_eval", "COARSEN_MIN_STRIDE", "COARSEN_MAX_STRIDE",
-           "gnc_weight_eval", "GncStats", "GncOptions", "GncRound", "GncSummary"]
+           "gnc_weight_eval", "GncStats", "GncOptions", "GncRound", "GncSummary",
+           "loop_support_plan", "LoopSupportOptions", "LoopSupportRecord", "LoopSupportStats", "LOOP_SUPPORT_MAX_WINDOW"]
 
 EDGE_ODOMETRY, EDGE_CLOSURE, EDGE_BOGUS = 0, 1, 2
 TERMINATION = {1: "CONVERGENCE_FTOL", 2: "CONVERGENCE_GTOL", 3: "CONVERGENCE_PTOL", 4: "NO_CONVERGENCE",
@@ -59,7 +60,9 @@ EXPORTS = [
     "pgo_synth_manhattan_truth", "pgo_traj_options_default", "pgo_trajectory_error_eval", "pgo_trajectory_error", "pgo_edge_weights",
     "pgo_coarsen_plan", "pgo_prolong_eval", "pgo_coarsen", "pgo_prolong",
     "pgo_set_edge_weights", "pgo_get_edge_weights", "pgo_gnc_options_default", "pgo_gnc_weight_eval", "pgo_gnc_update", "pgo_gnc_solve",
+    "pgo_loop_support_options_default", "pgo_loop_support_plan", "pgo_loop_support",
 ]
+LOOP_SUPPORT_MAX_WINDOW = 256   # PGO_LOOP_SUPPORT_MAX_WINDOW
 COARSEN_MIN_STRIDE, COARSEN_MAX_STRIDE = 2, 256   # PGO_COARSEN_*_STRIDE (include/pgo.h)
 SCORE_POSES_PER_WG = 512   # PGO_SCORE_POSES_PER_WG
 WINDOW_MAX_POSES, WINDOW_MAX_EDGES, WINDOW_MAX_ITERS = 64, 256, 32   # PGO_WINDOW_MAX_* (include/pgo.h)
@@ -312,6 +315,34 @@ class GncSummary(C.Structure):
         return d
 
 
+class LoopSupportOptions(C.Structure):
+    """mirror of pgo_loop_support_options (defaults: pgo_loop_support_options_default)"""
+    _fields_ = [("window", C.c_int32), ("min_support", C.c_int32), ("apply", C.c_int32), ("_pad", C.c_int32),
+                ("tol_xy", C.c_double), ("tol_th", C.c_double)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().pgo_loop_support_options_default(C.byref(self))
+        for k, v in kw.items():
+            if k not in ("window", "min_support", "apply", "tol_xy", "tol_th"):
+                raise TypeError("unknown loop support option " + k)
+            setattr(self, k, v)
+
+
+class LoopSupportRecord(C.Structure):
+    """mirror of pgo_loop_support: one edge of loop_support_plan / Solver.loop_support"""
+    _fields_ = [("selected", C.c_int32), ("n_pairs", C.c_int32), ("n_consistent", C.c_int32), ("best", C.c_int32),
+                ("q_min", C.c_double)]
+
+
+class LoopSupportStats(C.Structure):
+    _fields_ = [("n_pairs_total", C.c_int64), ("n_selected", C.c_int32), ("n_supported", C.c_int32), ("max_pairs", C.c_int32),
+                ("_pad", C.c_int32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "_pad"}
+
+
 _LIB = None
 
 
@@ -453,6 +484,11 @@ def lib():
     L.pgo_gnc_weight_eval.argtypes = [C.c_double, C.c_double, C.c_int32, dp, dp]
     L.pgo_gnc_update.argtypes = [vp, C.c_double, C.c_double, bp, C.POINTER(GncStats)]
     L.pgo_gnc_solve.argtypes = [vp, C.POINTER(GncOptions), C.POINTER(GncSummary), C.POINTER(GncRound), C.c_int32]
+    L.pgo_loop_support_options_default.argtypes = [C.POINTER(LoopSupportOptions)]
+    L.pgo_loop_support_options_default.restype = None
+    L.pgo_loop_support_plan.argtypes = [C.c_int32, C.c_int32, ip, ip, dp, bp, bp, C.POINTER(LoopSupportOptions), C.POINTER(LoopSupportRecord),
+                                        C.POINTER(LoopSupportStats), dp]
+    L.pgo_loop_support.argtypes = [vp, C.POINTER(LoopSupportOptions), bp, C.POINTER(LoopSupportRecord), C.POINTER(LoopSupportStats)]
     _LIB = L
     return L
 
@@ -638,6 +674,34 @@ def gnc_weight_eval(cbar, mu, s):
     out = np.zeros(s.shape)
     _check(lib().pgo_gnc_weight_eval(float(cbar), float(mu), s.size, _dp(s.reshape(-1)), _dp(out.reshape(-1))))
     return out
+
+
+def _support_records(res, n):
+    return np.ctypeslib.as_array(res)[:n].copy() if n else np.zeros(0, np.dtype(LoopSupportRecord))
+
+
+def loop_support_plan(n_poses, ia, ib, meas, kind, select=None, window=32, tol_xy=0.1, tol_th=0.05, min_support=1, want_T=False):
+    """pgo_loop_support_plan (host only), the serial statement of Solver.loop_support: every selected loop (default: the edges
+    with kind != 0 that are not chain edges; else a mask over the edges) against its neighbours along the odometry chain --
+    the selected loops whose ends lie within `window` poses of its own -- through the 4-cycle the two close with the odometry.
+    Returns (records, stats): a structured array over the edges with the fields of LoopSupportRecord (selected, n_pairs,
+    n_consistent, best, q_min) and the dict of LoopSupportStats; with want_T also the (n_poses, 3) odometry trajectory.
+    The default tolerances fit synth_manhattan's odometry noise: a real dataset needs its own."""
+    ia = np.ascontiguousarray(ia, np.int32)
+    ib = np.ascontiguousarray(ib, np.int32)
+    meas = np.ascontiguousarray(meas, np.float64).reshape(-1, 3)
+    kind = np.ascontiguousarray(kind, np.uint8)
+    if not (len(ia) == len(ib) == len(kind) == len(meas)):
+        raise ValueError("loop_support_plan: ia, ib, meas and kind must have one entry per edge")
+    m = _mask(select, len(ia), "select")
+    o = LoopSupportOptions(window=int(window), tol_xy=float(tol_xy), tol_th=float(tol_th), min_support=int(min_support))
+    res = (LoopSupportRecord * max(len(ia), 1))()
+    st = LoopSupportStats()
+    T = np.zeros((max(int(n_poses), 1), 3)) if want_T else None
+    _check(lib().pgo_loop_support_plan(n_poses, len(ia), _ip(ia), _ip(ib), _dp(meas), _bp(kind), _bp(m) if m is not None else None,
+                                       C.byref(o), res, C.byref(st), _dp(T)))
+    rec = _support_records(res, len(ia))
+    return (rec, st.as_dict(), T[:int(n_poses)]) if want_T else (rec, st.as_dict())
 
 
 def shard_plan(n_poses, ia, ib, world, rank, row_align=1):
@@ -1082,6 +1146,18 @@ class Solver:
         _check(lib().pgo_gnc_solve(self._h, C.byref(o), C.byref(summ), rounds, cap))
         return summ.as_dict(), [rounds[k].as_dict() for k in range(min(summ.rounds, cap))]
 
+    def loop_support(self, select=None, window=32, tol_xy=0.1, tol_th=0.05, min_support=1, apply=False):
+        """pgo_loop_support: loop_support_plan on the measurements the handle holds on the device; the estimate plays no part.
+        apply=True writes the verdict into the edge weight plane (METHOD 0 / 1): every selected edge gets 1 if it has at least
+        min_support consistent neighbours, else 0; every other edge keeps its weight.  Returns (records, stats)."""
+        m = _mask(select, self.n_edges, "select")
+        o = LoopSupportOptions(window=int(window), tol_xy=float(tol_xy), tol_th=float(tol_th), min_support=int(min_support),
+                               apply=int(bool(apply)))
+        res = (LoopSupportRecord * max(self.n_edges, 1))()
+        st = LoopSupportStats()
+        _check(lib().pgo_loop_support(self._h, C.byref(o), _bp(m) if m is not None else None, res, C.byref(st)))
+        return _support_records(res, self.n_edges), st.as_dict()
+
     def coarsen(self, stride: int):
         """pgo_coarsen: the coarse graph of the handle's measurements at `stride` (see coarsen_plan), with the handle's current
         poses at the key poses as its initial poses.  Returns (Graph, origin): origin[e] = the fine edge behind coarse edge e,
@@ -1102,18 +1178,24 @@ class Solver:
             raise ValueError(f"prolong: {len(X)} coarse poses, expected {(self.n_poses + s - 1) // s}")
         _check(lib().pgo_prolong(self._h, s, _dp(X)))
 
-    def initialize_hierarchical(self, stride: int, coarse_options: "Options | None" = None, device: int = 0) -> Summary:
+    def initialize_hierarchical(self, stride: int, coarse_options: "Options | None" = None, device: int = 0,
+                                carry_weights: bool = False) -> Summary:
         """coarsen -> a solver on the coarse graph -> solve -> prolong: the handle's poses start the fine solve near the answer
         of the coarse one.  coarse_options (default: the handle's method, pcg_rtol 1e-10 -- the exact mode --, everything else
-        left to the library; a fixed pose that is a key pose stays the fixed pose).  Returns the coarse solve's Summary."""
+        left to the library; a fixed pose that is a key pose stays the fixed pose).  carry_weights: every coarse edge takes the
+        weight its fine edge has in the handle's weight plane (after loop_support(apply=True): the coarse solve runs without
+        the dropped loops); the composites of the chain have weight 1.  Returns the coarse solve's Summary."""
         s = int(stride)
-        graph, _ = self.coarsen(s)
+        graph, origin = self.coarsen(s)
         if coarse_options is None:
             f = int(self.options.fixed_pose)
             coarse_options = Options(method=int(self.options.method), pcg_rtol=1e-10,
                                      fixed_pose=(f if f < 0 else (f // s if f % s == 0 else 0)))
         coarse = Solver(graph, coarse_options, device=device)
         try:
+            if carry_weights:
+                w = self.get_edge_weights()
+                coarse.set_edge_weights(np.where(origin >= 0, w[np.maximum(origin, 0)], 1.0))
             summary = coarse.solve()
             self.prolong(s, coarse.poses())
         finally:

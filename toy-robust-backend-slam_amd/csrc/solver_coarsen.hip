@@ -30,8 +30,8 @@ inline bool kept(const std::vector<int32_t>& chain, const int32_t* ia, const int
 }  // namespace
 
 // the tables in the caller's numbering, once per handle
-int pgo_handle::coarsen_tables(const char* who) {
-  if (cs_ready) return PGO_OK;
+int pgo_handle::coarsen_tables(const char* who, bool all_finite) {
+  if (cs_ready) return all_finite && cs_bad >= 0 ? not_finite(who, cs_bad) : PGO_OK;
   const int64_t N = S.n_poses, EL = S.n_edges_local, E = n_edges_total;   // (one rank: every edge is local)
   if (EL != E) return fail(PGO_ERR_UNSUPPORTED, std::string(who) + ": one rank only");
   std::vector<int32_t> inv;   // internal position -> caller's pose
@@ -50,7 +50,7 @@ int pgo_handle::coarsen_tables(const char* who) {
     kd[e] = kind_local[k];
     if (!pgo::coarsen_finite3(S.mx[k], S.my[k], S.mt[k]) && (bad < 0 || e < bad)) bad = e;
   }
-  if (bad >= 0) return not_finite(who, bad);
+  if (bad >= 0 && all_finite) return not_finite(who, bad);
   const int32_t gap = pgo::pick_chain_edges((int32_t)N, E, ea.data(), eb.data(), &chain);
   if (gap >= 0) return no_chain(who, gap);
   std::vector<int32_t> tab((size_t)(N + 3 * E) + (size_t)((E + 3) / 4), 0);
@@ -73,6 +73,7 @@ int pgo_handle::coarsen_tables(const char* who) {
   cs_ea_h.swap(ea);
   cs_eb_h.swap(eb);
   cs_loc_h.swap(loc);
+  cs_bad = bad;
   cs_ready = true;
   return PGO_OK;
 }

@@ -11,6 +11,7 @@
 //   solver_score.hip    pgo_trajectory_error, pgo_edge_weights: scoring a solve on the device (score.hip.h, traj_error.h)
 //   solver_coarsen.hip  pgo_coarsen, pgo_prolong: a coarse graph along the odometry chain and back (coarsen.hip.h, coarsen.h)
 //   solver_gnc.hip      pgo_set_edge_weights, pgo_gnc_update, pgo_gnc_solve: the edge weight plane and GNC-TLS (gnc.hip.h, gnc.h)
+//   solver_support.hip  pgo_loop_support: loop edges judged by odometry cycle consistency (loop_support.hip.h, loop_support.h)
 // Every kernel header declares its kernels `static`: a translation unit carries the kernels it launches.
 //
 // Replaces, for DCS-ceres/main.cpp METHOD 0/1 (paths relative to /root/reference/DCS-ceres):
@@ -548,9 +549,24 @@ struct pgo_handle {
   int64_t cs_comp_cap = 0, cs_work_cap = 0;
   int32_t cs_stride = 0;
   std::vector<uint8_t> cs_host;   // host image of a call's outputs
-  int coarsen_tables(const char* who);
+  int64_t cs_bad = -1;            // the smallest edge whose measurement is not finite (-1: none), found when the tables were built
+  int coarsen_tables(const char* who, bool all_finite = true);   // all_finite: such an edge is PGO_ERR_NUMERIC
   int coarsen(int32_t stride, pgo_graph** coarse_out, int32_t* origin, int32_t origin_cap, int32_t* n_coarse_edges);
   int prolong(int32_t stride, const double* coarse_xyt);
+
+  // loop support (pgo_loop_support; solver_support.hip).  It walks the tables of pgo_coarsen (cs_tab).  ls_traj = the trajectory
+  // T (N x 5) | the segment ends | the key poses, computed at the first call and kept (measurements never change on a handle).
+  // ls_tab = the table of a selection -- the loops sorted by (lo, edge) | first [N + 1] | slot of every edge | M^-1 per slot --,
+  // built on the host at the first call for that selection (ls_sel_h: its bytes) and kept; ls_work = a call's per-slot results,
+  // records, chunk totals and statistics.  Both are grown on demand and kept (win_reserve).
+  bool ls_traj_ready = false, ls_tab_ready = false;
+  double* ls_traj = nullptr;
+  std::vector<uint8_t> ls_sel_h;
+  int32_t ls_n_sel = 0;
+  void *ls_tab = nullptr, *ls_work = nullptr;
+  int64_t ls_tab_cap = 0, ls_work_cap = 0;
+  std::vector<uint8_t> ls_host;   // host image of a call's outputs
+  int loop_support(const pgo_loop_support_options* o, const uint8_t* select_or_null, pgo_loop_support_record* out, pgo_loop_support_stats* stats);
 
   int create(int32_t N, const double* poses_h, int32_t E, const int32_t* ia, const int32_t* ib, const double* meas,
              const double* info6, const uint8_t* kind);

@@ -1,6 +1,7 @@
 // Command-line front end with the reference's run contract (DCS-ceres/main.cpp:22-40, do_build.sh:10):
 //     ./main DATASET NUM_OUTLIER_LOOPS METHOD [--seed S] [--data DIR] [--save DIR] [--device D] [--precision P]
 //            [--loss NAME[:A]] [--loop-loss NAME[:A]] [--score FILE [--align]] [--init-stride S] [--gnc CBAR [--gnc-inner K]]
+//            [--loop-support MIN[:WINDOW[:TOL_XY[:TOL_TH]]]]
 // METHOD 0 = baseline, 1 = DCS, 2 = switchable constraints run on the MI355X backend; 3/4 are outside it (exit code 3).
 // Reads DIR/DATASET.g2o (default ../data, as the reference), writes init_/opt_ nodes+edges text files that
 // drawer/plot_results.py consumes (default ../save; unlike the reference the directory is created).
@@ -48,6 +49,10 @@ int main(int argc, char* argv[]) {
               << "       [--gnc CBAR [--gnc-inner K]]  (METHOD 0 only: graduated non-convexity with the TLS surrogate over the closure and bogus\n"
               << "       blocks, CBAR = the residual norm above which a block is an outlier, K LM iterations per round, default 5; prints the\n"
               << "       rounds and writes weights.txt, one weight per edge in the order of the edges files)\n"
+              << "       [--loop-support MIN[:WINDOW[:TOL_XY[:TOL_TH]]]]  (METHOD 0 and 1: before anything else, judge the closure and bogus blocks\n"
+              << "       by odometry cycle consistency and drop -- weight 0 -- those with fewer than MIN consistent neighbours within WINDOW\n"
+              << "       poses, default 32; tolerances per sqrt(step), default 0.1 m and 0.05 rad: fit them to the dataset's odometry;\n"
+              << "       --init-stride and --gnc then run without the dropped blocks; writes weights.txt)\n"
               << "METHOD: 0=baseline, 1=DCS, 2=Switchable (3=Layer, 4=Simple Layer MCTS: not in this backend)\n"
               << "Example: " << argv[0] << " INTEL 50 1\n";
     return -1;
@@ -56,7 +61,8 @@ int main(int argc, char* argv[]) {
   long long seed = -1;
   int device = 0, precision = 0, score_align = 0, init_stride = 0, gnc_inner = 5;
   double gnc_cbar = 0.0;
-  bool gnc_on = false;
+  bool gnc_on = false, support_on = false;
+  pgo::LoopSupportOptions support;
   for (int i = 4; i < argc; i += 2) {
     if (!strcmp(argv[i], "--align")) {   // (the one option without a value)
       score_align = 1;
@@ -75,6 +81,21 @@ int main(int argc, char* argv[]) {
     else if (!strcmp(argv[i], "--init-stride")) init_stride = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "--gnc")) { gnc_on = true; gnc_cbar = atof(argv[i + 1]); }
     else if (!strcmp(argv[i], "--gnc-inner")) gnc_inner = atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "--loop-support")) {   // MIN[:WINDOW[:TOL_XY[:TOL_TH]]]
+      support_on = true;
+      std::vector<std::string> f;
+      std::string spec = argv[i + 1];
+      for (size_t at = 0; at <= spec.size();) {
+        const size_t colon = std::min(spec.find(':', at), spec.size());
+        f.push_back(spec.substr(at, colon - at));
+        at = colon + 1;
+      }
+      if (f.size() > 4 || f[0].empty()) { std::cerr << "--loop-support MIN[:WINDOW[:TOL_XY[:TOL_TH]]]\n"; return -1; }
+      support.min_support = atoi(f[0].c_str());
+      if (f.size() > 1) support.window = atoi(f[1].c_str());
+      if (f.size() > 2) support.tol_xy = atof(f[2].c_str());
+      if (f.size() > 3) support.tol_th = atof(f[3].c_str());
+    }
     else { std::cerr << "unknown option " << argv[i] << "\n"; return -1; }
   }
   std::unique_ptr<pgo::LossFunction> loss_function, loop_loss;
@@ -93,6 +114,10 @@ int main(int argc, char* argv[]) {
   }
   if (gnc_on && method != 0) {
     std::cerr << "--gnc runs on METHOD 0 only (the weights take the place of DCS / the switches)\n";
+    return -1;
+  }
+  if (support_on && method == 2) {
+    std::cerr << "--loop-support writes edge weights: METHOD 0 and 1 only\n";
     return -1;
   }
   try {
@@ -135,6 +160,22 @@ int main(int argc, char* argv[]) {
     options.linear_solver_type = pgo::SPARSE_NORMAL_CHOLESKY;
     options.device = device;
     pgo::Solver::Summary summary;
+    const size_t n_odo = g2o_manager.nEdgesOdometry.size(), n_all = (size_t)problem.NumResidualBlocks();
+    if (support_on) {   // the closure and bogus blocks (added after the odometry blocks, above) judged by odometry cycle consistency
+      support.apply = true;
+      support.select.assign(n_all, 1);
+      std::fill(support.select.begin(), support.select.begin() + (long)n_odo, (uint8_t)0);
+      pgo::LoopSupportSummary ss;
+      pgo::LoopSupport(options, support, &problem, &ss);
+      const size_t n_clo = g2o_manager.nEdgesClosure.size();
+      size_t drop_clo = 0, drop_bogus = 0;
+      for (size_t e = n_odo; e < n_all; ++e)
+        if (ss.blocks[e].selected && ss.blocks[e].n_consistent < support.min_support) ++(e < n_odo + n_clo ? drop_clo : drop_bogus);
+      std::cout << "loop-support: min " << support.min_support << " window " << support.window << " tol_xy " << support.tol_xy << " tol_th "
+                << support.tol_th << ": " << ss.stats.n_selected << " selected blocks, " << ss.stats.n_supported << " supported, dropped "
+                << drop_clo << " closure and " << drop_bogus << " bogus; " << ss.stats.n_pairs_total << " pairs, at most " << ss.stats.max_pairs
+                << " per block" << std::endl;
+    }
     if (init_stride != 0) {   // hierarchical initialisation: the parameter blocks start at the coarse graph's prolonged solution
       pgo::Solver::Options coarse_options;
       coarse_options.device = device;
@@ -148,9 +189,10 @@ int main(int argc, char* argv[]) {
       pgo::GncOptions gnc;
       gnc.cbar = gnc_cbar;
       gnc.inner_iterations = gnc_inner;
-      const size_t n_odo = g2o_manager.nEdgesOdometry.size(), n_all = (size_t)problem.NumResidualBlocks();
       gnc.select.assign(n_all, 1);
       std::fill(gnc.select.begin(), gnc.select.begin() + (long)n_odo, (uint8_t)0);
+      for (size_t e = 0; e < problem.ResidualBlockWeights().size(); ++e)   // (--loop-support: a dropped block stays dropped)
+        if (problem.ResidualBlockWeights()[e] == 0.0) gnc.select[e] = 0;
       pgo::GncSummary gs;
       options.minimizer_progress_to_stdout = false;
       pgo::SolveGnc(options, gnc, &problem, &gs);
@@ -168,6 +210,12 @@ int main(int argc, char* argv[]) {
       if (!wf) throw std::runtime_error("cannot write " + save + "/weights.txt");
     } else {
       pgo::Solve(options, &problem, &summary);
+      if (support_on) {
+        std::ofstream wf(save + "/weights.txt");
+        wf.precision(17);
+        for (double w : problem.ResidualBlockWeights()) wf << w << "\n";
+        if (!wf) throw std::runtime_error("cannot write " + save + "/weights.txt");
+      }
     }
     std::cout << summary.FullReport() << std::endl;
 

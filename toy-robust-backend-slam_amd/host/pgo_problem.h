@@ -102,6 +102,14 @@ class Problem {
   }
   int NumResidualBlocks() const { return (int)ia_.size(); }
   int NumParameterBlocks() const { return (int)ptr_.size(); }
+  // The weight in [0, 1] of every residual block, in the order the blocks were added (include/pgo.h, "edge weight plane"):
+  // what LoopSupport with apply left, or the caller's own.  Empty: none -- every block counts fully.  Blocks added afterwards
+  // have weight 1.  A problem with weights is a METHOD 0 or DCS one.
+  const std::vector<double>& ResidualBlockWeights() const { return weights_; }
+  void SetResidualBlockWeights(const std::vector<double>& w) {
+    if (w.size() > ia_.size()) throw std::invalid_argument("more weights than residual blocks");
+    weights_ = w;
+  }
 
  private:
   friend struct SolverAccess;
@@ -134,6 +142,7 @@ class Problem {
   std::vector<double*> switch_;                    // per residual block: its switch variable or nullptr
   std::unordered_map<double*, double> prior_lambda_;  // switch -> lambda of its prior
   bool any_dcs_ = false, any_sc_ = false;
+  std::vector<double> weights_;                    // per residual block, or empty (SetResidualBlockWeights)
 };
 
 namespace Solver {
@@ -187,6 +196,21 @@ struct GncSummary {
   std::vector<pgo_gnc_round> rounds;
   std::vector<double> weights;       // per residual block, after the call
   Solver::Summary final_solve;       // the last solve's summary and iteration records
+};
+
+// Loop edges judged by odometry cycle consistency (include/pgo.h, "loop support"; pgo_loop_support): no solve, no estimate.
+// The default tolerances fit pgo_synth_manhattan's odometry noise; a real dataset needs its own.
+struct LoopSupportOptions {
+  int window = 32, min_support = 1;
+  double tol_xy = 0.1, tol_th = 0.05;
+  bool apply = false;                // true: the verdict becomes the problem's residual block weights (1 supported, 0 not)
+  // one byte per residual block, in the order the blocks were added: non-zero = the block is a loop to judge.  Empty: the blocks
+  // the problem classifies as other than kind 0 (odometry) -- in a METHOD 0 problem every block is kind 0, so name the loops here
+  std::vector<uint8_t> select;
+};
+struct LoopSupportSummary {
+  pgo_loop_support_stats stats{};
+  std::vector<pgo_loop_support_record> blocks;   // per residual block
 };
 
 struct SolverAccess {
@@ -255,6 +279,11 @@ struct SolverAccess {
     int st = pgo_set_losses(h, (int32_t)L.size(), L.data(), E ? pr->class_.data() : nullptr);
     const std::vector<uint8_t> mask = ConstantMask(pr);
     if (st == PGO_OK && !mask.empty()) st = pgo_set_active(h, nullptr, mask.data());
+    if (st == PGO_OK && !pr->weights_.empty()) {
+      std::vector<double> w = pr->weights_;
+      w.resize((size_t)E, 1.0);
+      st = pgo_set_edge_weights(h, w.data());
+    }
     if (st != PGO_OK) {
       const std::string msg = pgo_last_error();
       pgo_destroy(h);
@@ -307,6 +336,26 @@ struct SolverAccess {
     sum->final_solve.s = sum->g.final_solve;
     Finish(pr, h, st, &sum->final_solve);
   }
+  static void LoopSupport(const Solver::Options& opt, const LoopSupportOptions& ls, Problem* pr, LoopSupportSummary* sum) {
+    const size_t E = pr->ia_.size();
+    if (!ls.select.empty() && ls.select.size() != E) throw std::invalid_argument("LoopSupportOptions::select: one byte per residual block");
+    pgo_t* h = Prepare(opt, pr);
+    pgo_loop_support_options o;
+    pgo_loop_support_options_default(&o);
+    o.window = ls.window;
+    o.min_support = ls.min_support;
+    o.tol_xy = ls.tol_xy;
+    o.tol_th = ls.tol_th;
+    o.apply = ls.apply ? 1 : 0;
+    sum->blocks.assign(E, pgo_loop_support_record());
+    int st = pgo_loop_support(h, &o, ls.select.empty() ? nullptr : ls.select.data(), sum->blocks.data(), &sum->stats);
+    std::vector<double> w(E, 1.0);
+    if (st == PGO_OK && ls.apply && E > 0) st = pgo_get_edge_weights(h, w.data());
+    const std::string msg = st != PGO_OK ? std::string(pgo_last_error()) : std::string();
+    pgo_destroy(h);
+    if (st != PGO_OK) throw std::runtime_error(std::string("pgo: ") + pgo_strerror(st) + ": " + msg);
+    if (ls.apply) pr->weights_.swap(w);
+  }
   // Hierarchical initialisation (include/pgo.h): the problem's graph coarsened at `stride`, the coarse graph solved exactly (the
   // problem's METHOD, pcg_rtol 1e-10, everything else left to the library; a constant block that is a key pose stays the
   // constant one), the result prolonged and written into the caller's parameter blocks in place -- the start of the Solve
@@ -315,7 +364,11 @@ struct SolverAccess {
     pgo_t* h = Prepare(opt, pr);
     pgo_graph* cg = nullptr;
     pgo_t* ch = nullptr;
-    int st = pgo_coarsen(h, stride, &cg, nullptr, 0, nullptr);
+    // (a problem with residual block weights: every coarse edge takes the weight of the block it came from)
+    const int32_t E = (int32_t)pr->ia_.size();
+    std::vector<int32_t> origin(pr->weights_.empty() ? 0 : (size_t)E);
+    int32_t n_coarse = 0;
+    int st = pgo_coarsen(h, stride, &cg, origin.empty() ? nullptr : origin.data(), (int32_t)origin.size(), &n_coarse);
     Solver::Summary local;
     Solver::Summary* cs = coarse_sum ? coarse_sum : &local;
     if (st == PGO_OK) {
@@ -325,6 +378,12 @@ struct SolverAccess {
       o.pcg_rtol = 1e-10;
       o.fixed_pose = pr->fixed_ < 0 ? pr->fixed_ : (pr->fixed_ % stride == 0 ? pr->fixed_ / stride : 0);
       st = pgo_create_from_graph(&ch, cg, &o, nullptr, opt.device);
+    }
+    if (st == PGO_OK && !origin.empty()) {
+      std::vector<double> cw((size_t)n_coarse, 1.0);
+      for (int32_t e = 0; e < n_coarse; ++e)
+        if (origin[e] >= 0 && (size_t)origin[e] < pr->weights_.size()) cw[e] = pr->weights_[origin[e]];
+      st = pgo_set_edge_weights(ch, cw.data());
     }
     if (st == PGO_OK) st = pgo_solve(ch, &cs->s);
     std::vector<double> X;
@@ -454,6 +513,11 @@ inline void InitializeHierarchical(Problem* problem, int stride, const Solver::O
 // Solve with graduated non-convexity: the parameter blocks end at the final solve's poses, summary->weights at the weights
 inline void SolveGnc(const Solver::Options& opt, const GncOptions& gnc, Problem* problem, GncSummary* summary) {
   SolverAccess::SolveGnc(opt, gnc, problem, summary);
+}
+// Judge the problem's loop blocks by odometry cycle consistency; with options.apply the verdict becomes the problem's residual
+// block weights, which every Solve, SolveGnc and InitializeHierarchical that follows honours
+inline void LoopSupport(const Solver::Options& opt, const LoopSupportOptions& options, Problem* problem, LoopSupportSummary* summary) {
+  SolverAccess::LoopSupport(opt, options, problem, summary);
 }
 // many independent problems at once; summaries->size() == problems.size() afterwards
 inline void SolveBatch(const Solver::Options& opt, const std::vector<Problem*>& problems, std::vector<Solver::Summary>* summaries,
