@@ -27,8 +27,7 @@ int pgo_handle::set_losses(int32_t n_classes, const pgo_loss* losses, const uint
     const int c = edge_class ? edge_class[S.orig_edge[k]] : std::min<int>(kind_local[k], n_classes - 1);
     S.flags[k] = (uint8_t)((S.flags[k] & (3u | dev::EDGE_INACTIVE)) | ((unsigned)c << 2));   // (bit 4: pgo_set_active's mask stays)
   }
-  lin_valid = false;
-  lm_active = false;
+  solve_is_stale();
   if (EL == 0) return PGO_OK;
   HIPC(hipSetDevice(device));
   PGOC(upload(e_flags, S.flags));
@@ -41,8 +40,7 @@ int pgo_handle::set_losses(int32_t n_classes, const pgo_loss* losses, const uint
 // coarse aggregates follows the resolved constant set, the direct solve steps aside while an edge of its chain is inactive,
 // and the running solve (if any) is stale.  Both NULL: the handle is as it was created.
 int pgo_handle::set_active(const uint8_t* edge_active, const uint8_t* pose_constant) {
-  if (opt.method == 2) return fail(PGO_ERR_UNSUPPORTED, "pgo_set_active: METHOD 0 and 1 only");
-  if (comm || force_collectives) return fail(PGO_ERR_UNSUPPORTED, "pgo_set_active: one rank without a communicator only");
+  PGOC(requires("pgo_set_active", METHOD_01 | ONE_RANK));
   HIPC(hipSetDevice(device));
   const int64_t EL = S.n_edges_local, N = S.n_poses;   // (one rank: every edge is local, every row owned)
   const bool restore = !edge_active && !pose_constant;
@@ -126,8 +124,7 @@ int pgo_handle::set_active(const uint8_t* edge_active, const uint8_t* pose_const
     }
     act_chain_cut = chain_cut;
   }
-  lin_valid = false;
-  lm_active = false;
+  solve_is_stale();
   if (EL > 0) PGOC(upload(e_flags, S.flags));
   if (fixed_mask) PGOC(upload(fixed_mask, restore ? fixed_mask_h : act_const_h));
   if (coarse_built) {
@@ -251,8 +248,7 @@ int pgo_set_poses(pgo_t* h, const double* poses) {
     poses = tmp.data();
   }
   HIPC(hipMemcpyAsync(h->poses, poses, (size_t)3 * h->S.n_poses * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  h->lin_valid = false;
-  h->lm_active = false;
+  h->solve_is_stale();
   return h->sync();
 }
 
@@ -311,10 +307,7 @@ int pgo_eval(pgo_t* h, const double* poses_or_null, int apply_loss, double* cost
     PGOC(h->sync());  // tmp dies with this scope
     x = h->cand;
   }
-  if (want_jac) {
-    h->lin_valid = false;  // the record buffer is about to be overwritten
-    h->lm_active = false;
-  }
+  if (want_jac) h->solve_is_stale();  // the record buffer is about to be overwritten
   PGOC(h->eval_enqueue(x, h->sw, apply_loss, want_jac, 0));
   PGOC(h->fetch_scal(0, 2));
   if (cost) *cost = h->h_scal[0];

@@ -7,19 +7,18 @@
 #include "coarsen.hip.h"
 
 namespace {
-int64_t up16(int64_t b) { return (b + 15) / 16 * 16; }
+// cs_comp = C | Cend, as pgo_coarsen writes and pgo_prolong reads them
+struct Composites {
+  pgo::Layout L;
+  pgo::Span<double> C, Cend;
+  Composites(int64_t N, int64_t K) : C(L.add<double>(3 * N)), Cend(L.add<double>(3 * (K - 1))) {}
+};
 
 int check_sizes(const std::string& who, int64_t N, int32_t stride) {
   if (stride < PGO_COARSEN_MIN_STRIDE || stride > PGO_COARSEN_MAX_STRIDE)
     return fail(PGO_ERR_INVALID_ARG, who + ": stride must be " + std::to_string(PGO_COARSEN_MIN_STRIDE) + ".." + std::to_string(PGO_COARSEN_MAX_STRIDE));
   if (N <= stride) return fail(PGO_ERR_INVALID_ARG, who + ": " + std::to_string(N) + " poses give one key pose at stride " + std::to_string(stride) + " (n_poses must exceed the stride)");
   return PGO_OK;
-}
-int no_chain(const std::string& who, int32_t gap) {
-  return fail(PGO_ERR_UNSUPPORTED, who + ": poses " + std::to_string(gap) + " and " + std::to_string(gap + 1) + " are not joined by an edge");
-}
-int not_finite(const std::string& who, int64_t e) {
-  return fail(PGO_ERR_NUMERIC, who + ": the measurement of edge " + std::to_string(e) + " is not finite");
 }
 // is caller's edge e kept on the coarse graph?  (not a chain edge, ends in two segments)
 inline bool kept(const std::vector<int32_t>& chain, const int32_t* ia, const int32_t* ib, int64_t e, int32_t S) {
@@ -64,10 +63,7 @@ int pgo_handle::coarsen_tables(const char* who, bool all_finite) {
   memcpy(tab.data() + N + 2 * E, loc.data(), (size_t)E * 4);
   memcpy(tab.data() + N + 3 * E, kd.data(), (size_t)E);
   if (!cs_tab) PGOC(dalloc(&cs_tab, (int64_t)tab.size()));
-  if (!perm.empty() && !score_perm) {
-    PGOC(dalloc(&score_perm, N));
-    PGOC(upload(score_perm, perm));
-  }
+  PGOC(perm_device());
   PGOC(upload(cs_tab, tab));
   PGOC(sync());   // (`tab` dies with this scope)
   cs_ea_h.swap(ea);
@@ -80,12 +76,10 @@ int pgo_handle::coarsen_tables(const char* who, bool all_finite) {
 
 int pgo_handle::coarsen(int32_t stride, pgo_graph** coarse_out, int32_t* origin, int32_t origin_cap, int32_t* n_coarse_edges) {
   const char* who = "pgo_coarsen";
-  if (comm || force_collectives) return fail(PGO_ERR_UNSUPPORTED, std::string(who) + ": one rank without a communicator only");
-  if (batch_mode) return fail(PGO_ERR_UNSUPPORTED, std::string(who) + ": not on a batched handle");
+  PGOC(requires(who, ONE_RANK | NOT_BATCH));
   if (!coarse_out) return fail(PGO_ERR_INVALID_ARG, std::string(who) + ": null pointer");
   const int64_t N = S.n_poses, E = n_edges_total;
   PGOC(check_sizes(who, N, stride));
-  const long long grid_knob = knob("coarsen_grid");
   HIPC(hipSetDevice(device));
   PGOC(coarsen_tables(who));
   const int64_t K = (N + stride - 1) / stride;
@@ -96,44 +90,45 @@ int pgo_handle::coarsen(int32_t stride, pgo_graph** coarse_out, int32_t* origin,
     return fail(PGO_ERR_INVALID_ARG, std::string(who) + ": the coarse graph has " + std::to_string(Ec) + " edges, origin holds " + std::to_string(origin_cap));
   // ---- buffers, before anything is enqueued: comp = C | Cend;  work = cnt | off | key poses | meas | ia | ib | origin | kind
   const int64_t nc = (E + dev::COARSEN_CHUNK - 1) / dev::COARSEN_CHUNK;
-  const int64_t c_end = 3 * N * 8, c_all = c_end + 3 * (K - 1) * 8;
-  const int64_t w_cnt = 0, w_off = w_cnt + nc * 4, w_key = up16(w_off + nc * 4), w_meas = w_key + 3 * K * 8, w_ia = w_meas + 3 * Ec * 8,
-                w_ib = w_ia + Ec * 4, w_org = w_ib + Ec * 4, w_kind = w_org + Ec * 4, w_all = w_kind + up16(Ec);
-  PGOC(win_reserve(&cs_comp, &cs_comp_cap, c_all));
-  PGOC(win_reserve(&cs_work, &cs_work_cap, w_all));
-  std::unique_ptr<pgo_graph> G(new pgo_graph);
-  cs_host.resize((size_t)(w_all - w_key));
-  cs_stride = 0;   // (C and Cend are being rewritten)
-  char* wk = static_cast<char*>(cs_work);
+  const Composites comp(N, K);
+  pgo::Layout LW;
+  const auto w_cnt = LW.add<int32_t>(nc), w_off = LW.add<int32_t>(nc);
+  const auto w_key = LW.add<double>(3 * K), w_meas = LW.add<double>(3 * Ec);   // (the copy-out: w_key to w_kind)
+  const auto w_ia = LW.add<int32_t>(Ec), w_ib = LW.add<int32_t>(Ec), w_org = LW.add<int32_t>(Ec);
+  const auto w_kind = LW.add<uint8_t>(Ec);
+  PGOC(reserve(cs_comp, comp.L.bytes()));
+  PGOC(reserve(cs_work, LW.bytes()));
   dev::CoarsenArgs A;
+  PGOC(perm_device(&A.perm));   // (coarsen_tables made it)
+  std::unique_ptr<pgo_graph> G(new pgo_graph);
+  cs_host.resize((size_t)LW.bytes());
+  cs_stride = 0;   // (C and Cend are being rewritten)
   A.mx = e_mx;
   A.my = e_my;
   A.mt = e_mt;
   A.poses = poses;
-  A.perm = perm.empty() ? nullptr : score_perm;
-  A.chain = cs_tab;
-  A.ea = cs_tab + N;
-  A.eb = cs_tab + N + E;
-  A.eloc = cs_tab + N + 2 * E;
-  A.ekind = reinterpret_cast<const uint8_t*>(cs_tab + N + 3 * E);
+  A.chain = cs_chain();
+  A.ea = cs_ea();
+  A.eb = cs_eb();
+  A.eloc = cs_eloc();
+  A.ekind = cs_ekind();
   A.n = (int32_t)N;
   A.n_edges = (int32_t)E;
   A.stride = stride;
   A.n_key = (int32_t)K;
   A.n_chunks = (int32_t)nc;
   A._pad = 0;
-  A.C = reinterpret_cast<double*>(cs_comp);
-  A.Cend = reinterpret_cast<double*>(static_cast<char*>(cs_comp) + c_end);
-  A.cnt = reinterpret_cast<int32_t*>(wk + w_cnt);
-  A.off = reinterpret_cast<int32_t*>(wk + w_off);
-  A.o_key = reinterpret_cast<double*>(wk + w_key);
-  A.o_meas = reinterpret_cast<double*>(wk + w_meas);
-  A.o_ia = reinterpret_cast<int32_t*>(wk + w_ia);
-  A.o_ib = reinterpret_cast<int32_t*>(wk + w_ib);
-  A.o_origin = reinterpret_cast<int32_t*>(wk + w_org);
-  A.o_kind = reinterpret_cast<uint8_t*>(wk + w_kind);
-  auto grid_for = [&](int64_t units) { return (int)(grid_knob > 0 ? std::min<long long>(grid_knob, 65535) : std::min<int64_t>(std::max<int64_t>(units, 1), 65535)); };
-  const int g_seg = grid_for((K + dev::WG / 64 - 1) / (dev::WG / 64)), g_chunk = grid_for(nc);
+  A.C = comp.C.in(cs_comp.p);
+  A.Cend = comp.Cend.in(cs_comp.p);
+  A.cnt = w_cnt.in(cs_work.p);
+  A.off = w_off.in(cs_work.p);
+  A.o_key = w_key.in(cs_work.p);
+  A.o_meas = w_meas.in(cs_work.p);
+  A.o_ia = w_ia.in(cs_work.p);
+  A.o_ib = w_ib.in(cs_work.p);
+  A.o_origin = w_org.in(cs_work.p);
+  A.o_kind = w_kind.in(cs_work.p);
+  const int g_seg = launch_grid("coarsen_grid", (K + dev::WG / 64 - 1) / (dev::WG / 64)), g_chunk = launch_grid("coarsen_grid", nc);
   switch ((stride + 63) / 64) {
     case 1: hipLaunchKernelGGL(dev::k_chain_compose<1>, dim3(g_seg), dim3(dev::WG), 0, stream, A); break;
     case 2: hipLaunchKernelGGL(dev::k_chain_compose<2>, dim3(g_seg), dim3(dev::WG), 0, stream, A); break;
@@ -148,18 +143,15 @@ int pgo_handle::coarsen(int32_t stride, pgo_graph** coarse_out, int32_t* origin,
   hipLaunchKernelGGL(dev::k_coarsen_edges<>, dim3(g_chunk), dim3(dev::WG), 0, stream, A);
   PGOC(check_launch("k_coarsen_edges"));
   // ---- one copy-out
-  HIPC(hipMemcpyAsync(cs_host.data(), wk + w_key, (size_t)(w_all - w_key), hipMemcpyDeviceToHost, stream));
+  HIPC(hipMemcpyAsync(w_key.in(cs_host.data()), A.o_key, (size_t)pgo::run_bytes(w_key, w_kind), hipMemcpyDeviceToHost, stream));
   PGOC(sync());
   cs_stride = stride;
-  const char* hb = reinterpret_cast<const char*>(cs_host.data()) - w_key;
   pgo::Graph& g = G->g;
   g.pose_id.resize((size_t)K);
   for (int64_t k = 0; k < K; ++k) g.pose_id[k] = (int32_t)k;
-  const double* hk = reinterpret_cast<const double*>(hb + w_key);
-  const double* hm = reinterpret_cast<const double*>(hb + w_meas);
-  const int32_t *ha = reinterpret_cast<const int32_t*>(hb + w_ia), *hbb = reinterpret_cast<const int32_t*>(hb + w_ib),
-                *ho = reinterpret_cast<const int32_t*>(hb + w_org);
-  const uint8_t* hkd = reinterpret_cast<const uint8_t*>(hb + w_kind);
+  const double *hk = w_key.in(cs_host.data()), *hm = w_meas.in(cs_host.data());
+  const int32_t *ha = w_ia.in(cs_host.data()), *hbb = w_ib.in(cs_host.data()), *ho = w_org.in(cs_host.data());
+  const uint8_t* hkd = w_kind.in(cs_host.data());
   g.pose.assign(hk, hk + 3 * K);
   g.ea.assign(ha, ha + Ec);
   g.eb.assign(hbb, hbb + Ec);
@@ -179,8 +171,7 @@ int pgo_handle::coarsen(int32_t stride, pgo_graph** coarse_out, int32_t* origin,
 
 int pgo_handle::prolong(int32_t stride, const double* X) {
   const char* who = "pgo_prolong";
-  if (comm || force_collectives) return fail(PGO_ERR_UNSUPPORTED, std::string(who) + ": one rank without a communicator only");
-  if (batch_mode) return fail(PGO_ERR_UNSUPPORTED, std::string(who) + ": not on a batched handle");
+  PGOC(requires(who, ONE_RANK | NOT_BATCH));
   if (!X) return fail(PGO_ERR_INVALID_ARG, std::string(who) + ": null pointer");
   const int64_t N = S.n_poses;
   PGOC(check_sizes(who, N, stride));
@@ -190,26 +181,27 @@ int pgo_handle::prolong(int32_t stride, const double* X) {
   for (int64_t k = 0; k < K; ++k)
     if (!pgo::coarsen_finite3(X[3 * k], X[3 * k + 1], X[3 * k + 2]))
       return fail(PGO_ERR_NUMERIC, std::string(who) + ": coarse pose " + std::to_string(k) + " is not finite");
-  const long long grid_knob = knob("coarsen_grid");
   HIPC(hipSetDevice(device));
-  PGOC(win_reserve(&cs_work, &cs_work_cap, 3 * K * 8));
-  HIPC(hipMemcpyAsync(cs_work, X, (size_t)(3 * K * 8), hipMemcpyHostToDevice, stream));
+  const Composites comp(N, K);
+  pgo::Layout LW;   // work = the coarse poses
+  const auto w_x = LW.add<double>(3 * K);
+  PGOC(reserve(cs_work, LW.bytes()));
   dev::ProlongArgs A;
-  A.X = static_cast<const double*>(cs_work);
-  A.C = static_cast<const double*>(cs_comp);
-  A.Cend = reinterpret_cast<const double*>(static_cast<char*>(cs_comp) + 3 * N * 8);
-  A.perm = perm.empty() ? nullptr : score_perm;
+  PGOC(perm_device(&A.perm));   // (pgo_coarsen made it)
+  HIPC(hipMemcpyAsync(w_x.in(cs_work.p), X, (size_t)w_x.bytes(), hipMemcpyHostToDevice, stream));
+  A.X = w_x.in(cs_work.p);
+  A.C = comp.C.in(cs_comp.p);
+  A.Cend = comp.Cend.in(cs_comp.p);
   A.constant = fixed_mask;
   A.poses = poses;
   A.n = (int32_t)N;
   A.stride = stride;
   A.n_key = (int32_t)K;
   A.fixed_internal = fixed_internal;
-  const int grid = (int)(grid_knob > 0 ? std::min<long long>(grid_knob, 65535) : std::min<int64_t>((N + dev::WG - 1) / dev::WG, 65535));
+  const int grid = launch_grid("coarsen_grid", (N + dev::WG - 1) / dev::WG);
   hipLaunchKernelGGL(dev::k_prolong<>, dim3(grid), dim3(dev::WG), 0, stream, A);
   PGOC(check_launch("k_prolong"));
-  lin_valid = false;   // as pgo_set_poses: the running solve (if any) is stale
-  lm_active = false;
+  solve_is_stale();   // as pgo_set_poses
   return sync();   // (the caller's X may die after the call)
 }
 

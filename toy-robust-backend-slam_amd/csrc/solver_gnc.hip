@@ -4,18 +4,6 @@
 #include "solver_handle.hip.h"
 #include "gnc.hip.h"
 
-namespace {
-int64_t up16(int64_t b) { return (b + 15) / 16 * 16; }
-}  // namespace
-
-int pgo_handle::weights_supported(const char* who) const {
-  if (opt.method == 2) return fail(PGO_ERR_UNSUPPORTED, std::string(who) + ": METHOD 0 and 1 only");
-  if (opt.info_weighting || info_mode) return fail(PGO_ERR_UNSUPPORTED, std::string(who) + ": info_weighting is not supported");
-  if (comm || force_collectives) return fail(PGO_ERR_UNSUPPORTED, std::string(who) + ": one rank without a communicator only");
-  if (batch_mode) return fail(PGO_ERR_UNSUPPORTED, std::string(who) + ": not on a batched handle");
-  return PGO_OK;
-}
-
 int pgo_handle::weights_alloc() {
   const int64_t EL = S.n_edges_local;   // (one rank: every edge is local)
   if (!e_w) PGOC(dalloc(&e_w, EL));
@@ -26,7 +14,7 @@ int pgo_handle::weights_alloc() {
 // (if any) is stale.  NULL: no plane -- K1 is back on the instantiations the handle's losses and mask ask for.
 int pgo_handle::set_edge_weights(const double* w) {
   const char* who = "pgo_set_edge_weights";
-  PGOC(weights_supported(who));
+  PGOC(requires(who, PLAIN_HANDLE));
   const int64_t EL = S.n_edges_local;
   if (w)
     for (int64_t e = 0; e < n_edges_total; ++e)
@@ -41,14 +29,13 @@ int pgo_handle::set_edge_weights(const double* w) {
     PGOC(sync());   // (`loc` dies with this scope)
   }
   w_set = w != nullptr && EL > 0;
-  lin_valid = false;
-  lm_active = false;
+  solve_is_stale();
   return PGO_OK;
 }
 
 int pgo_handle::get_edge_weights(double* out) {
   const char* who = "pgo_get_edge_weights";
-  PGOC(weights_supported(who));
+  PGOC(requires(who, PLAIN_HANDLE));
   if (!out) return fail(PGO_ERR_INVALID_ARG, std::string(who) + ": null pointer");
   const int64_t EL = S.n_edges_local;
   if (!w_set) {
@@ -66,7 +53,7 @@ int pgo_handle::get_edge_weights(double* out) {
 // reset_selected (pgo_gnc_solve's step 1): every selected weight <- 1, measured there
 int pgo_handle::gnc_update(double cbar, double mu, const uint8_t* select, bool reset_selected, pgo_gnc_stats* out) {
   const char* who = "pgo_gnc_update";
-  PGOC(weights_supported(who));
+  PGOC(requires(who, PLAIN_HANDLE));
   if (!(std::isfinite(cbar) && cbar > 0.0)) return fail(PGO_ERR_INVALID_ARG, std::string(who) + ": cbar must be finite and > 0");
   if (std::isnan(mu) || std::isinf(mu)) return fail(PGO_ERR_INVALID_ARG, std::string(who) + ": mu is not finite");
   const int mode = reset_selected ? 2 : (mu > 0.0 ? 1 : 0);
@@ -78,38 +65,35 @@ int pgo_handle::gnc_update(double cbar, double mu, const uint8_t* select, bool r
     if (out) *out = st;
     return PGO_OK;
   }
-  const long long grid_knob = knob("gnc_grid");
   HIPC(hipSetDevice(device));
   // ---- buffers, before anything changes: gnc_buf = stats | partials | caller's edge -> local edge | select bytes
   const int64_t nc = (E + dev::WG - 1) / dev::WG;
-  const int64_t b_out = 0, b_part = up16((int64_t)sizeof(pgo_gnc_stats)), b_loc = b_part + dev::GNC_NPART * nc * 8,
-                b_sel = up16(b_loc + E * 4), b_all = b_sel + up16(E);
-  const bool table_stale = b_all > gnc_buf_cap;   // (a handle's E never changes: the table is written when the buffer is made)
-  PGOC(win_reserve(&gnc_buf, &gnc_buf_cap, b_all));
-  const bool fresh_plane = mode != 0 && !w_set;
-  if (mode != 0) PGOC(weights_alloc());
+  pgo::Layout L;
+  const auto b_out = L.add<pgo_gnc_stats>(1);
+  const auto b_part = L.add<double>(dev::GNC_NPART * nc);
+  const auto b_loc = L.add<int32_t>(E);   // (the upload: b_loc to b_sel, or b_sel alone)
+  const auto b_sel = L.add<uint8_t>(E);
+  bool table_stale = false, fresh_plane = false;   // (a handle's E never changes: the table is written when the buffer is made)
+  PGOC(reserve(gnc_buf, L.bytes(), &table_stale));
+  if (mode != 0) PGOC(weights_begin(&fresh_plane));
   // ---- upload: the resolved selection (selected AND active), the edge table once, an all-ones plane at its first use
-  std::vector<uint8_t> host((size_t)(b_all - b_loc), 0);
-  int32_t* loc_h = reinterpret_cast<int32_t*>(host.data());
-  uint8_t* sel_h = host.data() + (b_sel - b_loc);
+  std::vector<uint8_t> host((size_t)L.bytes(), 0);
+  int32_t* loc_h = b_loc.in(host.data());
+  uint8_t* sel_h = b_sel.in(host.data());
   for (int64_t k = 0; k < EL; ++k) {
     const int64_t e = S.orig_edge[k];
     loc_h[e] = (int32_t)k;
     const bool active = !(S.flags[k] & dev::EDGE_INACTIVE);
     sel_h[e] = (active && (select ? select[e] != 0 : kind_local[k] != PGO_EDGE_ODOMETRY)) ? 1 : 0;
   }
-  char* buf = static_cast<char*>(gnc_buf);
-  if (table_stale) HIPC(hipMemcpyAsync(buf + b_loc, host.data(), host.size(), hipMemcpyHostToDevice, stream));
-  else HIPC(hipMemcpyAsync(buf + b_sel, sel_h, (size_t)E, hipMemcpyHostToDevice, stream));
+  if (table_stale) HIPC(hipMemcpyAsync(b_loc.in(gnc_buf.p), loc_h, (size_t)pgo::run_bytes(b_loc, b_sel), hipMemcpyHostToDevice, stream));
+  else HIPC(hipMemcpyAsync(b_sel.in(gnc_buf.p), sel_h, (size_t)b_sel.bytes(), hipMemcpyHostToDevice, stream));
   std::vector<double> ones;
-  if (fresh_plane) {
-    ones.assign((size_t)EL, 1.0);
-    PGOC(upload(e_w, ones));
-  }
+  if (fresh_plane) PGOC(weights_ones(&ones));
   dev::GncArgs A;
   A.E = edge_args(poses, nullptr, 0);
-  A.loc = reinterpret_cast<const int32_t*>(buf + b_loc);
-  A.select = reinterpret_cast<const uint8_t*>(buf + b_sel);
+  A.loc = b_loc.in(gnc_buf.p);
+  A.select = b_sel.in(gnc_buf.p);
   A.w = (mode != 0 || w_set) ? e_w : nullptr;
   A.n = (int32_t)E;
   A.n_chunks = (int32_t)nc;
@@ -117,19 +101,18 @@ int pgo_handle::gnc_update(double cbar, double mu, const uint8_t* select, bool r
   A._pad = 0;
   A.c2 = cbar * cbar;
   A.mu = mu;
-  A.part = reinterpret_cast<double*>(buf + b_part);
-  A.out = reinterpret_cast<pgo_gnc_stats*>(buf + b_out);
-  const int grid = (int)(grid_knob > 0 ? std::min<long long>(grid_knob, 65535) : std::min<int64_t>(nc, 65535));
+  A.part = b_part.in(gnc_buf.p);
+  A.out = b_out.in(gnc_buf.p);
+  const int grid = launch_grid("gnc_grid", nc);
   hipLaunchKernelGGL(dev::k_gnc_update<>, dim3(grid), dim3(dev::WG), 0, stream, A);
   PGOC(check_launch("k_gnc_update"));
   hipLaunchKernelGGL(dev::k_gnc_fold<>, dim3(1), dim3(dev::WG), 0, stream, A);
   PGOC(check_launch("k_gnc_fold"));
-  HIPC(hipMemcpyAsync(&st, buf + b_out, sizeof st, hipMemcpyDeviceToHost, stream));
+  HIPC(hipMemcpyAsync(&st, A.out, sizeof st, hipMemcpyDeviceToHost, stream));
   PGOC(sync());   // (`host` and `ones` die with this scope)
   if (mode != 0) {
     w_set = true;
-    lin_valid = false;
-    lm_active = false;
+    solve_is_stale();
   }
   if (out) *out = st;
   return PGO_OK;
@@ -148,7 +131,7 @@ int check_gnc_options(const char* who, const pgo_gnc_options* o) {
 
 int pgo_handle::gnc_solve(const pgo_gnc_options* o, pgo_gnc_summary* summary, pgo_gnc_round* rounds, int32_t rounds_cap) {
   const char* who = "pgo_gnc_solve";
-  PGOC(weights_supported(who));
+  PGOC(requires(who, PLAIN_HANDLE));
   if (opt.method != 0) return fail(PGO_ERR_INVALID_ARG, std::string(who) + ": METHOD 0 only (the weights take the place of DCS)");
   PGOC(check_gnc_options(who, o));
   HIPC(hipSetDevice(device));
@@ -195,8 +178,7 @@ int pgo_handle::gnc_solve(const pgo_gnc_options* o, pgo_gnc_summary* summary, pg
     if (s1 != PGO_OK || termination == PGO_TERM_FAILURE) {
       (void)hipMemcpyAsync(poses, gnc_x, x_bytes, hipMemcpyDeviceToDevice, stream);
       (void)hipStreamSynchronize(stream);
-      lin_valid = false;
-      lm_active = false;
+      solve_is_stale();
       G.mu_last = mu;
       return finish(s1 != PGO_OK ? s1 : fail(PGO_ERR_NUMERIC, std::string(who) + ": the inner solve of round " + std::to_string(k + 1) + " failed"));
     }

@@ -13,6 +13,8 @@
 //   solver_gnc.hip      pgo_set_edge_weights, pgo_gnc_update, pgo_gnc_solve: the edge weight plane and GNC-TLS (gnc.hip.h, gnc.h)
 //   solver_support.hip  pgo_loop_support: loop edges judged by odometry cycle consistency (loop_support.hip.h, loop_support.h)
 // Every kernel header declares its kernels `static`: a translation unit carries the kernels it launches.
+// The add-on calls (the last five units) share the helpers below: requires() for their refusals, reserve() and the Layouts of
+// scratch.h for their staging and work buffers.
 //
 // Replaces, for DCS-ceres/main.cpp METHOD 0/1 (paths relative to /root/reference/DCS-ceres):
 //   main.cpp:66-68,95-153   problem assembly  -> pgo_create (shard structure + device upload)
@@ -46,6 +48,7 @@
 #include "direct.hip.h"
 #include "coarse.hip.h"
 #include "pgo_internal.h"
+#include "scratch.h"
 
 using pgo::fail;
 namespace dev = pgo::dev;
@@ -68,6 +71,14 @@ namespace dev = pgo::dev;
 // (table and setter: solver_abi.hip)
 long long knob(const char* name);
 int require_device(int device);   // a gfx950 device of that index is visible (solver_abi.hip)
+
+// the refusals pgo_coarsen_plan / pgo_loop_support_plan share with the calls on a handle
+static inline int no_chain(const std::string& who, int32_t gap) {
+  return fail(PGO_ERR_UNSUPPORTED, who + ": poses " + std::to_string(gap) + " and " + std::to_string(gap + 1) + " are not joined by an edge");
+}
+static inline int not_finite(const std::string& who, int64_t e) {
+  return fail(PGO_ERR_NUMERIC, who + ": the measurement of edge " + std::to_string(e) + " is not finite");
+}
 
 static inline double wall_s() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -319,6 +330,45 @@ struct pgo_handle {
     if (e != hipSuccess) return fail(PGO_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
     return PGO_OK;
   }
+  // a scratch buffer of at least `bytes`: grown on demand (to at least twice its size) and kept; *moved: it was (re)allocated
+  // and holds nothing.  (The stream is idle: every call that uses such a buffer ends with a synchronisation.)
+  int reserve(pgo::Scratch& s, int64_t bytes, bool* moved = nullptr) {
+    if (moved) *moved = bytes > s.cap;
+    if (bytes <= s.cap) return PGO_OK;
+    const int64_t want = std::max<int64_t>(bytes, 2 * s.cap);
+    void* q = nullptr;
+    hipError_t e = hipMalloc(&q, (size_t)want);
+    if (e != hipSuccess) return fail(PGO_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+    if (s.p) {
+      allocs.erase(std::remove(allocs.begin(), allocs.end(), s.p), allocs.end());
+      (void)hipFree(s.p);
+      device_bytes -= s.cap;
+    }
+    allocs.push_back(q);
+    device_bytes += want;
+    s.p = q;
+    s.cap = want;
+    return PGO_OK;
+  }
+  // what a call needs of its handle; the first unmet need, in this order, is its PGO_ERR_UNSUPPORTED
+  enum : unsigned { METHOD_01 = 1, NO_INFO = 2, ONE_RANK = 4, NOT_BATCH = 8, PLAIN_HANDLE = METHOD_01 | NO_INFO | ONE_RANK | NOT_BATCH };
+  int requires(const char* who, unsigned needs) const {
+    const char* what = nullptr;
+    if ((needs & METHOD_01) && opt.method != 0 && opt.method != 1) what = ": METHOD 0 and 1 only";
+    else if ((needs & NO_INFO) && (opt.info_weighting || info_mode)) what = ": info_weighting is not supported";
+    else if ((needs & ONE_RANK) && (comm || force_collectives)) what = ": one rank without a communicator only";
+    else if ((needs & NOT_BATCH) && batch_mode) what = ": not on a batched handle";
+    return what ? fail(PGO_ERR_UNSUPPORTED, std::string(who) + what) : PGO_OK;
+  }
+  void solve_is_stale() {   // as after pgo_set_poses: pgo_lm_step refuses until pgo_lm_begin
+    lin_valid = false;
+    lm_active = false;
+  }
+  // workgroups for `units` of work, or what the test hook `knob_name` asks for
+  int launch_grid(const char* knob_name, int64_t units) const {
+    const long long k = knob(knob_name);
+    return (int)std::min<int64_t>(k > 0 ? k : std::max<int64_t>(units, 1), 65535);
+  }
 
   // ---- reductions to scalars: scal[first..first+k) = reduce(parts) [+ all-reduce], no host sync
   int reduce_to_scal(std::initializer_list<PartRef> parts, int first, bool allreduce_max = false);
@@ -389,14 +439,22 @@ struct pgo_handle {
   // edge weights (pgo_set_edge_weights) and graduated non-convexity (pgo_gnc_update, pgo_gnc_solve; solver_gnc.hip, gnc.hip.h,
   // gnc.h): one double in [0, 1] per local edge.  The plane is allocated at its first use and kept; while one is in force K1 runs
   // its LOSSES instantiations, which read it.  gnc_buf holds a call's select bytes, the per-workgroup partials and the folded
-  // statistics (made at the first call and kept, win_reserve), and the caller's edge -> local edge table of k_gnc_update.
+  // statistics (made at the first call and kept, reserve), and the caller's edge -> local edge table of k_gnc_update.
   double* e_w = nullptr;
   bool w_set = false;
-  void* gnc_buf = nullptr;
-  int64_t gnc_buf_cap = 0;
+  pgo::Scratch gnc_buf;
   double* gnc_x = nullptr;   // pgo_gnc_solve: the poses a round started from (allocated at the first call, kept)
-  int weights_supported(const char* who) const;   // the refusals the weight plane and GNC share
   int weights_alloc();                            // the plane, before anything changes
+  // a call that writes the plane: weights_begin before anything changes (*fresh: no plane is in force), then, where the call
+  // enqueues its uploads, weights_ones on a fresh plane (`ones` is the host source: it lives until the call's synchronisation)
+  int weights_begin(bool* fresh) {
+    *fresh = !w_set;
+    return weights_alloc();
+  }
+  int weights_ones(std::vector<double>* ones) {
+    ones->assign((size_t)S.n_edges_local, 1.0);
+    return upload(e_w, *ones);
+  }
   int set_edge_weights(const double* w_or_null);
   int get_edge_weights(double* w_out);
   int gnc_update(double cbar, double mu, const uint8_t* select_or_null, bool reset_selected, pgo_gnc_stats* out);
@@ -517,12 +575,10 @@ struct pgo_handle {
   // into win_in; win_work holds the per-edge records and the outputs.  Both buffers are grown on demand and kept.
   std::vector<int32_t> win_edge_local;      // caller's edge -> local edge (built at the first call)
   std::vector<int32_t> win_pos, win_owner;  // row -> list position in the window being resolved / window that lists it (-1 when idle)
-  std::vector<int32_t> win_host;
+  std::vector<uint8_t> win_host;            // host image of win_in
   std::vector<uint32_t> win_sort;
-  void *win_in = nullptr, *win_work = nullptr;
-  int64_t win_in_cap = 0, win_work_cap = 0;
+  pgo::Scratch win_in, win_work;
   bool win_lds_set = false;
-  int win_reserve(void** buf, int64_t* cap, int64_t bytes);
   // pose_idx / edge_idx / anchor: this handle's caller numbering (a batch: the union's); `who` prefixes the error texts
   int window_solve(const char* who, int32_t n_windows, const int32_t* pose_ptr, const int32_t* pose_idx, const int32_t* edge_ptr,
                    const int32_t* edge_idx, const int32_t* anchor, int32_t max_iters, int32_t commit, double* poses_out,
@@ -530,10 +586,17 @@ struct pgo_handle {
 
   // scoring (pgo_trajectory_error, pgo_edge_weights; solver_score.hip): score_in stages what a call uploads (the reference and
   // the mask, or the caller's poses), score_work holds the partials and the outputs; both are grown on demand and kept
-  // (win_reserve).  score_perm / score_eorig: device copies of perm and of S.orig_edge, made at the first call that needs them.
-  void *score_in = nullptr, *score_work = nullptr;
-  int64_t score_in_cap = 0, score_work_cap = 0;
+  // (reserve).  score_perm / score_eorig: device copies of perm and of S.orig_edge, made at the first call that needs them.
+  pgo::Scratch score_in, score_work;
   int32_t *score_perm = nullptr, *score_eorig = nullptr;
+  int perm_device(const int32_t** out = nullptr) {   // *out = the device copy of perm, made at its first use; nullptr: the identity
+    if (!perm.empty() && !score_perm) {
+      PGOC(dalloc(&score_perm, (int64_t)S.n_poses));
+      PGOC(upload(score_perm, perm));
+    }
+    if (out) *out = perm.empty() ? nullptr : score_perm;
+    return PGO_OK;
+  }
   std::vector<uint8_t> score_host;   // host image of score_in
   int trajectory_error(const double* ref, const uint8_t* mask, const pgo_traj_options* opt, pgo_traj_error* out, double* per_pose);
   int edge_weights(const double* poses_or_null, pgo_edge_weight* out);
@@ -541,12 +604,16 @@ struct pgo_handle {
   // hierarchical initialisation (pgo_coarsen, pgo_prolong; solver_coarsen.hip).  The tables in the caller's numbering are built
   // at the first call and kept: cs_tab = chain [N] | endpoints a [E] | b [E] | local edge [E] (-1: a chain edge) | kind bytes [E].
   // cs_comp holds C (N x 3) and Cend of stride cs_stride (0: none yet), cs_work the scan scratch and the outputs of a call (or the
-  // coarse poses pgo_prolong uploads); both are grown on demand and kept (win_reserve).  The device copy of perm is score_perm.
+  // coarse poses pgo_prolong uploads); both are grown on demand and kept (reserve).  The device copy of perm is perm_device's.
   bool cs_ready = false;
   std::vector<int32_t> cs_ea_h, cs_eb_h, cs_loc_h;
   int32_t* cs_tab = nullptr;
-  void *cs_comp = nullptr, *cs_work = nullptr;
-  int64_t cs_comp_cap = 0, cs_work_cap = 0;
+  const int32_t* cs_chain() const { return cs_tab; }
+  const int32_t* cs_ea() const { return cs_chain() + S.n_poses; }
+  const int32_t* cs_eb() const { return cs_ea() + n_edges_total; }
+  const int32_t* cs_eloc() const { return cs_eb() + n_edges_total; }
+  const uint8_t* cs_ekind() const { return reinterpret_cast<const uint8_t*>(cs_eloc() + n_edges_total); }
+  pgo::Scratch cs_comp, cs_work;
   int32_t cs_stride = 0;
   std::vector<uint8_t> cs_host;   // host image of a call's outputs
   int64_t cs_bad = -1;            // the smallest edge whose measurement is not finite (-1: none), found when the tables were built
@@ -558,13 +625,12 @@ struct pgo_handle {
   // T (N x 5) | the segment ends | the key poses, computed at the first call and kept (measurements never change on a handle).
   // ls_tab = the table of a selection -- the loops sorted by (lo, edge) | first [N + 1] | slot of every edge | M^-1 per slot --,
   // built on the host at the first call for that selection (ls_sel_h: its bytes) and kept; ls_work = a call's per-slot results,
-  // records, chunk totals and statistics.  Both are grown on demand and kept (win_reserve).
+  // records, chunk totals and statistics.  Both are grown on demand and kept (reserve).
   bool ls_traj_ready = false, ls_tab_ready = false;
   double* ls_traj = nullptr;
   std::vector<uint8_t> ls_sel_h;
   int32_t ls_n_sel = 0;
-  void *ls_tab = nullptr, *ls_work = nullptr;
-  int64_t ls_tab_cap = 0, ls_work_cap = 0;
+  pgo::Scratch ls_tab, ls_work;
   std::vector<uint8_t> ls_host;   // host image of a call's outputs
   int loop_support(const pgo_loop_support_options* o, const uint8_t* select_or_null, pgo_loop_support_record* out, pgo_loop_support_stats* stats);
 

@@ -14,56 +14,56 @@ int check_traj_options(const char* who, const pgo_traj_options* opt, pgo_traj_op
   if (o->rpe_delta < 0) return fail(PGO_ERR_INVALID_ARG, std::string(who) + ": rpe_delta < 0");
   return PGO_OK;
 }
-int64_t up16(int64_t b) { return (b + 15) / 16 * 16; }
+struct TrajOut {   // what k_traj_fold<2> leaves: the record, and behind it the first pose that is not finite (-1: none)
+  pgo_traj_error e;
+  int32_t bad, _pad;
+};
+static_assert(sizeof(TrajOut) == sizeof(pgo_traj_error) + 8, "the index sits right behind the record");
 }  // namespace
 
 int pgo_handle::trajectory_error(const double* ref, const uint8_t* mask, const pgo_traj_options* opt, pgo_traj_error* out,
                                  double* per_pose) {
   const char* who = "pgo_trajectory_error";
-  if (comm || force_collectives) return fail(PGO_ERR_UNSUPPORTED, std::string(who) + ": one rank without a communicator only");
-  if (batch_mode) return fail(PGO_ERR_UNSUPPORTED, std::string(who) + ": not on a batched handle");
+  PGOC(requires(who, ONE_RANK | NOT_BATCH));
   if (!ref || !out) return fail(PGO_ERR_INVALID_ARG, std::string(who) + ": null pointer");
   pgo_traj_options o;
   PGOC(check_traj_options(who, opt, &o));
-  const long long grid_knob = knob("score_grid");
   HIPC(hipSetDevice(device));
   const int64_t N = S.n_poses;
   const int64_t nc = (N + dev::SCORE_CHUNK - 1) / dev::SCORE_CHUNK;
   // ---- buffers, before anything is enqueued: staging = state | ref | mask;  work = out (+ the index) | psum | pmax | pidx | per-pose
-  const int64_t i_state = 0, i_ref = i_state + dev::SCORE_STATE * 8, i_mask = i_ref + 3 * N * 8, i_all = i_mask + (mask ? up16(N) : 0);
-  const int64_t w_out = 0, w_psum = w_out + up16((int64_t)sizeof(pgo_traj_error) + 8),
-                w_pmax = w_psum + dev::SCORE_NSUM * nc * 8, w_pidx = w_pmax + dev::SCORE_NMAX * nc * 8,
-                w_pp = up16(w_pidx + dev::SCORE_NIDX * nc * 4), w_all = w_pp + (per_pose ? 2 * N * 8 : 0);
-  PGOC(win_reserve(&score_in, &score_in_cap, i_all));
-  PGOC(win_reserve(&score_work, &score_work_cap, w_all));
-  if (!perm.empty() && !score_perm) {
-    PGOC(dalloc(&score_perm, N));
-    PGOC(upload(score_perm, perm));
-  }
-  // ---- upload
-  score_host.assign((size_t)i_all, 0);
-  reinterpret_cast<double*>(score_host.data() + i_state)[6] = 1.0;   // the identity transform (phi, c, s, tx, ty at 5..9): what the
-                                                                      // error pass reads when no alignment runs
-  memcpy(score_host.data() + i_ref, ref, (size_t)(3 * N * 8));
-  if (mask) memcpy(score_host.data() + i_mask, mask, (size_t)N);
-  HIPC(hipMemcpyAsync(score_in, score_host.data(), (size_t)i_all, hipMemcpyHostToDevice, stream));
-  char* wk = static_cast<char*>(score_work);
+  pgo::Layout LI, LW;
+  const auto i_state = LI.add<double>(dev::SCORE_STATE), i_ref = LI.add<double>(3 * N);
+  const auto i_mask = LI.add<uint8_t>(mask ? N : 0);
+  const auto w_out = LW.add<TrajOut>(1);
+  const auto w_psum = LW.add<double>(dev::SCORE_NSUM * nc), w_pmax = LW.add<double>(dev::SCORE_NMAX * nc);
+  const auto w_pidx = LW.add<int32_t>(dev::SCORE_NIDX * nc);
+  const auto w_pp = LW.add<double>(per_pose ? 2 * N : 0);
+  PGOC(reserve(score_in, LI.bytes()));
+  PGOC(reserve(score_work, LW.bytes()));
   dev::TrajArgs A;
+  PGOC(perm_device(&A.perm));
+  // ---- upload
+  score_host.assign((size_t)LI.bytes(), 0);
+  i_state.in(score_host.data())[6] = 1.0;   // the identity transform (phi, c, s, tx, ty at 5..9): what the error pass reads when
+                                            // no alignment runs
+  memcpy(i_ref.in(score_host.data()), ref, (size_t)i_ref.bytes());
+  if (mask) memcpy(i_mask.in(score_host.data()), mask, (size_t)N);
+  HIPC(hipMemcpyAsync(score_in.p, score_host.data(), score_host.size(), hipMemcpyHostToDevice, stream));
   A.est = poses;
-  A.perm = perm.empty() ? nullptr : score_perm;
-  A.ref = reinterpret_cast<const double*>(static_cast<char*>(score_in) + i_ref);
-  A.mask = mask ? reinterpret_cast<const uint8_t*>(static_cast<char*>(score_in) + i_mask) : nullptr;
+  A.ref = i_ref.in(score_in.p);
+  A.mask = mask ? i_mask.in(score_in.p) : nullptr;
   A.n = (int32_t)N;
   A.n_chunks = (int32_t)nc;
   A.delta = o.rpe_delta;
   A._pad = 0;
-  A.psum = reinterpret_cast<double*>(wk + w_psum);
-  A.pmax = reinterpret_cast<double*>(wk + w_pmax);
-  A.pidx = reinterpret_cast<int32_t*>(wk + w_pidx);
-  A.state = reinterpret_cast<double*>(static_cast<char*>(score_in) + i_state);
-  A.per_pose = per_pose ? reinterpret_cast<double*>(wk + w_pp) : nullptr;
-  A.out = reinterpret_cast<pgo_traj_error*>(wk + w_out);
-  const int grid = (int)(grid_knob > 0 ? std::min<long long>(grid_knob, 65535) : std::min<int64_t>(nc, 65535));
+  A.psum = w_psum.in(score_work.p);
+  A.pmax = w_pmax.in(score_work.p);
+  A.pidx = w_pidx.in(score_work.p);
+  A.state = i_state.in(score_in.p);
+  A.per_pose = per_pose ? w_pp.in(score_work.p) : nullptr;
+  A.out = &w_out.in(score_work.p)->e;
+  const int grid = launch_grid("score_grid", nc);
   if (o.align) {
     hipLaunchKernelGGL(dev::k_traj_centroid<>, dim3(grid), dim3(dev::WG), 0, stream, A);
     PGOC(check_launch("k_traj_centroid"));
@@ -79,16 +79,12 @@ int pgo_handle::trajectory_error(const double* ref, const uint8_t* mask, const p
   hipLaunchKernelGGL(dev::k_traj_fold<2>, dim3(1), dim3(dev::WG), 0, stream, A);
   PGOC(check_launch("k_traj_fold<2>"));
   // ---- one copy-out: the record with the index behind it, and the per-pose array
-  struct {
-    pgo_traj_error e;
-    int32_t bad, _pad;
-  } res;
-  static_assert(sizeof res == sizeof(pgo_traj_error) + 8, "the index sits right behind the record");
+  TrajOut res;
   std::vector<double> pp;
-  HIPC(hipMemcpyAsync(&res, wk + w_out, sizeof res, hipMemcpyDeviceToHost, stream));
+  HIPC(hipMemcpyAsync(&res, w_out.in(score_work.p), sizeof res, hipMemcpyDeviceToHost, stream));
   if (per_pose) {
     pp.resize((size_t)(2 * N));
-    HIPC(hipMemcpyAsync(pp.data(), wk + w_pp, (size_t)(2 * N * 8), hipMemcpyDeviceToHost, stream));
+    HIPC(hipMemcpyAsync(pp.data(), A.per_pose, (size_t)w_pp.bytes(), hipMemcpyDeviceToHost, stream));
   }
   PGOC(sync());
   if (res.bad >= 0) return fail(PGO_ERR_NUMERIC, std::string(who) + ": pose " + std::to_string(res.bad) + " is not finite");
@@ -99,40 +95,40 @@ int pgo_handle::trajectory_error(const double* ref, const uint8_t* mask, const p
 
 int pgo_handle::edge_weights(const double* poses_or_null, pgo_edge_weight* out) {
   const char* who = "pgo_edge_weights";
-  if (opt.method != 0 && opt.method != 1) return fail(PGO_ERR_UNSUPPORTED, std::string(who) + ": METHOD 0 and 1 only (METHOD 2: pgo_get_switches)");
-  if (opt.info_weighting || info_mode) return fail(PGO_ERR_UNSUPPORTED, std::string(who) + ": info_weighting is not supported");
-  if (comm || force_collectives) return fail(PGO_ERR_UNSUPPORTED, std::string(who) + ": one rank without a communicator only");
-  if (batch_mode) return fail(PGO_ERR_UNSUPPORTED, std::string(who) + ": not on a batched handle");
+  if (const int s = requires(who, METHOD_01)) return fail(s, std::string(pgo_last_error()) + " (METHOD 2: pgo_get_switches)");
+  PGOC(requires(who, NO_INFO | ONE_RANK | NOT_BATCH));
   if (!out) return fail(PGO_ERR_INVALID_ARG, std::string(who) + ": null pointer");
   HIPC(hipSetDevice(device));
   const int64_t N = S.n_poses, EL = S.n_edges_local;   // (one rank: every edge is local)
   if (EL == 0) return PGO_OK;
-  const int64_t w_all = EL * (int64_t)sizeof(pgo_edge_weight);
-  if (poses_or_null) PGOC(win_reserve(&score_in, &score_in_cap, 3 * N * 8));
-  PGOC(win_reserve(&score_work, &score_work_cap, w_all));
+  pgo::Layout LI, LW;   // staging = the caller's poses;  work = the records
+  const auto i_x = LI.add<double>(poses_or_null ? 3 * N : 0);
+  const auto w_rec = LW.add<pgo_edge_weight>(EL);
+  if (poses_or_null) PGOC(reserve(score_in, LI.bytes()));
+  PGOC(reserve(score_work, LW.bytes()));
   if (!score_eorig) {
     PGOC(dalloc(&score_eorig, EL));
     PGOC(upload(score_eorig, S.orig_edge));
   }
   const double* x = poses;
   if (poses_or_null) {   // (the handle's candidate buffer belongs to the LM loop: the caller's poses go through the staging buffer)
-    score_host.resize((size_t)(3 * N * 8));
-    double* hp = reinterpret_cast<double*>(score_host.data());
-    if (perm.empty()) memcpy(hp, poses_or_null, (size_t)(3 * N * 8));
+    score_host.resize((size_t)LI.bytes());
+    double* hp = i_x.in(score_host.data());
+    if (perm.empty()) memcpy(hp, poses_or_null, (size_t)i_x.bytes());
     else
       for (int64_t i = 0; i < N; ++i) memcpy(hp + 3 * (int64_t)perm[i], poses_or_null + 3 * i, 3 * sizeof(double));
-    HIPC(hipMemcpyAsync(score_in, hp, (size_t)(3 * N * 8), hipMemcpyHostToDevice, stream));
-    x = static_cast<const double*>(score_in);
+    HIPC(hipMemcpyAsync(score_in.p, hp, (size_t)i_x.bytes(), hipMemcpyHostToDevice, stream));
+    x = i_x.in(score_in.p);
   }
   dev::EdgeArgs A = edge_args(x, nullptr, 0);
   const int grid = (int)std::min<int64_t>((EL + dev::WG - 1) / dev::WG, 8192);
   hipLaunchKernelGGL(dev::k_edge_weights<>, dim3(grid), dim3(dev::WG), 0, stream, A, (int32_t)(opt.method == 1), (const int32_t*)score_eorig,
-                     static_cast<pgo_edge_weight*>(score_work));
+                     w_rec.in(score_work.p));
   PGOC(check_launch("k_edge_weights"));
   std::vector<pgo_edge_weight> tmp((size_t)EL);   // (nothing reaches the caller's array unless the whole call succeeds)
-  HIPC(hipMemcpyAsync(tmp.data(), score_work, (size_t)w_all, hipMemcpyDeviceToHost, stream));
+  HIPC(hipMemcpyAsync(tmp.data(), w_rec.in(score_work.p), (size_t)w_rec.bytes(), hipMemcpyDeviceToHost, stream));
   PGOC(sync());
-  memcpy(out, tmp.data(), (size_t)w_all);
+  memcpy(out, tmp.data(), (size_t)w_rec.bytes());
   return PGO_OK;
 }
 

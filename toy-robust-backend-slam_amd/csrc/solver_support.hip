@@ -7,8 +7,6 @@
 #include "loop_support.hip.h"
 
 namespace {
-int64_t up16(int64_t b) { return (b + 15) / 16 * 16; }
-
 int check_options(const std::string& who, const pgo_loop_support_options* o) {
   if (!o) return fail(PGO_ERR_INVALID_ARG, who + ": null options");
   if (o->window < 1 || o->window > PGO_LOOP_SUPPORT_MAX_WINDOW)
@@ -18,23 +16,15 @@ int check_options(const std::string& who, const pgo_loop_support_options* o) {
   if (o->min_support < 1) return fail(PGO_ERR_INVALID_ARG, who + ": min_support must be >= 1");
   return PGO_OK;
 }
-int no_chain(const std::string& who, int32_t gap) {
-  return fail(PGO_ERR_UNSUPPORTED, who + ": poses " + std::to_string(gap) + " and " + std::to_string(gap + 1) + " are not joined by an edge");
-}
-int not_finite(const std::string& who, int64_t e) {
-  return fail(PGO_ERR_NUMERIC, who + ": the measurement of edge " + std::to_string(e) + " is not finite");
-}
 }  // namespace
 
 int pgo_handle::loop_support(const pgo_loop_support_options* o, const uint8_t* select, pgo_loop_support_record* out, pgo_loop_support_stats* stats) {
   const char* who = "pgo_loop_support";
-  if (comm || force_collectives) return fail(PGO_ERR_UNSUPPORTED, std::string(who) + ": one rank without a communicator only");
-  if (batch_mode) return fail(PGO_ERR_UNSUPPORTED, std::string(who) + ": not on a batched handle");
+  PGOC(requires(who, ONE_RANK | NOT_BATCH));
   PGOC(check_options(who, o));
-  if (o->apply) PGOC(weights_supported(who));
+  if (o->apply) PGOC(requires(who, PLAIN_HANDLE));
   const int64_t N = S.n_poses, E = n_edges_total;
   if (N < 2) return fail(PGO_ERR_INVALID_ARG, std::string(who) + ": n_poses must be >= 2");
-  const long long grid_knob = knob("support_grid");
   HIPC(hipSetDevice(device));
   PGOC(coarsen_tables(who, false));
   // ---- the resolved selection, and its measurements and the chain's checked
@@ -59,19 +49,23 @@ int pgo_handle::loop_support(const pgo_loop_support_options* o, const uint8_t* s
     pgo::support_sort(N, E, cs_ea_h.data(), cs_eb_h.data(), sel.data(), &s_edge, &s_lo, &s_hi, &first, &slot_of);
     n_sel = (int64_t)s_edge.size();
   }
-  const int64_t t_edge = 0, t_lo = t_edge + n_sel * 4, t_hi = t_lo + n_sel * 4, t_first = t_hi + n_sel * 4, t_slot = t_first + (N + 1) * 4,
-                t_minv = up16(t_slot + E * 4), t_all = t_minv + n_sel * P * 8;
   const int64_t nc = (E + dev::WG - 1) / dev::WG;
-  const int64_t w_stats = 0, w_part = up16((int64_t)sizeof(pgo_loop_support_stats)), w_q = w_part + dev::SUPPORT_NPART * nc * 8, w_out = w_q + n_sel * 8,
-                w_cnt = w_out + E * (int64_t)sizeof(pgo_loop_support_record), w_all = w_cnt + 3 * n_sel * 4;
+  pgo::Layout LT, LW;
+  const auto t_edge = LT.add<int32_t>(n_sel), t_lo = LT.add<int32_t>(n_sel), t_hi = LT.add<int32_t>(n_sel);   // (the host writes
+  const auto t_first = LT.add<int32_t>(N + 1), t_slot = LT.add<int32_t>(E);   // t_edge to t_slot, k_support_prepare the rest)
+  const auto t_minv = LT.add<double>(n_sel * P);
+  const auto w_stats = LW.add<pgo_loop_support_stats>(1);
+  const auto w_part = LW.add<double>(dev::SUPPORT_NPART * nc), w_q = LW.add<double>(n_sel);
+  const auto w_out = LW.add<pgo_loop_support_record>(E);
+  const auto w_cnt = LW.add<int32_t>(3 * n_sel);
   if (!ls_traj) PGOC(dalloc(&ls_traj, (N + 2 * n_seg) * P));
   if (new_table) ls_tab_ready = false;   // (the buffer may move and is rewritten)
-  PGOC(win_reserve(&ls_tab, &ls_tab_cap, t_all));
-  PGOC(win_reserve(&ls_work, &ls_work_cap, w_all));
-  const bool fresh_plane = o->apply && !w_set;
-  if (o->apply) PGOC(weights_alloc());
-  if (out) ls_host.resize((size_t)(E * (int64_t)sizeof(pgo_loop_support_record)));
-  auto grid_for = [&](int64_t units) { return (int)(grid_knob > 0 ? std::min<long long>(grid_knob, 65535) : std::min<int64_t>(std::max<int64_t>(units, 1), 65535)); };
+  PGOC(reserve(ls_tab, LT.bytes()));
+  PGOC(reserve(ls_work, LW.bytes()));
+  bool fresh_plane = false;
+  if (o->apply) PGOC(weights_begin(&fresh_plane));
+  if (out) ls_host.resize((size_t)w_out.bytes());
+  auto grid_for = [&](int64_t units) { return launch_grid("support_grid", units); };
   auto per_lane = [&](int64_t n) { return grid_for((n + dev::WG - 1) / dev::WG); };
   // ---- the trajectory, once per handle
   if (!ls_traj_ready) {
@@ -79,7 +73,7 @@ int pgo_handle::loop_support(const pgo_loop_support_options* o, const uint8_t* s
     A.mx = e_mx;
     A.my = e_my;
     A.mt = e_mt;
-    A.chain = cs_tab;
+    A.chain = cs_chain();
     A.n = (int32_t)N;
     A.n_seg = (int32_t)n_seg;
     A.T = ls_traj;
@@ -92,22 +86,20 @@ int pgo_handle::loop_support(const pgo_loop_support_options* o, const uint8_t* s
     hipLaunchKernelGGL(dev::k_support_traj<>, dim3(per_lane(N)), dim3(dev::WG), 0, stream, A);
     PGOC(check_launch("k_support_traj"));
   }
-  char* tb = static_cast<char*>(ls_tab);
-  char* wk = static_cast<char*>(ls_work);
   dev::SupportArgs A;
   A.mx = e_mx;
   A.my = e_my;
   A.mt = e_mt;
-  A.ea = cs_tab + N;
-  A.eb = cs_tab + N + E;
-  A.eloc = cs_tab + N + 2 * E;
+  A.ea = cs_ea();
+  A.eb = cs_eb();
+  A.eloc = cs_eloc();
   A.T = ls_traj;
-  A.s_edge = reinterpret_cast<const int32_t*>(tb + t_edge);
-  A.s_lo = reinterpret_cast<const int32_t*>(tb + t_lo);
-  A.s_hi = reinterpret_cast<const int32_t*>(tb + t_hi);
-  A.first = reinterpret_cast<const int32_t*>(tb + t_first);
-  A.slot_of = reinterpret_cast<const int32_t*>(tb + t_slot);
-  A.minv = reinterpret_cast<double*>(tb + t_minv);
+  A.s_edge = t_edge.in(ls_tab.p);
+  A.s_lo = t_lo.in(ls_tab.p);
+  A.s_hi = t_hi.in(ls_tab.p);
+  A.first = t_first.in(ls_tab.p);
+  A.slot_of = t_slot.in(ls_tab.p);
+  A.minv = t_minv.in(ls_tab.p);
   A.n = (int32_t)N;
   A.n_edges = (int32_t)E;
   A.n_sel = (int32_t)n_sel;
@@ -118,34 +110,31 @@ int pgo_handle::loop_support(const pgo_loop_support_options* o, const uint8_t* s
   A._pad = 0;
   A.txy2 = o->tol_xy * o->tol_xy;
   A.tth2 = o->tol_th * o->tol_th;
-  A.r_cnt = reinterpret_cast<int32_t*>(wk + w_cnt);
-  A.r_q = reinterpret_cast<double*>(wk + w_q);
-  A.out = reinterpret_cast<pgo_loop_support_record*>(wk + w_out);
+  A.r_cnt = w_cnt.in(ls_work.p);
+  A.r_q = w_q.in(ls_work.p);
+  A.out = w_out.in(ls_work.p);
   A.w = o->apply ? e_w : nullptr;
-  A.part = reinterpret_cast<double*>(wk + w_part);
-  A.stats = reinterpret_cast<pgo_loop_support_stats*>(wk + w_stats);
+  A.part = w_part.in(ls_work.p);
+  A.stats = w_stats.in(ls_work.p);
   // ---- the table of the selection, once per selection
-  std::vector<int32_t> img;
+  std::vector<uint8_t> img;
   if (new_table) {
-    img.resize((size_t)((t_slot + E * 4) / 4));
+    img.resize((size_t)pgo::run_bytes(t_edge, t_slot));   // (the run starts the buffer: the spans address its image as they stand)
     if (n_sel) {
-      memcpy(img.data() + t_edge / 4, s_edge.data(), (size_t)n_sel * 4);
-      memcpy(img.data() + t_lo / 4, s_lo.data(), (size_t)n_sel * 4);
-      memcpy(img.data() + t_hi / 4, s_hi.data(), (size_t)n_sel * 4);
+      memcpy(t_edge.in(img.data()), s_edge.data(), (size_t)t_edge.bytes());
+      memcpy(t_lo.in(img.data()), s_lo.data(), (size_t)t_lo.bytes());
+      memcpy(t_hi.in(img.data()), s_hi.data(), (size_t)t_hi.bytes());
     }
-    memcpy(img.data() + t_first / 4, first.data(), (size_t)(N + 1) * 4);
-    if (E) memcpy(img.data() + t_slot / 4, slot_of.data(), (size_t)E * 4);
-    HIPC(hipMemcpyAsync(tb, img.data(), img.size() * 4, hipMemcpyHostToDevice, stream));
+    memcpy(t_first.in(img.data()), first.data(), (size_t)t_first.bytes());
+    if (E) memcpy(t_slot.in(img.data()), slot_of.data(), (size_t)t_slot.bytes());
+    HIPC(hipMemcpyAsync(t_edge.in(ls_tab.p), img.data(), img.size(), hipMemcpyHostToDevice, stream));
     if (n_sel) {
       hipLaunchKernelGGL(dev::k_support_prepare<>, dim3(per_lane(n_sel)), dim3(dev::WG), 0, stream, A);
       PGOC(check_launch("k_support_prepare"));
     }
   }
   std::vector<double> ones;
-  if (fresh_plane) {
-    ones.assign((size_t)S.n_edges_local, 1.0);
-    PGOC(upload(e_w, ones));
-  }
+  if (fresh_plane) PGOC(weights_ones(&ones));
   if (n_sel) {
     hipLaunchKernelGGL(dev::k_loop_support<>, dim3(per_lane(n_sel)), dim3(dev::WG), 0, stream, A);
     PGOC(check_launch("k_loop_support"));
@@ -156,8 +145,8 @@ int pgo_handle::loop_support(const pgo_loop_support_options* o, const uint8_t* s
   PGOC(check_launch("k_support_fold"));
   pgo_loop_support_stats st;
   memset(&st, 0, sizeof st);
-  HIPC(hipMemcpyAsync(&st, wk + w_stats, sizeof st, hipMemcpyDeviceToHost, stream));
-  if (out && E) HIPC(hipMemcpyAsync(ls_host.data(), wk + w_out, ls_host.size(), hipMemcpyDeviceToHost, stream));
+  HIPC(hipMemcpyAsync(&st, A.stats, sizeof st, hipMemcpyDeviceToHost, stream));
+  if (out && E) HIPC(hipMemcpyAsync(ls_host.data(), A.out, ls_host.size(), hipMemcpyDeviceToHost, stream));
   PGOC(sync());   // (`img` and `ones` die with this scope)
   ls_traj_ready = true;
   if (new_table) {
@@ -167,8 +156,7 @@ int pgo_handle::loop_support(const pgo_loop_support_options* o, const uint8_t* s
   }
   if (o->apply) {
     w_set = true;
-    lin_valid = false;
-    lm_active = false;
+    solve_is_stale();
   }
   if (out && E) memcpy(out, ls_host.data(), ls_host.size());
   if (stats) *stats = st;

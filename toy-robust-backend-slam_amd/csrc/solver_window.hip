@@ -5,31 +5,11 @@
 #include "solver_handle.hip.h"
 #include "window.hip.h"
 
-int pgo_handle::win_reserve(void** buf, int64_t* cap, int64_t bytes) {
-  if (bytes <= *cap) return PGO_OK;
-  const int64_t want = std::max<int64_t>(bytes, 2 * *cap);
-  void* q = nullptr;
-  hipError_t e = hipMalloc(&q, (size_t)want);
-  if (e != hipSuccess) return fail(PGO_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-  if (*buf) {   // (the stream is idle: every call that uses the buffer ends with a synchronisation)
-    allocs.erase(std::remove(allocs.begin(), allocs.end(), *buf), allocs.end());
-    (void)hipFree(*buf);
-    device_bytes -= *cap;
-  }
-  allocs.push_back(q);
-  device_bytes += want;
-  *buf = q;
-  *cap = want;
-  return PGO_OK;
-}
-
 int pgo_handle::window_solve(const char* who, int32_t nw, const int32_t* pose_ptr, const int32_t* pose_idx, const int32_t* edge_ptr,
                              const int32_t* edge_idx, const int32_t* anchor, int32_t max_iters, int32_t commit, double* poses_out,
                              pgo_window_result* results, pgo_iter_record* records) {
   const std::string W = std::string(who) + ": ";
-  if (opt.method != 0 && opt.method != 1) return fail(PGO_ERR_UNSUPPORTED, W + "METHOD 0 and 1 only");
-  if (opt.info_weighting || info_mode) return fail(PGO_ERR_UNSUPPORTED, W + "info_weighting is not supported");
-  if (comm || force_collectives) return fail(PGO_ERR_UNSUPPORTED, W + "one rank without a communicator only");
+  PGOC(requires(who, METHOD_01 | NO_INFO | ONE_RANK));   // (a batch is allowed: pgo_batch_window_solve)
   if (w_set)   // (k_window_solve evaluates the edges itself and does not read the plane)
     return fail(PGO_ERR_UNSUPPORTED, W + "not while edge weights are set (pgo_set_edge_weights(h, NULL) first)");
   if (nw < 0) return fail(PGO_ERR_INVALID_ARG, W + "n_windows < 0");
@@ -58,10 +38,14 @@ int pgo_handle::window_solve(const char* who, int32_t nw, const int32_t* pose_pt
     win_owner.assign((size_t)N, -1);
   }
   // ---- host image: desc | pidx | eloc | eab | blk | blk_ptr | ent  (blocks <= poses + edges, contributions <= 3 x edges)
-  const int64_t o_desc = 0, o_pidx = o_desc + 8 * (int64_t)nw, o_eloc = o_pidx + TP, o_eab = o_eloc + TE, o_blk = o_eab + TE,
-                o_bptr = o_blk + TP + TE, o_ent = o_bptr + TP + TE + 1, n_int = o_ent + 3 * TE;
-  win_host.assign((size_t)n_int, 0);
-  int32_t* M = win_host.data();
+  pgo::Layout LI;
+  const auto s_desc = LI.add<dev::WinDesc>(nw);
+  const auto s_pidx = LI.add<int32_t>(TP), s_eloc = LI.add<int32_t>(TE), s_eab = LI.add<int32_t>(TE), s_blk = LI.add<int32_t>(TP + TE),
+             s_bptr = LI.add<int32_t>(TP + TE + 1), s_ent = LI.add<int32_t>(3 * TE);
+  win_host.assign((size_t)LI.bytes(), 0);
+  dev::WinDesc* const h_desc = s_desc.in(win_host.data());
+  int32_t *const h_pidx = s_pidx.in(win_host.data()), *const h_eloc = s_eloc.in(win_host.data()), *const h_eab = s_eab.in(win_host.data()),
+                *const h_blk = s_blk.in(win_host.data()), *const h_bptr = s_bptr.in(win_host.data()), *const h_ent = s_ent.in(win_host.data());
   int64_t n_blk = 0, n_ent = 0;
   int n3cap = 3;
   int status = PGO_OK;
@@ -90,7 +74,7 @@ int pgo_handle::window_solve(const char* who, int32_t nw, const int32_t* pose_pt
       }
       win_pos[row] = k;
       win_owner[row] = w;
-      M[o_pidx + p0 + k] = row;
+      h_pidx[p0 + k] = row;
       listed = k + 1;
     }
     int32_t anchor_pos = -1;
@@ -111,44 +95,44 @@ int pgo_handle::window_solve(const char* who, int32_t nw, const int32_t* pose_pt
         bad(w, "an endpoint of edge " + std::to_string(e) + " is not in the pose list");
         break;
       }
-      M[o_eloc + e0 + k] = l;
-      M[o_eab + e0 + k] = pa | (pb << 8);
+      h_eloc[e0 + k] = l;
+      h_eab[e0 + k] = pa | (pb << 8);
       // contributions, keyed (block, listed edge): sorting keeps every block's contributions in list order
       const uint32_t hi = (uint32_t)std::max(pa, pb), lo = (uint32_t)std::min(pa, pb), side_hi = pa > pb ? 0u : 1u;
       win_sort.push_back((uint32_t)pa << 17 | (uint32_t)pa << 9 | (uint32_t)k << 1 | 0u);
       win_sort.push_back((uint32_t)pb << 17 | (uint32_t)pb << 9 | (uint32_t)k << 1 | 1u);
       win_sort.push_back(1u << 25 | hi << 17 | lo << 9 | (uint32_t)k << 1 | side_hi);
     }
-    for (int32_t k = 0; k < listed; ++k) win_pos[M[o_pidx + p0 + k]] = -1;   // idle again, whatever happened
+    for (int32_t k = 0; k < listed; ++k) win_pos[h_pidx[p0 + k]] = -1;   // idle again, whatever happened
     if (status != PGO_OK) break;
     std::sort(win_sort.begin(), win_sort.end());
-    int32_t* D = M + o_desc + 8 * (int64_t)w;
-    D[0] = p0;
-    D[1] = np;
-    D[2] = e0;
-    D[3] = ne;
-    D[4] = anchor_pos;
-    D[5] = (int32_t)n_blk;
+    dev::WinDesc& D = h_desc[w];
+    D.pose0 = p0;
+    D.np = np;
+    D.edge0 = e0;
+    D.ne = ne;
+    D.anchor = anchor_pos;
+    D.blk0 = (int32_t)n_blk;
     size_t c = 0;
     for (int32_t p = 0; p < np; ++p) {   // the diagonal blocks first, one per listed pose (empty: a pose without an edge)
-      M[o_blk + n_blk] = p | (p << 8);
-      M[o_bptr + n_blk] = (int32_t)n_ent;
+      h_blk[n_blk] = p | (p << 8);
+      h_bptr[n_blk] = (int32_t)n_ent;
       ++n_blk;
-      for (; c < win_sort.size() && (win_sort[c] >> 17) == (uint32_t)p; ++c) M[o_ent + n_ent++] = (int32_t)(win_sort[c] & 511u);
+      for (; c < win_sort.size() && (win_sort[c] >> 17) == (uint32_t)p; ++c) h_ent[n_ent++] = (int32_t)(win_sort[c] & 511u);
     }
     while (c < win_sort.size()) {        // then the blocks (p, q), p > q, that an edge joins
       const uint32_t key = win_sort[c] >> 9;
-      M[o_blk + n_blk] = (int32_t)((key >> 8) & 255u) | (int32_t)((key & 255u) << 8);
-      M[o_bptr + n_blk] = (int32_t)n_ent;
+      h_blk[n_blk] = (int32_t)((key >> 8) & 255u) | (int32_t)((key & 255u) << 8);
+      h_bptr[n_blk] = (int32_t)n_ent;
       ++n_blk;
-      for (; c < win_sort.size() && (win_sort[c] >> 9) == key; ++c) M[o_ent + n_ent++] = (int32_t)(win_sort[c] & 511u);
+      for (; c < win_sort.size() && (win_sort[c] >> 9) == key; ++c) h_ent[n_ent++] = (int32_t)(win_sort[c] & 511u);
     }
-    D[6] = (int32_t)n_blk - D[5];
+    D.nblk = (int32_t)n_blk - D.blk0;
     n3cap = std::max(n3cap, 3 * np);
   }
-  M[o_bptr + n_blk] = (int32_t)n_ent;
+  h_bptr[n_blk] = (int32_t)n_ent;
   for (int64_t k = 0; k < TP; ++k) {   // (rows recorded so far; on an error the tail of the image is still 0)
-    const int32_t row = M[o_pidx + k];
+    const int32_t row = h_pidx[k];
     if (row >= 0 && row < N) win_owner[row] = -1;
   }
   if (status != PGO_OK) return fail(status, msg);
@@ -156,29 +140,27 @@ int pgo_handle::window_solve(const char* who, int32_t nw, const int32_t* pose_pt
   // ---- device
   HIPC(hipSetDevice(device));
   const int64_t rec_rows = (int64_t)max_iters + 1;
-  auto up16 = [](int64_t b) { return (b + 15) / 16 * 16; };
-  const int64_t b_rec = 0, b_out = b_rec + up16(TE * dev::WIN_REC * 8), b_res = b_out + up16(TP * 3 * 8),
-                b_its = b_res + up16((int64_t)nw * (int64_t)sizeof(pgo_window_result)),
-                b_all = b_its + (records ? up16((int64_t)nw * rec_rows * (int64_t)sizeof(pgo_iter_record)) : 0);
-  PGOC(win_reserve(&win_in, &win_in_cap, n_int * 4));
-  PGOC(win_reserve(&win_work, &win_work_cap, std::max<int64_t>(b_all, 16)));
+  pgo::Layout LW;   // work = per-edge records | poses out | results | iteration records
+  const auto s_rec = LW.add<double>(TE * dev::WIN_REC), s_out = LW.add<double>(TP * 3);
+  const auto s_res = LW.add<pgo_window_result>(nw);
+  const auto s_its = LW.add<pgo_iter_record>(records ? nw * rec_rows : 0);
+  PGOC(reserve(win_in, LI.bytes()));
+  PGOC(reserve(win_work, LW.bytes()));
   const size_t lds_max = (size_t)dev::win_lds_doubles(3 * PGO_WINDOW_MAX_POSES) * sizeof(double);
   if (!win_lds_set) {   // more than 64 KiB of LDS needs the kernel's dynamic-LDS attribute
     HIPC(hipFuncSetAttribute(reinterpret_cast<const void*>(&dev::k_window_solve<>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
     win_lds_set = true;
   }
-  HIPC(hipMemcpyAsync(win_in, M, (size_t)n_int * 4, hipMemcpyHostToDevice, stream));
-  char* wk = static_cast<char*>(win_work);
-  if (records) HIPC(hipMemsetAsync(wk + b_its, 0, (size_t)(b_all - b_its), stream));
-  const int32_t* I = static_cast<const int32_t*>(win_in);
+  HIPC(hipMemcpyAsync(win_in.p, win_host.data(), win_host.size(), hipMemcpyHostToDevice, stream));
+  if (records) HIPC(hipMemsetAsync(s_its.in(win_work.p), 0, (size_t)s_its.bytes(), stream));
   dev::WinArgs A;
-  A.win = reinterpret_cast<const dev::WinDesc*>(I + o_desc);
-  A.pidx = I + o_pidx;
-  A.eloc = I + o_eloc;
-  A.eab = I + o_eab;
-  A.blk = I + o_blk;
-  A.blk_ptr = I + o_bptr;
-  A.ent = I + o_ent;
+  A.win = s_desc.in(win_in.p);
+  A.pidx = s_pidx.in(win_in.p);
+  A.eloc = s_eloc.in(win_in.p);
+  A.eab = s_eab.in(win_in.p);
+  A.blk = s_blk.in(win_in.p);
+  A.blk_ptr = s_bptr.in(win_in.p);
+  A.ent = s_ent.in(win_in.p);
   A.poses = poses;
   A.mx = e_mx;
   A.my = e_my;
@@ -202,20 +184,17 @@ int pgo_handle::window_solve(const char* who, int32_t nw, const int32_t* pose_pt
   A.min_relative_decrease = opt.min_relative_decrease;
   A.min_lm_diagonal = opt.min_lm_diagonal;
   A.max_lm_diagonal = opt.max_lm_diagonal;
-  A.rec = reinterpret_cast<double*>(wk + b_rec);
-  A.poses_out = reinterpret_cast<double*>(wk + b_out);
-  A.results = reinterpret_cast<pgo_window_result*>(wk + b_res);
-  A.records = records ? reinterpret_cast<pgo_iter_record*>(wk + b_its) : nullptr;
+  A.rec = s_rec.in(win_work.p);
+  A.poses_out = s_out.in(win_work.p);
+  A.results = s_res.in(win_work.p);
+  A.records = records ? s_its.in(win_work.p) : nullptr;
   const size_t lds = (size_t)dev::win_lds_doubles(n3cap) * sizeof(double);
   hipLaunchKernelGGL(dev::k_window_solve<>, dim3(nw), dim3(dev::WIN_WG), lds, stream, A);
   PGOC(check_launch("k_window_solve"));
-  if (poses_out && TP > 0) HIPC(hipMemcpyAsync(poses_out, wk + b_out, (size_t)TP * 3 * sizeof(double), hipMemcpyDeviceToHost, stream));
-  HIPC(hipMemcpyAsync(results, wk + b_res, (size_t)nw * sizeof(pgo_window_result), hipMemcpyDeviceToHost, stream));
-  if (records) HIPC(hipMemcpyAsync(records, wk + b_its, (size_t)nw * rec_rows * sizeof(pgo_iter_record), hipMemcpyDeviceToHost, stream));
-  if (commit) {   // as pgo_set_poses: the running solve (if any) is stale
-    lin_valid = false;
-    lm_active = false;
-  }
+  if (poses_out && TP > 0) HIPC(hipMemcpyAsync(poses_out, A.poses_out, (size_t)s_out.bytes(), hipMemcpyDeviceToHost, stream));
+  HIPC(hipMemcpyAsync(results, A.results, (size_t)s_res.bytes(), hipMemcpyDeviceToHost, stream));
+  if (records) HIPC(hipMemcpyAsync(records, A.records, (size_t)s_its.bytes(), hipMemcpyDeviceToHost, stream));
+  if (commit) solve_is_stale();   // as pgo_set_poses
   return sync();
 }
 
