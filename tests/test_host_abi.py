@@ -263,7 +263,7 @@ def test_debug_knobs_are_named_and_documented(pgo):
         pgo.set_knob("no_such_knob", 1)
     assert e.value.status == -1
     # ... and every name in the library's table is documented: the table is the one string list next to g_knobs
-    src = open(os.path.join(ROOT, "toy-robust-backend-slam_amd", "csrc", "solver_abi.hip")).read()
+    src = open(os.path.join(ROOT, "toy-robust-backend-slam_amd", "csrc", "knobs.cpp")).read()
     table = re.search(r"Knob g_knobs\[\] = \{(.*?)\};", src, flags=re.S).group(1)
     assert set(re.findall(r'\{"([a-z_0-9]+)"', table)) == set(documented)
 

@@ -24,8 +24,6 @@
 #include "comm.h"
 #include "pgo_internal.h"
 
-long long knob(const char* name);   // test hooks (solver_abi.hip)
-
 namespace pgo {
 
 // ------------------------------------------------------------------ RCCL

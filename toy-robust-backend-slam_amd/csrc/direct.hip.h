@@ -27,14 +27,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "constants.h"
+
 namespace pgo {
 namespace dev {
 
 constexpr int DLR_REC = 16;  // doubles per pose: input record M (6: 00 01 02 11 12 22) | C (9, row-major) | pad;
                              // factor record W (9, row-major) | S^-1 (6) | pad
 constexpr int DLR_V = 18;    // doubles per low-rank edge: Xa (9) | Xb (9), X[k][c] = d e_k / d (pose)_c * scale_c
-constexpr int CHOL_NB = 32;
-constexpr int DLR_MAX_SEP = 15;  // separator poses: the chain factorisation runs nsep + 1 pieces side by side (3 separators up to ~2000 poses)
 
 struct DlrArgs {
   int32_t n;                  // poses
@@ -257,7 +257,6 @@ __global__ __launch_bounds__(64) void k_dlr_factor(const double* __restrict__ tr
 // Column c < K is row c of V (non-zero on the two endpoint poses of its edge); column `vec_col` is the dense vector
 // rhs_b - rhs_sub (rhs_sub may be null).  One lane per column, a workgroup = 256 columns of one segment.
 constexpr int DLR_PRE = 18;   // doubles per pose of the prefix products: G (9) | Gb (9), row-major
-constexpr int DLR_MAX_SEG = 64;
 struct DlrColsArgs {
   const double* fac;
   const double* pre;

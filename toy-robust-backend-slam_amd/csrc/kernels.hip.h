@@ -14,12 +14,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "constants.h"
 #include "edge_model.h"
 
 namespace pgo {
 namespace dev {
 
-constexpr int WG = 256;          // workgroup size of every kernel here (4 waves)
 // Edge record, 14 doubles = 112 B (16-byte aligned):  A = d e/d P1 (9, row-major) | g2 | r (3) | cost.
 // The second Jacobian block is implied by the structure of the SE(2) error (also under DCS and the
 // Huber corrector, which scale whole rows / add e (x) grad psi with grad psi antisymmetric in (x,y)):
@@ -37,8 +37,6 @@ template <bool INFO> struct RecLayout {
   static constexpr int LDS = N + 1;                 // odd staging stride
   static constexpr int R0 = INFO ? 12 : 10;         // first residual entry
 };
-constexpr int PS = 3;            // doubles per pose in the GATHERED vector p.  Padding to 4 (32 B, never straddling a
-                                 // 64-byte sector) was measured: no fewer fetched bytes (FETCH_SIZE 566 vs 557 MiB), so 3.
 
 // ------------------------------------------------- streaming accesses
 // Data that a kernel touches exactly once (matrix / factor streams, CG vectors) is moved with the non-temporal hint so
@@ -1626,8 +1624,7 @@ __global__ __launch_bounds__(WG) void k_cg_update1_g(CgVec V, GroupPre G, int pa
 // step k of all 64 lanes is one coalesced 512-byte access; the vectors go through a wave-private LDS tile (coalesced global
 // access, strided LDS access with one pad per chunk: conflict-free).  120 B/pose of factors per PCG iteration (dense 4-pose
 // blocks: 288 B/pose).
-constexpr int CHAIN_CHUNK = 4;                        // the segment length is a multiple of this
-constexpr int CHAIN_TILE = 256;                       // rows of the largest tile = 64 lanes x CHAIN_CHUNK: n_pad is a multiple
+// (CHAIN_CHUNK: the segment length is a multiple of it; CHAIN_TILE: rows of the largest tile -- constants.h)
 
 __host__ __device__ __forceinline__ int64_t chain_tidx(int64_t i) {
   return (i & ~(int64_t)(CHAIN_TILE - 1)) + ((i & (CHAIN_CHUNK - 1)) << 6) + ((i & (CHAIN_TILE - 1)) / CHAIN_CHUNK);

@@ -5,12 +5,17 @@
 #include <string>
 #include <vector>
 
+#include "constants.h"
 #include "pgo.h"
 
 namespace pgo {
 
 // thread-local detail text behind pgo_last_error()
 int fail(int status, const std::string& msg);
+
+// test hooks (pgo_debug_set_knob, include/pgo.h; knobs.cpp): process-wide, read when a handle is created.  -1 = library default.
+long long knob(const char* name);
+int require_device(int device);   // a gfx950 device of that index is visible (solver_abi.hip)
 
 // ---------------------------------------------------------------- host graph
 // Flat-array replacement of ReadG2O's nNodes / nEdgesOdometry / nEdgesClosure /
@@ -72,11 +77,6 @@ struct ShardStructure {
   std::vector<int32_t> halo_send_row, halo_recv_row;   // global rows
   std::vector<int64_t> halo_send_off, halo_recv_off;   // world + 1 each, in rows
 };
-
-#ifndef PGO_TILE_INC
-#define PGO_TILE_INC 256   // (experiment builds may lower it: smaller tiles, more workgroups)
-#endif
-constexpr int TILE_INC = PGO_TILE_INC;
 
 inline int32_t rows_per_rank(int32_t n_poses, int world, int row_align) {
   const int64_t rpr = ((int64_t)n_poses + world - 1) / world;

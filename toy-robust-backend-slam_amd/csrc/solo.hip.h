@@ -21,7 +21,6 @@ namespace dev {
 constexpr int SOLO_WG = 512;              // 8 waves: two 256-lane halves for the SpMV, 8 chain tiles at a time
 constexpr int SOLO_U = 4;                 // row tiles per half per SpMV round
 constexpr int SOLO_TILES = 2 * SOLO_U;    // row tiles in flight per round
-constexpr int SOLO_CH = 4;                // chain layout: 256-row wave tiles
 
 struct SoloProb {
   int32_t row0, nrows;      // local rows [row0, row0 + nrows); row0 is a multiple of 256

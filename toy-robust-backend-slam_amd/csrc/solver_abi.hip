@@ -68,8 +68,8 @@ int pgo_handle::set_active(const uint8_t* edge_active, const uint8_t* pose_const
     }
     for (int64_t i = 0; i < N; ++i) n_cst += cst[i];
   }
-  if (edge_active && (direct || dl_possible || dl_ready || act_chain_cut)) {
-    // the direct solve's chain: the first local edge between every pair of consecutive poses (direct_setup)
+  if (edge_active && (direct() || takeover() || dl_ready || act_chain_cut)) {
+    // the direct solve's chain: the first local edge between every pair of consecutive poses (direct_chain_lists)
     std::vector<uint8_t> seen((size_t)N, 0);
     for (int64_t k = 0; k < EL && !chain_cut; ++k) {
       const int32_t lo_p = std::min(S.ia[k], S.ib[k]), hi_p = std::max(S.ia[k], S.ib[k]);
@@ -81,7 +81,7 @@ int pgo_handle::set_active(const uint8_t* edge_active, const uint8_t* pose_const
   }
   std::vector<int32_t> dead;
   int32_t* dead_buf = nullptr;
-  const bool coarse_built = (use_coarse || co_cov_ready) && !co_multi;
+  const bool coarse_built = co_built() && !co_multi();
   // device buffers this call may need, before anything changes
   if (!restore && !batch_mode && !act_mask) PGOC(dalloc(&act_mask, N));
   if (coarse_built) {
@@ -90,12 +90,12 @@ int pgo_handle::set_active(const uint8_t* edge_active, const uint8_t* pose_const
     if (!restore) act_const_h = cst;
     coarse_dead_list(&dead);
     act_const_h.swap(keep);
-    if ((int)dead.size() > co_dead_cap) PGOC(dalloc(&dead_buf, co_nagg));   // (once per handle: every later list fits)
+    if ((int)dead.size() > co_dead_cap) PGOC(dalloc(&dead_buf, CO().co_nagg));   // (once per handle: every later list fits)
   }
   // apply
   if (dead_buf) {
     co_dead = dead_buf;
-    co_dead_cap = co_nagg;
+    co_dead_cap = CO().co_nagg;
   }
   for (int64_t k = 0; k < EL; ++k) {
     const bool on = !edge_active || edge_active[S.orig_edge[k]];
@@ -112,18 +112,7 @@ int pgo_handle::set_active(const uint8_t* edge_active, const uint8_t* pose_const
     act_const_h = cst;
     if (!batch_mode) fixed_mask = act_mask;
   }
-  if (chain_cut != act_chain_cut) {
-    if (chain_cut) {
-      act_saved_direct = direct;
-      act_saved_possible = dl_possible;
-      direct = false;
-      dl_possible = false;
-    } else {
-      direct = act_saved_direct;
-      dl_possible = act_saved_possible;
-    }
-    act_chain_cut = chain_cut;
-  }
+  act_chain_cut = chain_cut;   // (direct(), takeover(): PCG while the chain is cut)
   solve_is_stale();
   if (EL > 0) PGOC(upload(e_flags, S.flags));
   if (fixed_mask) PGOC(upload(fixed_mask, restore ? fixed_mask_h : act_const_h));
@@ -135,20 +124,7 @@ int pgo_handle::set_active(const uint8_t* edge_active, const uint8_t* pose_const
 }
 
 // ====================================================================== C-ABI
-namespace {
-struct Knob {
-  const char* name;
-  std::atomic<long long> value;
-};
-Knob g_knobs[] = {{"spmv_pipe", {-1}}, {"fused_p", {-1}}, {"direct_fail_at", {-1}}, {"direct_setup_fail", {-1}}, {"single_reduction", {-1}}, {"verify_residual", {-1}}, {"shm_timeout_s", {-1}}, {"pad_tiles", {-1}}, {"cov_poses_per_pass", {-1}}, {"cov_direct_cols", {-1}}, {"gate_joint_shape", {-1}}, {"score_grid", {-1}}, {"coarsen_grid", {-1}}, {"gnc_grid", {-1}}, {"support_grid", {-1}}};
-}  // namespace
-long long knob(const char* name) {
-  for (Knob& k : g_knobs)
-    if (!strcmp(k.name, name)) return k.value.load();
-  return -1;
-}
-
-int require_device(int device) {
+int pgo::require_device(int device) {
   int n = 0;
   hipError_t e = hipGetDeviceCount(&n);
   if (e != hipSuccess || n <= 0) return fail(PGO_ERR_NO_DEVICE, "no HIP device visible (this backend has no CPU path)");
@@ -463,16 +439,6 @@ int pgo_solve_batch(pgo_t* const* handles, int32_t n, pgo_summary* summaries, in
   return PGO_OK;
 }
 
-int pgo_debug_set_knob(const char* name, long long value) {
-  if (!name) return fail(PGO_ERR_INVALID_ARG, "pgo_debug_set_knob: null name");
-  for (Knob& k : g_knobs)
-    if (!strcmp(k.name, name)) {
-      k.value.store(value < 0 ? -1 : value);
-      return PGO_OK;
-    }
-  return fail(PGO_ERR_INVALID_ARG, std::string("pgo_debug_set_knob: unknown knob ") + name);
-}
-
 int pgo_get_info(const pgo_t* h, pgo_handle_info* out) {
   if (!h || !out) return fail(PGO_ERR_INVALID_ARG, "pgo_get_info: null");
   memset(out, 0, sizeof *out);
@@ -485,28 +451,28 @@ int pgo_get_info(const pgo_t* h, pgo_handle_info* out) {
   out->n_edges_local = h->S.n_edges_local;
   out->n_tiles = h->S.n_tiles();
   out->n_incidences = h->S.n_inc_real;
-  out->pcg_block_poses = h->grp_B;
-  out->pcg_chain_len = h->chain_len;
-  out->chain_kernel = h->chain_chunk;
+  out->pcg_block_poses = h->plan.own.grp_B;
+  out->pcg_chain_len = h->plan.all.chain_len;
+  out->chain_kernel = h->plan.all.chain_chunk;
   out->pose_ordering = h->perm.empty() ? 0 : 1;
-  out->halo_exchange = h->use_halo ? 1 : 0;
-  out->halo_overlap = h->overlap ? 1 : 0;
+  out->halo_exchange = h->plan.all.use_halo ? 1 : 0;
+  out->halo_overlap = h->plan.own.overlap ? 1 : 0;
   out->halo_send_rows = (int64_t)h->S.halo_send_row.size();
   out->halo_recv_rows = (int64_t)h->S.halo_recv_row.size();
   out->device_bytes = h->device_bytes;
   out->host_enqueue_us_per_pcg_iter = h->n_enqueued > 0 ? 1e6 * h->t_enqueue / (double)h->n_enqueued : 0.0;
   out->pcg_graph_replay = (h->cg_graph_exec != nullptr && !h->graph_failed) ? 1 : 0;
-  out->linear_solver = h->direct ? 2 : 1;
-  out->direct_rank = h->direct ? h->dl_K : 0;
+  out->linear_solver = h->direct() ? 2 : 1;
+  out->direct_rank = h->direct() ? h->plan.dl.dl_K : 0;
   out->direct_fallbacks = h->dl_fallbacks;
   out->direct_switched_at = h->dl_switched_at;
-  out->pcg_single_reduction = h->use_sr ? 1 : 0;
-  out->pcg_coarse_poses = h->use_coarse ? h->co_agg : 0;
-  out->pcg_coarse_rank = h->use_coarse ? h->co_K : 0;
+  out->pcg_single_reduction = h->plan.all.use_sr ? 1 : 0;
+  out->pcg_coarse_poses = h->coarse_on() ? h->CO().co_agg : 0;
+  out->pcg_coarse_rank = h->coarse_on() ? h->CO().co_K : 0;
   out->pcg_coarse_off_iters = h->co_off_iters;
-  out->direct_separators = h->direct ? h->dl_nsep : 0;
-  out->direct_segments = h->direct ? h->dl_nseg : 0;
-  out->direct_refine_kernel = h->direct ? (h->dl_pre2 ? 1 : 2) : 0;
+  out->direct_separators = h->direct() ? h->plan.dl.dl_nsep : 0;
+  out->direct_segments = h->direct() ? h->plan.dl.dl_nseg : 0;
+  out->direct_refine_kernel = h->direct() ? (h->dl_pre2 ? 1 : 2) : 0;
   out->n_active_edges = h->n_active_edges;
   out->n_constant_poses = h->n_constant_poses;
   return PGO_OK;
@@ -530,7 +496,7 @@ int pgo_debug_normal_eq(pgo_t* h, double* g_out, double* hdiag_out) {
   if (h->comm && h->comm->world > 1) return fail(PGO_ERR_UNSUPPORTED, "world == 1 only");
   HIPC(hipSetDevice(h->device));
   h->lm_active = false;
-  hipLaunchKernelGGL(dev::k_jacobi_scale<>, dim3(h->g_rows), dim3(dev::WG), 0, h->stream, h->hd, h->S.n_loc, h->S.lo,
+  hipLaunchKernelGGL(dev::k_jacobi_scale<>, dim3(h->plan.own.g_rows), dim3(dev::WG), 0, h->stream, h->hd, h->S.n_loc, h->S.lo,
                      h->fixed_internal, 0, h->scale, (const uint8_t*)h->fixed_mask);
   PGOC(h->check_launch("k_jacobi_scale"));
   int st = h->linearize(false);
@@ -571,7 +537,7 @@ int pgo_debug_spmv(pgo_t* h, const double* x, double* yout) {
     src = tmp.data();
   }
   HIPC(hipMemcpyAsync(h->y, src, (size_t)3 * N * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(dev::k_scatter_owned<>, dim3(h->g_flat), dim3(dev::WG), 0, h->stream, h->S.n_loc, h->S.lo, h->y, h->p_full);
+  hipLaunchKernelGGL(dev::k_scatter_owned<>, dim3(h->plan.own.g_flat), dim3(dev::WG), 0, h->stream, h->S.n_loc, h->S.lo, h->y, h->p_full);
   PGOC(h->spmv_enqueue(h->p_full, h->ap, h->part[0], 0, nullptr));
   if (h->perm.empty()) {
     HIPC(hipMemcpyAsync(yout, h->ap, (size_t)3 * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -590,7 +556,7 @@ int pgo_debug_spmv(pgo_t* h, const double* x, double* yout) {
 // not affected.
 static int prepare_for_debug(pgo_handle* h) {
   PGOC(h->prepare_system());
-  if (h->direct) PGOC(h->prepare_preconditioner());   // (a handle on the direct solve does not factorise it per LM iteration)
+  if (h->direct()) PGOC(h->prepare_preconditioner());   // (a handle on the direct solve does not factorise it per LM iteration)
   return PGO_OK;
 }
 
@@ -608,7 +574,7 @@ int pgo_debug_system_spmv(pgo_t* h, const double* x, double* yout, double* d2_ou
     src = tmp.data();
   }
   HIPC(hipMemcpyAsync(h->ap, src, (size_t)3 * N * sizeof(double), hipMemcpyHostToDevice, h->stream));   // ap: scratch input
-  hipLaunchKernelGGL(dev::k_scatter_owned<>, dim3(h->g_flat), dim3(dev::WG), 0, h->stream, h->S.n_loc, h->S.lo, (const double*)h->ap, h->p_full);
+  hipLaunchKernelGGL(dev::k_scatter_owned<>, dim3(h->plan.own.g_flat), dim3(dev::WG), 0, h->stream, h->S.n_loc, h->S.lo, (const double*)h->ap, h->p_full);
   PGOC(h->check_launch("k_scatter_owned"));
   PGOC(h->spmv_enqueue(h->p_full, h->ap, h->part[0], 1, nullptr));
   std::vector<double> ytmp((size_t)3 * N), dtmp(d2_out ? (size_t)3 * N : 0);
@@ -630,7 +596,7 @@ int pgo_debug_system_spmv(pgo_t* h, const double* x, double* yout, double* d2_ou
 // with the second preconditioner level (a collective call: every rank passes the whole r and receives z on its own rows).
 int pgo_debug_precond(pgo_t* h, const double* r_in, double* z_out) {
   if (!h || !r_in || !z_out) return fail(PGO_ERR_INVALID_ARG, "pgo_debug_precond: null");
-  if (h->comm && h->comm->world > 1 && !h->co_multi) return fail(PGO_ERR_UNSUPPORTED, "world == 1 only (several ranks: with pcg_coarse_poses > 0)");
+  if (h->comm && h->comm->world > 1 && !h->co_multi()) return fail(PGO_ERR_UNSUPPORTED, "world == 1 only (several ranks: with pcg_coarse_poses > 0)");
   if (!h->lin_valid || h->iter < 1) return fail(PGO_ERR_INVALID_ARG, "pgo_debug_precond: run at least one LM iteration first");
   HIPC(hipSetDevice(h->device));
   const int64_t N = h->S.n_poses, lo = h->S.lo, NL = h->S.n_loc;
@@ -644,31 +610,31 @@ int pgo_debug_precond(pgo_t* h, const double* r_in, double* z_out) {
     HIPC(hipMemcpyAsync(h->ap, src + 3 * lo, (size_t)3 * NL * sizeof(double), hipMemcpyHostToDevice, h->stream));
   PGOC(prepare_for_debug(h));
   dev::CgVec V = h->cg_vec();
-  if (h->chain_len) {
+  if (h->plan.all.chain_len) {
     h->launch_cg_init_chain(h->ap, h->part[0], h->part[1]);
-  } else if (h->grp_B > 1) {
+  } else if (h->plan.own.grp_B > 1) {
     dev::GroupPre GP;
     GP.ginv = h->ginv;
-    GP.B = h->grp_B;
-    GP.nb = h->grp_nb;
-    GP.nb_pad = h->grp_pad;
-    GP.n_groups = h->n_groups;
-    hipLaunchKernelGGL(dev::k_cg_init_g<>, dim3(h->g_grp), dim3(dev::WG), 0, h->stream, V, GP, (const double*)h->ap, h->part[0], h->part[1]);
+    GP.B = h->plan.own.grp_B;
+    GP.nb = h->plan.own.grp_nb;
+    GP.nb_pad = h->plan.own.grp_pad;
+    GP.n_groups = h->plan.own.n_groups;
+    hipLaunchKernelGGL(dev::k_cg_init_g<>, dim3(h->plan.own.g_grp), dim3(dev::WG), 0, h->stream, V, GP, (const double*)h->ap, h->part[0], h->part[1]);
   } else {
-    hipLaunchKernelGGL(dev::k_cg_init<>, dim3(h->g_vec), dim3(dev::WG), 0, h->stream, V, (const double*)h->ap, h->part[0], h->part[1]);
+    hipLaunchKernelGGL(dev::k_cg_init<>, dim3(h->plan.own.g_vec), dim3(dev::WG), 0, h->stream, V, (const double*)h->ap, h->part[0], h->part[1]);
   }
   PGOC(h->check_launch("k_cg_init (debug)"));
-  if (h->use_coarse && h->co_multi) {   // several ranks: r_c through the all-reduce, the replicated coarse solve, the own rows of P e_c
+  if (h->coarse_on() && h->co_multi()) {   // several ranks: r_c through the all-reduce, the replicated coarse solve, the own rows of P e_c
     PGOC(h->coarse_restrict_reduce(h->part[0], 1, h->part[1], 1, nullptr));
     PGOC(h->coarse_solve(h->co_dotp, nullptr));
     hipLaunchKernelGGL(dev::k_coarse_prolong_m<>, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((NL + 255) / 256, 512))), dim3(256), 0,
-                       h->stream, (int)NL, (int)lo, h->co_agg, (const double*)h->co_pb, (int64_t)N, (const double*)h->co_ec, h->z, (double*)nullptr,
+                       h->stream, (int)NL, (int)lo, h->CO().co_agg, (const double*)h->co_pb, (int64_t)N, (const double*)h->co_ec, h->z, (double*)nullptr,
                        (const int32_t*)h->co_ok);
     PGOC(h->check_launch("k_coarse_prolong_m"));
-  } else if (h->use_coarse) {   // the second level's share of z
+  } else if (h->coarse_on()) {   // the second level's share of z
     PGOC(h->coarse_solve(h->part[3], nullptr));
     hipLaunchKernelGGL(dev::k_coarse_prolong<>, dim3((unsigned)std::min<int64_t>((h->S.n_loc + 255) / 256, 512)), dim3(256), 0, h->stream,
-                       (int)h->S.n_loc, h->co_agg, (const double*)h->co_pb, (const double*)h->co_ec, h->z, (double*)nullptr, (const int32_t*)h->co_ok);
+                       (int)h->S.n_loc, h->CO().co_agg, (const double*)h->co_pb, (const double*)h->co_ec, h->z, (double*)nullptr, (const int32_t*)h->co_ok);
     PGOC(h->check_launch("k_coarse_prolong"));
   }
   std::vector<double> ztmp((size_t)3 * N, 0.0);   // (several ranks: the peers' rows stay 0)
@@ -685,7 +651,7 @@ int pgo_debug_precond(pgo_t* h, const double* r_in, double* z_out) {
 int pgo_debug_direct_solve(pgo_t* h, const double* b_in, int32_t refine_steps, double* y_out) {
   if (!h || !b_in || !y_out) return fail(PGO_ERR_INVALID_ARG, "pgo_debug_direct_solve: null");
   if (refine_steps < -1 || refine_steps > 3) return fail(PGO_ERR_INVALID_ARG, "pgo_debug_direct_solve: refine_steps is -1 (the handle's own) or 0 .. 3");
-  if (!h->direct || !h->dl_ready) return fail(PGO_ERR_UNSUPPORTED, "pgo_debug_direct_solve: the handle is not on the direct solve");
+  if (!h->direct() || !h->dl_ready) return fail(PGO_ERR_UNSUPPORTED, "pgo_debug_direct_solve: the handle is not on the direct solve");
   if (!h->lin_valid) return fail(PGO_ERR_INVALID_ARG, "pgo_debug_direct_solve: call pgo_lm_begin first");
   HIPC(hipSetDevice(h->device));
   const size_t n3 = (size_t)3 * h->S.n_loc, npf = (size_t)dev::PS * h->n_full;   // (one rank, identity ordering: n_loc = N)
@@ -704,7 +670,7 @@ int pgo_debug_direct_solve(pgo_t* h, const double* b_in, int32_t refine_steps, d
     HIPC(hipMemcpyAsync(save + off_scal, h->scal, N_SCAL * sizeof(double), d2d, h->stream));
     HIPC(hipMemcpyAsync(save + off_b, b_in, n3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
     PGOC(h->prepare_system());
-    PGOC(h->direct_enqueue(save + off_b, refine_steps < 0 ? h->dl_refine : refine_steps));
+    PGOC(h->direct_enqueue(save + off_b, refine_steps < 0 ? h->plan.dl.dl_refine : refine_steps));
     HIPC(hipMemcpyAsync(y_out, h->y, n3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPC(hipMemcpyAsync(h->y, save, n3 * sizeof(double), d2d, h->stream));
     HIPC(hipMemcpyAsync(h->r, save + off_r, n3 * sizeof(double), d2d, h->stream));
@@ -759,7 +725,7 @@ int pgo_bench_assemble(pgo_t* h, int reps, pgo_kernel_stats* out) {
   // every record read once (112 B/edge); per incidence 8 B indices + 72 B block written; per row 72 B out + 4 B
   // pointer + 24 B scale
   // chain preconditioner: + the 72-byte block (i, i-1) per row into the factorisation's input record
-  out->algorithmic_bytes = 112.0 * h->S.n_edges_local + 80.0 * (double)h->S.n_inc_real + (100.0 + (h->chain_len ? 72.0 : 0.0)) * h->S.n_loc;
+  out->algorithmic_bytes = 112.0 * h->S.n_edges_local + 80.0 * (double)h->S.n_inc_real + (100.0 + (h->plan.all.chain_len ? 72.0 : 0.0)) * h->S.n_loc;
   return PGO_OK;
 }
 
@@ -773,7 +739,7 @@ int pgo_bench_spmv(pgo_t* h, int reps, pgo_kernel_stats* out) {
   out->units = h->S.n_inc_real + h->S.n_loc;
   // 76 B per off-diagonal block (value + column) ; per row: 48 B diagonal planes + 24 B D'D + 4 B row
   // pointer + 24 B y + 24 B p; the product kernel k_spmv_p reads the diagonal with D'D folded in (k_prepare): 24 B less
-  out->algorithmic_bytes = 76.0 * (double)h->S.n_inc_real + (h->spmv_pipe ? 100.0 : 124.0) * h->S.n_loc;
+  out->algorithmic_bytes = 76.0 * (double)h->S.n_inc_real + (h->plan.own.spmv_pipe ? 100.0 : 124.0) * h->S.n_loc;
   return PGO_OK;
 }
 
@@ -786,23 +752,23 @@ int pgo_bench_precond(pgo_t* h, int reps, pgo_kernel_stats* out) {
   dev::CgVec V = h->cg_vec();
   double ms = 0;
   const double nl = (double)h->S.n_loc;
-  if (h->chain_len) {
+  if (h->plan.all.chain_len) {
     PGOC(time_launches(h, reps, [&] { h->launch_cg_init_chain(h->gs, h->part[0], h->part[1]); }, &ms));
     out->algorithmic_bytes = (120.0 + 24.0 + 4 * 24.0) * nl;   // W, S^-1 planes + b read; y, r, z, p written
-  } else if (h->grp_B > 1) {
+  } else if (h->plan.own.grp_B > 1) {
     dev::GroupPre GP;
     GP.ginv = h->ginv;
-    GP.B = h->grp_B;
-    GP.nb = h->grp_nb;
-    GP.nb_pad = h->grp_pad;
-    GP.n_groups = h->n_groups;
+    GP.B = h->plan.own.grp_B;
+    GP.nb = h->plan.own.grp_nb;
+    GP.nb_pad = h->plan.own.grp_pad;
+    GP.n_groups = h->plan.own.n_groups;
     PGOC(time_launches(h, reps, [&] {
-      hipLaunchKernelGGL(dev::k_cg_init_g<>, dim3(h->g_grp), dim3(dev::WG), 0, h->stream, V, GP, (const double*)h->gs, h->part[0], h->part[1]);
+      hipLaunchKernelGGL(dev::k_cg_init_g<>, dim3(h->plan.own.g_grp), dim3(dev::WG), 0, h->stream, V, GP, (const double*)h->gs, h->part[0], h->part[1]);
     }, &ms));
-    out->algorithmic_bytes = (8.0 * 3 * h->grp_nb + 24.0 + 4 * 24.0) * nl;
+    out->algorithmic_bytes = (8.0 * 3 * h->plan.own.grp_nb + 24.0 + 4 * 24.0) * nl;
   } else {
     PGOC(time_launches(h, reps, [&] {
-      hipLaunchKernelGGL(dev::k_cg_init<>, dim3(h->g_vec), dim3(dev::WG), 0, h->stream, V, (const double*)h->gs, h->part[0], h->part[1]);
+      hipLaunchKernelGGL(dev::k_cg_init<>, dim3(h->plan.own.g_vec), dim3(dev::WG), 0, h->stream, V, (const double*)h->gs, h->part[0], h->part[1]);
     }, &ms));
     out->algorithmic_bytes = (48.0 + 24.0 + 4 * 24.0) * nl;
   }

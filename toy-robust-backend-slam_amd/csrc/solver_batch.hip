@@ -52,13 +52,13 @@ int pgo_batch::begin() {
   const pgo_options& o = H.opt;
   for (State& z : st) z = State();
   // iteration 0: unit scales -> column norms -> Jacobi scaling (per column, so per problem by construction)
-  hipLaunchKernelGGL(dev::k_jacobi_scale<>, dim3(H.g_rows), dim3(dev::WG), 0, H.stream, H.hd, H.S.n_loc, H.S.lo, -1, 0, H.scale,
+  hipLaunchKernelGGL(dev::k_jacobi_scale<>, dim3(H.plan.own.g_rows), dim3(dev::WG), 0, H.stream, H.hd, H.S.n_loc, H.S.lo, -1, 0, H.scale,
                      (const uint8_t*)H.fixed_mask);
   PGOC(H.check_launch("k_jacobi_scale"));
   PGOC(H.eval_enqueue(H.poses, nullptr, 1, true, 0));
   PGOC(H.assemble_enqueue());
   if (o.jacobi_scaling) {
-    hipLaunchKernelGGL(dev::k_jacobi_scale<>, dim3(H.g_rows), dim3(dev::WG), 0, H.stream, H.hd, H.S.n_loc, H.S.lo, -1, 1, H.scale,
+    hipLaunchKernelGGL(dev::k_jacobi_scale<>, dim3(H.plan.own.g_rows), dim3(dev::WG), 0, H.stream, H.hd, H.S.n_loc, H.S.lo, -1, 1, H.scale,
                        (const uint8_t*)H.fixed_mask);
     PGOC(H.check_launch("k_jacobi_scale"));
     PGOC(H.assemble_enqueue());
@@ -111,9 +111,9 @@ int pgo_batch::iterate(bool* all_done) {
   A.A = H.spmv_args(H.p_full, H.ap, H.part[0], 1, nullptr);
   A.V = H.cg_vec();
   A.C = H.chain_pre();
-  if (!H.chain_len) A.C.cw = nullptr;
-  A.chain_steps = H.solo_steps;
-  A.scan_levels = H.solo_scan;
+  if (!H.plan.all.chain_len) A.C.cw = nullptr;
+  A.chain_steps = H.plan.all.solo_steps;
+  A.scan_levels = H.plan.all.solo_scan;
   A.b = H.gs;
   A.prob = d_prob;
   A.out = d_out;
@@ -186,7 +186,7 @@ int pgo_batch::iterate(bool* all_done) {
   }
   if (any_accept) {
     HIPC(hipMemcpyAsync(d_accept, h_accept.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, H.stream));
-    hipLaunchKernelGGL(dev::k_accept_rows<>, dim3(H.g_flat), dim3(dev::WG), 0, H.stream, H.S.n_loc, H.S.lo, (const int32_t*)H.prob_of_256,
+    hipLaunchKernelGGL(dev::k_accept_rows<>, dim3(H.plan.own.g_flat), dim3(dev::WG), 0, H.stream, H.S.n_loc, H.S.lo, (const int32_t*)H.prob_of_256,
                        (const int32_t*)d_accept, (const double*)H.cand, H.poses);
     PGOC(H.check_launch("k_accept_rows"));
     // re-linearise everything: the problems that did not move reproduce their records and blocks bit for bit

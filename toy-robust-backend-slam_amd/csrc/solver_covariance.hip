@@ -45,25 +45,25 @@ int precond_column(pgo_handle* h, const double* b, double* zc) {
   double* z_saved = h->z;
   h->z = zc;
   const dev::CgVec V = h->cg_vec();
-  if (h->chain_len) {
+  if (h->plan.all.chain_len) {
     h->launch_cg_init_chain(b, h->part[0], h->part[1]);
-  } else if (h->grp_B > 1) {
+  } else if (h->plan.own.grp_B > 1) {
     dev::GroupPre GP;
     GP.ginv = h->ginv;
-    GP.B = h->grp_B;
-    GP.nb = h->grp_nb;
-    GP.nb_pad = h->grp_pad;
-    GP.n_groups = h->n_groups;
-    hipLaunchKernelGGL(dev::k_cg_init_g<>, dim3(h->g_grp), dim3(dev::WG), 0, h->stream, V, GP, b, h->part[0], h->part[1]);
+    GP.B = h->plan.own.grp_B;
+    GP.nb = h->plan.own.grp_nb;
+    GP.nb_pad = h->plan.own.grp_pad;
+    GP.n_groups = h->plan.own.n_groups;
+    hipLaunchKernelGGL(dev::k_cg_init_g<>, dim3(h->plan.own.g_grp), dim3(dev::WG), 0, h->stream, V, GP, b, h->part[0], h->part[1]);
   } else {
-    hipLaunchKernelGGL(dev::k_cg_init<>, dim3(h->g_vec), dim3(dev::WG), 0, h->stream, V, b, h->part[0], h->part[1]);
+    hipLaunchKernelGGL(dev::k_cg_init<>, dim3(h->plan.own.g_vec), dim3(dev::WG), 0, h->stream, V, b, h->part[0], h->part[1]);
   }
   int st = h->check_launch("k_cg_init (covariance)");
-  if (st == PGO_OK && h->use_coarse) {   // the second level's share: restriction of r (= b), coarse solve, prolongation into z
+  if (st == PGO_OK && h->coarse_on()) {   // the second level's share: restriction of r (= b), coarse solve, prolongation into z
     st = h->coarse_solve(h->part[3], nullptr);
     if (st == PGO_OK) {
       hipLaunchKernelGGL(dev::k_coarse_prolong<>, dim3((unsigned)std::min<int64_t>((h->S.n_loc + 255) / 256, 512)), dim3(256), 0, h->stream,
-                         (int)h->S.n_loc, h->co_agg, (const double*)h->co_pb, (const double*)h->co_ec, zc, (double*)nullptr, (const int32_t*)h->co_ok);
+                         (int)h->S.n_loc, h->CO().co_agg, (const double*)h->co_pb, (const double*)h->co_ec, zc, (double*)nullptr, (const int32_t*)h->co_ok);
       st = h->check_launch("k_coarse_prolong (covariance)");
     }
   }
@@ -96,34 +96,22 @@ int spmm(pgo_handle* h, int m, int64_t ld, const double* p, double* y, double* p
 }
 
 // The rigid-body coarse level for handles that were created without it (direct solves, the inexact mode, pcg_coarse_poses = 0)
-// on graphs of >= 512 poses: its structure is built once, with the aggregate size of the auto rule, and used by covariance
-// calls only -- use_coarse stays off for the LM loop, and what coarse_setup changes in the LM loop's choices is put back.
+// on graphs of >= 512 poses: the plan sized it (plan.co_cov, plan_coarse_for_covariance); its structure is built once, here, and
+// used by covariance calls only -- the LM loop's plan does not know it.
 int coarse_for_covariance(pgo_handle* h) {
-  if (h->use_coarse || h->co_cov_ready || h->S.n_loc < 512) return PGO_OK;
-  const int64_t NL = h->S.n_loc;
-  int want = NL <= 8192 ? 16 : 64;
-  while (3 * ((NL + want - 1) / want) + 1 > COARSE_MAX_RANK) want *= 2;
-  const int saved_want = h->opt.pcg_coarse_poses;
-  const bool fused_p = h->fused_p, use_sr = h->use_sr, dl_possible = h->dl_possible;
-  h->opt.pcg_coarse_poses = want;
-  const int st = h->coarse_setup(0, nullptr, nullptr);   // (one rank: the edge lists are not read)
-  h->opt.pcg_coarse_poses = saved_want;
-  h->fused_p = fused_p;
-  h->use_sr = use_sr;
-  h->dl_possible = dl_possible;
-  h->co_cov_ready = st == PGO_OK && h->use_coarse;
-  h->use_coarse = false;
-  return st;
+  if (h->plan.co.on || h->co_cov_ready || h->S.n_loc < 512) return PGO_OK;
+  if (h->plan.co_cov.no) return fail(h->plan.co_cov.no.status, h->plan.co_cov.no.why);
+  if (!h->plan.co_cov.on) return PGO_OK;
+  PGOC(h->coarse_build(0, nullptr, nullptr));   // (one rank: the edge lists are not read)
+  h->co_cov_ready = true;
+  return PGO_OK;
 }
 
 // the level is on for the duration of a covariance call only
 struct CoarseOn {
   pgo_handle* h;
-  bool was;
-  explicit CoarseOn(pgo_handle* hh) : h(hh), was(hh->use_coarse) {
-    if (h->co_cov_ready) h->use_coarse = true;
-  }
-  ~CoarseOn() { h->use_coarse = was; }
+  explicit CoarseOn(pgo_handle* hh) : h(hh) { h->co_for_call = h->co_cov_ready; }
+  ~CoarseOn() { h->co_for_call = false; }
 };
 
 // the undamped system at the current poses: linearisation (when the LM loop's is not current), METHOD 2's switch
@@ -131,12 +119,12 @@ struct CoarseOn {
 // next iteration from unchanged inputs (prepare_system; METHOD 2: refresh_switch_system), so its results do not change.
 int setup_system(pgo_handle* h, bool with_preconditioner) {
   if (!h->lin_valid) {   // (not for METHOD 2: refused earlier) Jacobi scales and J'J at the current poses, as pgo_lm_begin
-    hipLaunchKernelGGL(dev::k_jacobi_scale<>, dim3(h->g_rows), dim3(dev::WG), 0, h->stream, h->hd, h->S.n_loc, h->S.lo, h->fixed_internal, 0, h->scale,
+    hipLaunchKernelGGL(dev::k_jacobi_scale<>, dim3(h->plan.own.g_rows), dim3(dev::WG), 0, h->stream, h->hd, h->S.n_loc, h->S.lo, h->fixed_internal, 0, h->scale,
                        (const uint8_t*)h->fixed_mask);
     PGOC(h->check_launch("k_jacobi_scale"));
     PGOC(h->linearize(false));
     if (h->opt.jacobi_scaling) {
-      hipLaunchKernelGGL(dev::k_jacobi_scale<>, dim3(h->g_rows), dim3(dev::WG), 0, h->stream, h->hd, h->S.n_loc, h->S.lo, h->fixed_internal, 1,
+      hipLaunchKernelGGL(dev::k_jacobi_scale<>, dim3(h->plan.own.g_rows), dim3(dev::WG), 0, h->stream, h->hd, h->S.n_loc, h->S.lo, h->fixed_internal, 1,
                          h->scale, (const uint8_t*)h->fixed_mask);
       PGOC(h->check_launch("k_jacobi_scale"));
       PGOC(h->linearize(true));
@@ -154,7 +142,7 @@ int setup_system(pgo_handle* h, bool with_preconditioner) {
     h->sw_fresh = false;   // the next LM iteration re-assembles for its radius (refresh_switch_system)
   }
   if (st == PGO_OK) st = h->prepare_system();
-  if (st == PGO_OK && h->direct && with_preconditioner) st = h->prepare_preconditioner();   // (a handle on the direct solve does not set it up per iteration)
+  if (st == PGO_OK && h->direct() && with_preconditioner) st = h->prepare_preconditioner();   // (a handle on the direct solve does not set it up per iteration)
   h->tr.radius = radius_saved;
   return st;
 }
@@ -207,7 +195,7 @@ struct Session {
     if (kc >= 0 && (kc < 3 || kc > DIRECT_COLS_MAX || kc % 3 != 0))
       return fail(PGO_ERR_INVALID_ARG, fn + ": the cov_direct_cols knob is a multiple of 3 in 3..768");
     direct_cols = (int)kc;
-    if ((h->comm && h->comm->world > 1) || h->co_multi) return fail(PGO_ERR_UNSUPPORTED, fn + ": one rank only");
+    if ((h->comm && h->comm->world > 1) || h->co_multi()) return fail(PGO_ERR_UNSUPPORTED, fn + ": one rank only");
     if (h->batch_mode) return fail(PGO_ERR_UNSUPPORTED, fn + ": not on batched handles");
     // information weighting: even the columns whose true residual reaches 1e-5 differ from a sparse direct inverse by ~1e-3 on
     // INTEL (others stall at 2e-5) -- refused rather than returning blocks of that quality
@@ -215,7 +203,7 @@ struct Session {
     if (!h->has_anchor())   // (opt.fixed_pose, or a pose made constant by pgo_set_active)
       return fail(PGO_ERR_UNSUPPORTED, fn + ": fixed_pose = -1 leaves the gauge free (J'J is singular)");
     // solver = 1 never falls back: a PCG handle, or a handle that pgo_set_active took off the direct solve (a cut chain)
-    if (direct && !(h->direct && h->dl_ready))
+    if (direct && !(h->direct() && h->dl_ready))
       return fail(PGO_ERR_UNSUPPORTED, fn + ": solver = 1 needs a handle on the direct solve (pgo_handle_info.linear_solver = 2)");
     N = h->S.n_poses;
     return PGO_OK;
@@ -279,7 +267,7 @@ struct Session {
     if (!direct) return o.poses_per_pass;
     if (direct_cols > 0) return direct_cols / 3;
     const int64_t n3_ = 3 * N, g_ = std::max<int64_t>(1, std::min<int64_t>((n3_ + dev::WG - 1) / dev::WG, 1024));   // (= gp: g >= gs)
-    const int64_t per_col = (int64_t)sizeof(double) * (4 * n3_ + 6 * h->dl_nseg + h->dl_nU + 2 * h->dl_Kp + 3 * g_);
+    const int64_t per_col = (int64_t)sizeof(double) * (4 * n3_ + 6 * h->plan.dl.dl_nseg + h->plan.dl.dl_nU + 2 * h->plan.dl.dl_Kp + 3 * g_);
     return (int)std::max<int64_t>(1, std::min<int64_t>(DIRECT_COLS_MAX, DIRECT_PANEL_BYTES / per_col) / 3);
   }
 
@@ -292,11 +280,11 @@ struct Session {
       panel.ld = (int)ldt;
       PGOC(buf.alloc(&AP, mcap * ld));
       PGOC(buf.alloc(&panel.T, n3 * ldt));
-      PGOC(buf.alloc(&panel.E, (int64_t)h->dl_nseg * 3 * ldt));
-      PGOC(buf.alloc(&panel.E2, (int64_t)h->dl_nseg * 3 * ldt));
-      PGOC(buf.alloc(&panel.Wm, (int64_t)std::max(1, h->dl_nU) * ldt));
-      PGOC(buf.alloc(&panel.G, (int64_t)h->dl_Kp * ldt));
-      PGOC(buf.alloc(&panel.Y, (int64_t)h->dl_Kp * ldt));
+      PGOC(buf.alloc(&panel.E, (int64_t)h->plan.dl.dl_nseg * 3 * ldt));
+      PGOC(buf.alloc(&panel.E2, (int64_t)h->plan.dl.dl_nseg * 3 * ldt));
+      PGOC(buf.alloc(&panel.Wm, (int64_t)std::max(1, h->plan.dl.dl_nU) * ldt));
+      PGOC(buf.alloc(&panel.G, (int64_t)h->plan.dl.dl_Kp * ldt));
+      PGOC(buf.alloc(&panel.Y, (int64_t)h->plan.dl.dl_Kp * ldt));
       PGOC(buf.alloc(&part_a, (int64_t)mcap * gp));
       PGOC(buf.alloc(&part_b, (int64_t)mcap * gp));
       PGOC(buf.alloc(&part_c, (int64_t)mcap * gp));

@@ -6,13 +6,13 @@
 // (the separators' columns and Schur complement with them), the capacitance matrix I + V Z with V t, its Cholesky
 // factor and explicit inverse.  L receives the argument blocks of the launches for what follows.
 int pgo_handle::direct_factor(const double* rhs, bool fine_prefix, DirectLaunch* L) {
-  const int n = S.n_loc, K = dl_K, Kp = dl_Kp, nb = dl_Kp / 32;
+  const int n = S.n_loc, K = plan.dl.dl_K, Kp = plan.dl.dl_Kp, nb = plan.dl.dl_Kp / 32;
   dev::DlrArgs& A = L->A;
   A.n = n;
-  A.m = dl_m;
+  A.m = plan.dl.dl_m;
   A.K = K;
   A.Kp = Kp;
-  A.ld = dl_ld;
+  A.ld = plan.dl.dl_ld;
   A.jr = jr;
   A.scale = scale;
   A.d2 = d2;
@@ -29,37 +29,37 @@ int pgo_handle::direct_factor(const double* rhs, bool fine_prefix, DirectLaunch*
   A.cap = dl_cap;
   A.dwork = dl_dwork;
   A.cvec = dl_cvec;
-  A.nsep = dl_nsep;
-  for (int j = 0; j < dev::DLR_MAX_SEP; ++j) A.sep[j] = dl_sep[j];
+  A.nsep = plan.dl.dl_nsep;
+  for (int j = 0; j < dev::DLR_MAX_SEP; ++j) A.sep[j] = plan.dl.dl_sep[j];
   A.ksep = dl_ksep;
   A.sw_js = has_sw ? sw_js : nullptr;
   A.sw_c = has_sw ? sw_c : nullptr;
   A.rec_n = rec_doubles;
   A.rec_info = info_mode ? 1 : 0;
-  hipLaunchKernelGGL(dev::k_dlr_setup<>, dim3((n + dl_m + 255) / 256), dim3(256), 0, stream, A);
+  hipLaunchKernelGGL(dev::k_dlr_setup<>, dim3((n + plan.dl.dl_m + 255) / 256), dim3(256), 0, stream, A);
   PGOC(check_launch("k_dlr_setup"));
-  hipLaunchKernelGGL(dev::k_dlr_factor<>, dim3(dl_nsep + 1), dim3(64), 0, stream, (const double*)dl_trec, n, dl_fac, A);
+  hipLaunchKernelGGL(dev::k_dlr_factor<>, dim3(plan.dl.dl_nsep + 1), dim3(64), 0, stream, (const double*)dl_trec, n, dl_fac, A);
   PGOC(check_launch("k_dlr_factor"));
-  hipLaunchKernelGGL(dev::k_dlr_prefix<>, dim3(1), dim3(128), 0, stream, (const double*)dl_fac, n, dl_nseg, dl_seglen, dl_pre);
+  hipLaunchKernelGGL(dev::k_dlr_prefix<>, dim3(1), dim3(128), 0, stream, (const double*)dl_fac, n, plan.dl.dl_nseg, plan.dl.dl_seglen, dl_pre);
   PGOC(check_launch("k_dlr_prefix"));
   if (fine_prefix) {   // the refinement's single column: k_dlr_solve1
-    hipLaunchKernelGGL(dev::k_dlr_prefix<>, dim3(1), dim3(512), 0, stream, (const double*)dl_fac, n, dl_nseg2, dl_seglen2, dl_pre2);
+    hipLaunchKernelGGL(dev::k_dlr_prefix<>, dim3(1), dim3(512), 0, stream, (const double*)dl_fac, n, plan.dl.dl_nseg2, plan.dl.dl_seglen2, dl_pre2);
     PGOC(check_launch("k_dlr_prefix (fine segments)"));
   }
   dev::DlrColsArgs& C = L->C;
   C.fac = dl_fac;
   C.pre = dl_pre;
   C.n = n;
-  C.ncols = K + 1 + dl_nU;
+  C.ncols = K + 1 + plan.dl.dl_nU;
   C.K = K;
   C.vec_col = K;
-  C.ld = dl_ld;
+  C.ld = plan.dl.dl_ld;
   C.ucol0 = K + 1;
-  C.nsep = dl_nsep;
-  for (int j = 0; j < dev::DLR_MAX_SEP; ++j) C.sep[j] = dl_sep[j];
+  C.nsep = plan.dl.dl_nsep;
+  for (int j = 0; j < dev::DLR_MAX_SEP; ++j) C.sep[j] = plan.dl.dl_sep[j];
   C.ksep = dl_ksep;
-  C.nseg = dl_nseg;
-  C.seglen = dl_seglen;
+  C.nseg = plan.dl.dl_nseg;
+  C.seglen = plan.dl.dl_seglen;
   C.vrec = dl_vrec;
   C.va = dl_va;
   C.vb = dl_vb;
@@ -71,24 +71,24 @@ int pgo_handle::direct_factor(const double* rhs, bool fine_prefix, DirectLaunch*
   PGOC(direct_sweep(C));
   // the couplings at the separators (k_dlr_sep_*): Y = the U columns of this solve, R once per factorisation
   dev::DlrSepArgs& SA = L->SA;
-  SA.nsep = dl_nsep;
-  SA.nU = dl_nU;
+  SA.nsep = plan.dl.dl_nsep;
+  SA.nU = plan.dl.dl_nU;
   SA.n = n;
-  for (int j = 0; j < dev::DLR_MAX_SEP; ++j) SA.sep[j] = dl_sep[j];
+  for (int j = 0; j < dev::DLR_MAX_SEP; ++j) SA.sep[j] = plan.dl.dl_sep[j];
   SA.ksep = dl_ksep;
   SA.Y = dl_Z + (K + 1);
-  SA.yld = dl_ld;
+  SA.yld = plan.dl.dl_ld;
   SA.Sinv = dl_R;
   SA.trec = dl_trec;
   SA.Wm = dl_Wm;
-  if (dl_nsep > 0) {
+  if (plan.dl.dl_nsep > 0) {
     SA.X = dl_Z;
-    SA.ld = dl_ld;
+    SA.ld = plan.dl.dl_ld;
     SA.ncols = K + 1;
     hipLaunchKernelGGL(dev::k_dlr_sep_system<>, dim3(1), dim3(256), 0, stream, SA);
     PGOC(check_launch("k_dlr_sep_system"));
   }
-  PGOC(direct_separator_fix(SA, dl_Z, dl_ld, K + 1));
+  PGOC(direct_separator_fix(SA, dl_Z, plan.dl.dl_ld, K + 1));
   hipLaunchKernelGGL(dev::k_dlr_cap<>, dim3((std::max(Kp, K + 1) + 255) / 256, Kp), dim3(256), 0, stream, A);
   PGOC(check_launch("k_dlr_cap"));
   for (int kb = 0; kb < nb; ++kb) {
@@ -110,7 +110,7 @@ int pgo_handle::direct_sweep(const dev::DlrColsArgs& Q, bool panel_rhs) {
 
 // the separators' correction of the columns X [3n][ld] (Y and R of the factorisation in SA)
 int pgo_handle::direct_separator_fix(const dev::DlrSepArgs& SA, double* X, int ld, int ncols) {
-  if (dl_nsep == 0) return PGO_OK;
+  if (plan.dl.dl_nsep == 0) return PGO_OK;
   dev::DlrSepArgs Q = SA;
   Q.X = X;
   Q.ld = ld;
@@ -123,7 +123,7 @@ int pgo_handle::direct_separator_fix(const dev::DlrSepArgs& SA, double* X, int l
 // T <- (T + V'V)^-1 T for the P.ld columns of a panel, after direct_factor():  X0 = T^-1 B (sweeps on the pre-filled
 // panel, separators),  G = V X0,  W = N'(N G),  X = X0 - Z W  (the three products on the matrix cores: k_dlr_gemm)
 int pgo_handle::direct_panel_solve(const DirectLaunch& L, const DirectPanel& P) {
-  const int n = S.n_loc, K = dl_K, Kp = dl_Kp;
+  const int n = S.n_loc, K = plan.dl.dl_K, Kp = plan.dl.dl_Kp;
   dev::DlrColsArgs C = L.C;
   C.ncols = P.ld;
   C.K = 0;
@@ -158,7 +158,7 @@ int pgo_handle::direct_panel_solve(const DirectLaunch& L, const DirectPanel& P) 
   Q.tri = 2;
   hipLaunchKernelGGL(dev::k_dlr_gemm<1>, gk, dim3(256), 0, stream, Q);
   Q.A = dl_Z;    // X = X0 - Z W
-  Q.lda = dl_ld;
+  Q.lda = plan.dl.dl_ld;
   Q.B = P.G;
   Q.C = P.T;
   Q.M = 3 * n;
@@ -173,7 +173,7 @@ int pgo_handle::direct_panel_solve(const DirectLaunch& L, const DirectPanel& P) 
 // matrix; leaves the true residual in r (the model-decrease identity of lm_iteration_tail reads it) and |r|^2, |rhs|^2 in
 // scal[8..9].  LM passes gs and dl_refine; pgo_debug_direct_solve any right-hand side and 0..3 steps.
 int pgo_handle::direct_enqueue(const double* rhs, int refine) {
-  const int n = S.n_loc, K = dl_K, Kp = dl_Kp, nb = dl_Kp / 32;
+  const int n = S.n_loc, K = plan.dl.dl_K, Kp = plan.dl.dl_Kp, nb = plan.dl.dl_Kp / 32;
   const bool one_launch = refine > 0 && dl_pre2 != nullptr;   // the refinement's single column: k_dlr_solve1
   DirectLaunch L;
   PGOC(direct_factor(rhs, one_launch, &L));
@@ -186,11 +186,11 @@ int pgo_handle::direct_enqueue(const double* rhs, int refine) {
     return check_launch("k_tri_apply");
   };
   PGOC(capacitance_solve());
-  hipLaunchKernelGGL(dev::k_dlr_combine<>, dim3((3 * n + 3) / 4), dim3(256), 0, stream, (const double*)dl_Z, dl_ld, K, (const double*)dl_cvec,
-                     (const double*)dl_Z, dl_ld, K, 3 * n, y, 0);
+  hipLaunchKernelGGL(dev::k_dlr_combine<>, dim3((3 * n + 3) / 4), dim3(256), 0, stream, (const double*)dl_Z, plan.dl.dl_ld, K, (const double*)dl_cvec,
+                     (const double*)dl_Z, plan.dl.dl_ld, K, 3 * n, y, 0);
   PGOC(check_launch("k_dlr_combine"));
   auto residual_product = [&]() -> int {  // ap = (H + D'D) y
-    hipLaunchKernelGGL(dev::k_scatter_owned<>, dim3(g_flat), dim3(dev::WG), 0, stream, S.n_loc, S.lo, y, p_full);
+    hipLaunchKernelGGL(dev::k_scatter_owned<>, dim3(plan.own.g_flat), dim3(dev::WG), 0, stream, S.n_loc, S.lo, y, p_full);
     PGOC(check_launch("k_scatter_owned"));
     return spmv_enqueue(p_full, ap, part[0], 1, nullptr);
   };
@@ -202,18 +202,18 @@ int pgo_handle::direct_enqueue(const double* rhs, int refine) {
       Q.fac = dl_fac;
       Q.pre2 = dl_pre2;
       Q.n = n;
-      Q.nseg = dl_nseg2;
-      Q.seglen = dl_seglen2;
+      Q.nseg = plan.dl.dl_nseg2;
+      Q.seglen = plan.dl.dl_seglen2;
       Q.rhs_b = rhs;
       Q.rhs_sub = ap;
       Q.x = dl_x1;
-      Q.nsep = dl_nsep;
-      Q.nU = dl_nU;
-      for (int j = 0; j < dev::DLR_MAX_SEP; ++j) Q.sep[j] = dl_sep[j];
+      Q.nsep = plan.dl.dl_nsep;
+      Q.nU = plan.dl.dl_nU;
+      for (int j = 0; j < dev::DLR_MAX_SEP; ++j) Q.sep[j] = plan.dl.dl_sep[j];
       Q.ksep = dl_ksep;
       Q.trec = dl_trec;
       Q.Y = dl_Z + (K + 1);
-      Q.yld = dl_ld;
+      Q.yld = plan.dl.dl_ld;
       Q.Sinv = dl_R;
       hipLaunchKernelGGL(dev::k_dlr_solve1<>, dim3(1), dim3(256), 0, stream, Q);
       PGOC(check_launch("k_dlr_solve1"));
@@ -233,25 +233,25 @@ int pgo_handle::direct_enqueue(const double* rhs, int refine) {
     hipLaunchKernelGGL(dev::k_dlr_vdot<>, dim3((Kp + 255) / 256), dim3(256), 0, stream, A, (const double*)dl_x1, xld, 0, dl_cvec);
     PGOC(check_launch("k_dlr_vdot"));
     PGOC(capacitance_solve());
-    hipLaunchKernelGGL(dev::k_dlr_combine<>, dim3((3 * n + 3) / 4), dim3(256), 0, stream, (const double*)dl_Z, dl_ld, K, (const double*)dl_cvec,
+    hipLaunchKernelGGL(dev::k_dlr_combine<>, dim3((3 * n + 3) / 4), dim3(256), 0, stream, (const double*)dl_Z, plan.dl.dl_ld, K, (const double*)dl_cvec,
                        (const double*)dl_x1, xld, 0, 3 * n, y, 1);
     PGOC(check_launch("k_dlr_combine"));
   }
   PGOC(residual_product());
   hipLaunchKernelGGL(dev::k_dlr_resid<>, dim3((3 * n + 255) / 256), dim3(256), 0, stream, (int64_t)3 * n, rhs, (const double*)ap, r);
   PGOC(check_launch("k_dlr_resid"));
-  hipLaunchKernelGGL(dev::k_dot<>, dim3(g_flat), dim3(dev::WG), 0, stream, (int64_t)3 * n, (const double*)r, (const double*)r, part[2]);
-  hipLaunchKernelGGL(dev::k_dot<>, dim3(g_flat), dim3(dev::WG), 0, stream, (int64_t)3 * n, rhs, rhs, part[4]);
+  hipLaunchKernelGGL(dev::k_dot<>, dim3(plan.own.g_flat), dim3(dev::WG), 0, stream, (int64_t)3 * n, (const double*)r, (const double*)r, part[2]);
+  hipLaunchKernelGGL(dev::k_dot<>, dim3(plan.own.g_flat), dim3(dev::WG), 0, stream, (int64_t)3 * n, rhs, rhs, part[4]);
   PGOC(check_launch("k_dot"));
-  return reduce_to_scal({{part[2], g_flat, 0}, {part[4], g_flat, 0}}, 8);
+  return reduce_to_scal({{part[2], plan.own.g_flat, 0}, {part[4], plan.own.g_flat, 0}}, 8);
 }
 
 // The ~130 launches of a direct solve are the same every time, but replaying them from a captured hipGraph was measured
 // to gain nothing in GN it/s (the solve is bound by its dependent kernels, not by the host), while capture + instantiation
 // cost ~5 ms, as much as five LM iterations of a fresh handle: they are launched eagerly.
 int pgo_handle::direct_solve() {
-  PGOC(direct_enqueue(gs, dl_refine));
-  if (dl_fail_at > 0 && iter == dl_fail_at)   // test hook ("direct_fail_at"): a direct solve that returns NaNs
+  PGOC(direct_enqueue(gs, plan.dl.dl_refine));
+  if (plan.dl.dl_fail_at > 0 && iter == plan.dl.dl_fail_at)   // test hook ("direct_fail_at"): a direct solve that returns NaNs
     HIPC(hipMemsetAsync(y, 0xFF, (size_t)3 * S.n_loc * sizeof(double), stream));
   return PGO_OK;
 }

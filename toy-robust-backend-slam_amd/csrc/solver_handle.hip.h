@@ -1,7 +1,7 @@
 #pragma once
 // The solver handle of the pose-graph backend: device buffers, launch helpers and the declarations of the pieces that
 // live in the translation units around it --
-//   solver_create.hip   pgo_handle::create: shard structure -> device, solver / preconditioner choices (direct_setup, coarse_setup)
+//   solver_create.hip   pgo_handle::create: shard structure -> the plan (plan.h: every choice made once) -> device (direct_build, coarse_build)
 //   solver_lm.hip       Ceres' TrustRegionMinimizer + LevenbergMarquardtStrategy policy (lm_begin, lm_iteration, ...)
 //   solver_pcg.hip      block-Jacobi PCG, its preconditioners' set-up, the coarse level
 //   solver_direct.hip   the direct chain + low-rank solve
@@ -48,6 +48,7 @@
 #include "direct.hip.h"
 #include "coarse.hip.h"
 #include "pgo_internal.h"
+#include "plan.h"
 #include "scratch.h"
 
 using pgo::fail;
@@ -67,10 +68,8 @@ namespace dev = pgo::dev;
 // The library reads two documented environment variables only -- PGO_FORCE_COLLECTIVES, PGO_GRAPH_COLLECTIVES (create()) --
 // and never lets the environment override a pgo_options field.
 
-// Test hooks (pgo_debug_set_knob, include/pgo.h): process-wide, read when a handle is created.  -1 = library default.
-// (table and setter: solver_abi.hip)
-long long knob(const char* name);
-int require_device(int device);   // a gfx950 device of that index is visible (solver_abi.hip)
+using pgo::knob;
+using pgo::require_device;
 
 // the refusals pgo_coarsen_plan / pgo_loop_support_plan share with the calls on a handle
 static inline int no_chain(const std::string& who, int32_t gap) {
@@ -92,22 +91,15 @@ struct PartRef {   // one array of per-workgroup partials for reduce_to_scal
 namespace {
 constexpr int N_SCAL = 16;
 constexpr int N_PART = 6;
-constexpr int DIRECT_MAX_POSES = 65536;   // largest graph the direct (chain + low-rank) solve takes
-constexpr int DIRECT_MAX_RANK = 6144;    // 3 x (edges outside the chain) + 1: order of the dense capacitance matrix
-// Cost model of the adaptive PCG / direct choice (solver_lm.hip): MEASURED ON MI355X -- a PCG iteration of the two-launch
-// loop on graphs of a few thousand poses, and the rank up to which auto takes the direct solve outright (INTEL + 50: 918 ->
-// 1.5 ms per LM iteration; FRH, 4515: 13 ms against 29 ms of PCG; M3500, 5862: 22 ms, the same as PCG).  Device-specific
-// constants, not options: they only decide speed, never results.
-constexpr double PCG_SECONDS_PER_ITER_SMALL = 14e-6;
-constexpr int DIRECT_PROBE_EVERY = 10;
-constexpr int DIRECT_AUTO_RANK = 2048;
-constexpr int COARSE_MAX_RANK = 6144;        // order of the dense coarse matrix (k_chol_panel's range)
-constexpr int COARSE_EXPLICIT_RANK = 1024;   // up to here the explicit inverse N'N is formed once per LM iteration
 }  // namespace
 
 struct pgo_handle {
   pgo_options opt;
   pgo::ShardStructure S;
+  // Every choice made once per handle (plan.h): written by create(), read-only afterwards.  What changes during a handle's life
+  // is the live state below, and the solver in force is derived from both where it is needed (direct(), takeover(), coarse_on()).
+  pgo::Plan plan;
+  const pgo::CoarsePlan& CO() const { return plan.co.on ? plan.co : plan.co_cov; }   // the coarse level that is (or can be) built
   pgo_comm* comm = nullptr;
   int device = 0;
   hipStream_t stream = nullptr;
@@ -131,19 +123,15 @@ struct pgo_handle {
   int32_t *inc_ptr = nullptr, *inc_edge = nullptr, *inc_col = nullptr, *tile_row = nullptr;
   uint8_t* inc_rowoff = nullptr;
   int4* tile_desc = nullptr;
-  bool spmv_one_tile = false;   // the plain-tile product kernel as k_spmv_1: one tile per workgroup, as many workgroups as tiles
-  bool spmv_pipe = false;   // software-pipelined K3 (k_spmv_p): when no tile is a chunked heavy row or has > 85 rows
-  int64_t inc_stride = 0;
   // normal equations
   double *hoff = nullptr, *hd = nullptr, *gs = nullptr, *d2 = nullptr, *minv = nullptr, *hdd = nullptr;
   // CG
   double *y = nullptr, *r = nullptr, *z = nullptr, *ap = nullptr, *p_full = nullptr;
   // second preconditioner level (coarse.hip.h): additive coarse correction on the rigid-body modes of pose aggregates
-  bool use_coarse = false;
-  int co_agg = 0, co_nagg = 0, co_K = 0, co_Kp = 0, co_ncb = 0;
+  int co_ncb = 0;
   double *co_pb = nullptr, *co_cap = nullptr, *co_nm = nullptr, *co_dwork = nullptr, *co_rc = nullptr, *co_cy = nullptr, *co_ec = nullptr;
   int32_t *co_cb_i = nullptr, *co_cb_j = nullptr, *co_cb_ptr = nullptr, *co_cb_q = nullptr, *co_cb_row = nullptr;
-  int coarse_setup(int32_t E, const int32_t* ia, const int32_t* ib);   // create: aggregates, coarse block lists, buffers
+  int coarse_build(int32_t E, const int32_t* ia, const int32_t* ib);   // the level the plan sized (CO()): block lists, buffers
   int coarse_factor();     // per LM iteration: basis, Galerkin matrix, Cholesky + inverse factor
   double* co_ainv = nullptr;   // explicit inverse N'N (coarse orders <= COARSE_EXPLICIT_RANK: one product per apply)
   int32_t* co_ok = nullptr;    // device flag: the factorisation of this LM iteration is usable
@@ -151,12 +139,13 @@ struct pgo_handle {
   int co_ndead = 0;
   bool co_flag_pending = false;   // pcg() left co_ok in scal[15] for the host fetch of lm_iteration_tail
   int co_off_iters = 0;        // LM iterations whose PCG solve found the level switched off (co_ok = 0)
-  bool co_cov_ready = false;   // the level was built for pgo_pose_covariance only (solver_covariance.hip): the LM loop runs without it
-  int co_ndot = 0;             // partials of r_c . e_c appended to the r.z partials
+  bool co_cov_ready = false;   // plan.co_cov was built, for pgo_pose_covariance only (solver_covariance.hip): the LM loop runs without it
+  bool co_for_call = false;    // ... and a covariance call is using it now (CoarseOn)
+  bool co_built() const { return plan.co.on || co_cov_ready; }
+  bool coarse_on() const { return plan.co.on || co_for_call; }
+  bool co_multi() const { return co_built() && CO().co_multi; }
   int coarse_solve(double* dot_part, const int32_t* done);   // e_c = (P'(H + D'D)P)^-1 P' r  (+ partials of r_c . e_c)
   // several ranks (coarse.hip.h, "several ranks"): replicated coarse problem, aggregates numbered globally
-  bool co_multi = false;
-  int co_aoff = 0, co_nown = 0;   // this rank's aggregates: [co_aoff, co_aoff + co_nown) (co_nagg counts all of them)
   int co_ncb_max = 0;             // blocks per rank in the gathered list (the largest rank's count)
   uint8_t* co_live = nullptr;     // [N] poses with an edge
   double* co_red = nullptr;       // [Kp + 2]: r_c (global), then the r.z / r.r sums -- one all-reduce
@@ -168,43 +157,30 @@ struct pgo_handle {
   int coarse_assemble_multi();
   int coarse_restrict_reduce(const double* rz_part, int n_rz, const double* rr_part, int n_rr, const int32_t* done);
   // single-reduction PCG loop (k_cg_sr_*: one all-reduce per iteration; several ranks, inexact mode, chain preconditioner)
-  bool use_sr = false;
-  bool verify_residual = false;   // test hook: pcg() reports the true residual of its solution
   double* sr_s = nullptr;   // s = A p, carried by recurrence
   dev::CgState* st = nullptr;
   dev::CgState* h_st = nullptr;  // pinned
   // reductions
   double* part[N_PART] = {nullptr};
   double* fold_buf = nullptr;   // 6 x 16: reduce_to_scal's intermediate for partial arrays too long for one workgroup
-  int part_cap = 0;
   double* scal = nullptr;
   double* h_scal = nullptr;  // pinned
   int* bad = nullptr;
   // block-Jacobi over groups of B poses (B > 1): explicit dense inverses
-  int grp_B = 1, grp_nb = 3, grp_pad = 32, n_groups = 0, g_grp = 1;
-  size_t grp_lds = 0;
-  int grp_prep_grid = 1;
   double* ginv = nullptr;
   // chain (block-tridiagonal) preconditioner over 64-pose segments (opt.pcg_chain_len): C planes, W planes, S^-1 planes
-  int chain_len = 0, g_chain = 1, chain_pad = 0;
-  int chain_chunk = 0, chain_steps = 0;  // lean apply: poses per lane (2 / 4) and recurrence steps
-  int chain_scan = 0;                    // > 0: the lean apply runs its recurrence as this many scan levels (few long segments)
-  int chain_nw = 4;                      // wavefronts per workgroup of the lean kernels: 1 on small graphs (a tile per CU)
   double *chain_c = nullptr, *chain_w = nullptr, *chain_s = nullptr;
   int32_t* chain_dup_rows = nullptr;   // rows whose block (i, i-1) sums several edges (k_chain_dupfix)
   int n_chain_dup = 0;
   // halo exchange of the search direction (world > 1, opt.halo_exchange)
-  bool use_halo = false;
   int32_t *halo_send_rows = nullptr, *halo_recv_rows = nullptr;
   double *halo_send_buf = nullptr, *halo_recv_buf = nullptr;
   std::vector<int64_t> halo_send_off3, halo_recv_off3;  // offsets in doubles (3 per row)
   // overlap of the halo exchange with the SpMV (opt.halo_overlap): the blocks with owned columns (MODE 4 of k_spmv) are
   // multiplied while the exchange runs on a second stream; the few blocks with remote columns follow (k_spmv_remote)
-  bool overlap = false;
   hipStream_t comm_stream = nullptr;
   hipEvent_t ev_pack = nullptr, ev_halo = nullptr;
   int32_t *rr_rows = nullptr, *rr_ptr = nullptr, *rr_slots = nullptr;
-  int n_rr = 0, g_spmv_loc = 0, g_rr = 0;
   // METHOD 2: switch variables (one per local edge; only robust edges use theirs), eliminated per edge
   bool has_sw = false;
   double *sw = nullptr, *sw_cand = nullptr, *sw_js = nullptr, *sw_sigma = nullptr, *sw_c = nullptr, *sw_gamma = nullptr,
@@ -234,7 +210,6 @@ struct pgo_handle {
   int64_t n_enqueued = 0;
   // small graphs on one rank: the direction update rides in the next SpMV (k_spmv MODE 5) -- two launches per PCG
   // iteration instead of three; p_full / p_full2 alternate by iteration parity
-  bool fused_p = false;
   double* p_full2 = nullptr;
   // batched handle (pgo_batch_*): the block-diagonal union of independent problems, each starting at a multiple of 256 rows
   bool batch_mode = false;
@@ -245,30 +220,25 @@ struct pgo_handle {
   double* prob_radius = nullptr;        // trust-region radius per problem
   double* edge_cost = nullptr;          // cost per local edge (k_edge_eval -> k_prob_reduce)
   // batched handles: the whole PCG solve of an LM iteration as ONE launch, one workgroup per problem (solo.hip.h, solver_batch.hip)
-  int solo_steps = 0, solo_scan = 0;
-  // grids
-  int g_edge = 1, g_rows = 1, g_vec = 1, g_flat = 1, g_spmv = 1, g_asm = 1;
   // direct solve for small chain-like graphs (direct.hip.h): T (odometry chain) + V'V (the other edges) by Woodbury
-  bool direct = false;
-  int dl_m = 0, dl_K = 0, dl_Kp = 0, dl_ld = 0, dl_refine = 1;
+  // The plan says how a handle starts (plan.dl.direct) and whether the direct solve may take over (plan.dl.dl_possible); which solver
+  // is in force now follows from that and the live state: the adaptive rule's side, a failed take-over, a cut chain.
+  bool on_direct = false;    // the adaptive PCG / direct rule (lm_iteration) is on the direct solve
+  bool dl_gave_up = false;   // the take-over's set-up failed once: PCG for good
+  bool takeover() const { return plan.dl.dl_possible && !dl_gave_up && !act_chain_cut; }
+  bool direct() const { return !act_chain_cut && (plan.dl.direct || (takeover() && on_direct)); }
   int32_t *dl_chain_edge = nullptr, *dl_lr_edge = nullptr, *dl_va = nullptr, *dl_vb = nullptr;
   double *dl_trec = nullptr, *dl_fac = nullptr, *dl_pre = nullptr, *dl_vrec = nullptr, *dl_Z = nullptr, *dl_cap = nullptr, *dl_dwork = nullptr,
          *dl_nm = nullptr, *dl_cy = nullptr, *dl_cvec = nullptr, *dl_x1 = nullptr, *dl_E = nullptr, *dl_E2 = nullptr;
-  int dl_nseg = 1, dl_seglen = 1;
-  int dl_nseg2 = 1, dl_seglen2 = 1;   // the finer segmentation of k_dlr_solve1 (up to 256 segments of <= 16 poses)
-  double* dl_pre2 = nullptr;
-  int dl_nsep = 0, dl_sep[dev::DLR_MAX_SEP] = {0}, dl_nU = 0;
+  double* dl_pre2 = nullptr;   // the finer segmentation of k_dlr_solve1 (up to 256 segments of <= 16 poses)
   double *dl_ksep = nullptr, *dl_R = nullptr, *dl_Wm = nullptr;
   double dl_rel = 0.0;  // |g - (H + D'D) y| / |g| of the latest direct solve
   bool dl_retry = false;   // the current LM iteration is being redone by PCG after a failed direct solve
   int dl_fallbacks = 0;    // how often that happened
-  int dl_fail_at = 0;      // test hook (pgo_debug_set_knob "direct_fail_at"): poison the direct solve of this LM iteration
-  bool dl_possible = false;     // auto, rank above DIRECT_AUTO_RANK: the direct solve can take over from PCG (lm_iteration)
-  double dl_est_seconds = 0.0;  // what a direct solve of this rank costs (model fitted to INTEL / FRH / M3500)
   int dl_switched_at = 0;       // LM iteration after which it first did
   int dl_last_probe = 0, dl_dear_run = 0;
   bool dl_ready = false;        // the direct solve's buffers exist
-  void clear_direct_buffers() {   // after a failed direct_setup(): every pointer it may have set (the memory is freed by the caller)
+  void clear_direct_buffers() {   // after a failed direct_build(): every pointer it may have set (the memory is freed by the caller)
     dl_chain_edge = dl_lr_edge = dl_va = dl_vb = nullptr;
     dl_trec = dl_fac = dl_pre = dl_vrec = dl_Z = dl_cap = dl_dwork = dl_nm = dl_cy = dl_cvec = dl_x1 = dl_E = dl_E2 = nullptr;
     dl_pre2 = dl_ksep = dl_R = dl_Wm = nullptr;
@@ -431,7 +401,6 @@ struct pgo_handle {
   uint8_t* act_mask = nullptr;        // solo handles: device copy, allocated at the first pgo_set_active and kept
   int32_t n_active_edges = 0, n_constant_poses = 0;   // resolved (pgo_handle_info)
   bool act_chain_cut = false;         // an edge of the direct solve's chain is inactive: PCG until it is active again
-  bool act_saved_direct = false, act_saved_possible = false;
   int co_dead_cap = 0;                // entries co_dead can hold
   bool has_anchor() const { return fixed_internal >= 0 || act_anchor; }
   void coarse_dead_list(std::vector<int32_t>* dead) const;
@@ -493,7 +462,7 @@ struct pgo_handle {
     A.n_tiles = S.n_tiles();
     A.n_loc = S.n_loc;
     A.lo = S.lo;
-    A.inc_stride = inc_stride;
+    A.inc_stride = plan.own.inc_stride;
     A.hoff = hoff;
     A.hd = hd;
     A.gs = gs;
@@ -502,8 +471,8 @@ struct pgo_handle {
     A.sw_gamma = sw_gamma;
     A.diag_full = diag_full;
     A.gs_full = gs_full;
-    A.chain_rec = chain_len ? chain_c : nullptr;
-    A.chain_seg = chain_len ? chain_len : 1;
+    A.chain_rec = plan.all.chain_len ? chain_c : nullptr;
+    A.chain_seg = plan.all.chain_len ? plan.all.chain_len : 1;
     return A;
   }
   int assemble_enqueue();
@@ -520,7 +489,7 @@ struct pgo_handle {
     A.lo = S.lo;
     A.with_d2 = with_d2;
     A.nt = 1;   // non-temporal H-stream loads in k_spmv: 179 -> 166 us at 1M poses
-    A.inc_stride = inc_stride;
+    A.inc_stride = plan.own.inc_stride;
     A.hoff = hoff;
     A.hd = hd;
     A.d2 = d2;
@@ -563,7 +532,7 @@ struct pgo_handle {
     CP.cw = chain_w;
     CP.cs = chain_s;
     CP.n_loc = S.n_loc;
-    CP.n_pad = chain_pad;
+    CP.n_pad = plan.own.chain_pad;
     return CP;
   }
   // PCG start-up / first update kernel with the chain preconditioner
@@ -643,7 +612,8 @@ struct pgo_handle {
   int lm_iteration_tail(bool* stop, pgo_iter_record& R, double it0, double t0, int k_it, double rel);
   int prepare_system();
   int pcg(int* iters, double* rel);
-  int direct_setup(int32_t N, bool switch_now = false);
+  int32_t direct_chain_lists(std::vector<int32_t>* chain, std::vector<int32_t>* lr, std::vector<int32_t>* va, std::vector<int32_t>* vb) const;
+  int direct_build();   // the buffers and lists of the direct solve the plan sized (create, or lm_iteration's take-over)
   int direct_solve();
   int direct_enqueue(const double* rhs, int refine);
   struct DirectLaunch {   // the argument blocks of a factorisation's launches, for the solves that follow it

@@ -29,10 +29,10 @@ int pgo_handle::refresh_switch_system() {
                      opt.min_lm_diagonal, opt.max_lm_diagonal, part[2], part[3]);
   PGOC(check_launch("k_switch_prepare"));
   PGOC(assemble_enqueue());
-  hipLaunchKernelGGL(dev::k_grad_max<>, dim3(g_flat), dim3(dev::WG), 0, stream, (const double*)gs_full, (const double*)scale, S.n_loc,
+  hipLaunchKernelGGL(dev::k_grad_max<>, dim3(plan.own.g_flat), dim3(dev::WG), 0, stream, (const double*)gs_full, (const double*)scale, S.n_loc,
                      S.lo, part[0]);
   PGOC(check_launch("k_grad_max"));
-  PGOC(reduce_to_scal({{part[0], g_flat, 1}, {part[2], g_sw, 1}}, 10, true));
+  PGOC(reduce_to_scal({{part[0], plan.own.g_flat, 1}, {part[2], g_sw, 1}}, 10, true));
   PGOC(reduce_to_scal({{part[3], g_sw, 0}}, 12));
   PGOC(fetch_scal(10, 3));
   gmax = std::max(h_scal[10], h_scal[11]);
@@ -52,8 +52,8 @@ int pgo_handle::lm_begin() {
   termination = 0;
   tr = pgo::tr_begin(opt.radius0);
   last_pcg_iters = 0;
-  if (dl_possible) {   // every solve of the handle takes the same solver decisions (lm_iteration)
-    direct = false;
+  if (takeover()) {   // every solve of the handle takes the same solver decisions (lm_iteration)
+    on_direct = false;
     dl_last_probe = dl_dear_run = 0;
   }
   t_eval = t_asm = t_lin = t_cand = 0;
@@ -70,7 +70,7 @@ int pgo_handle::lm_begin() {
     PGOC(sync());  // `ones` dies with this scope
   }
   // pass 1: unit scales (0 on the constant pose) -> column norms for Jacobi scaling
-  hipLaunchKernelGGL(dev::k_jacobi_scale<>, dim3(g_rows), dim3(dev::WG), 0, stream, hd, S.n_loc, S.lo, fixed, 0, scale, (const uint8_t*)fixed_mask);
+  hipLaunchKernelGGL(dev::k_jacobi_scale<>, dim3(plan.own.g_rows), dim3(dev::WG), 0, stream, hd, S.n_loc, S.lo, fixed, 0, scale, (const uint8_t*)fixed_mask);
   PGOC(check_launch("k_jacobi_scale"));
   PGOC(allgather(scale));
   PGOC(linearize(false));
@@ -81,18 +81,18 @@ int pgo_handle::lm_begin() {
     PGOC(check_launch("k_switch_scale"));
   }
   if (opt.jacobi_scaling) {
-    hipLaunchKernelGGL(dev::k_jacobi_scale<>, dim3(g_rows), dim3(dev::WG), 0, stream, hd, S.n_loc, S.lo, fixed, 1, scale, (const uint8_t*)fixed_mask);
+    hipLaunchKernelGGL(dev::k_jacobi_scale<>, dim3(plan.own.g_rows), dim3(dev::WG), 0, stream, hd, S.n_loc, S.lo, fixed, 1, scale, (const uint8_t*)fixed_mask);
     PGOC(check_launch("k_jacobi_scale"));
     PGOC(allgather(scale));
     PGOC(linearize(true));  // the records do not depend on the scales: re-assemble only
   }
   cost = initial_cost = cost0;
-  hipLaunchKernelGGL(dev::k_grad_max<>, dim3(g_flat), dim3(dev::WG), 0, stream, gs, scale, S.n_loc, S.lo, part[0]);
+  hipLaunchKernelGGL(dev::k_grad_max<>, dim3(plan.own.g_flat), dim3(dev::WG), 0, stream, gs, scale, S.n_loc, S.lo, part[0]);
   PGOC(check_launch("k_grad_max"));
-  PGOC(reduce_to_scal({{part[0], g_flat, 1}}, 2, true));
-  hipLaunchKernelGGL(dev::k_xnorm<>, dim3(g_flat), dim3(dev::WG), 0, stream, S.n_loc, S.lo, poses, scale, part[1]);
+  PGOC(reduce_to_scal({{part[0], plan.own.g_flat, 1}}, 2, true));
+  hipLaunchKernelGGL(dev::k_xnorm<>, dim3(plan.own.g_flat), dim3(dev::WG), 0, stream, S.n_loc, S.lo, poses, scale, part[1]);
   PGOC(check_launch("k_xnorm"));
-  PGOC(reduce_to_scal({{part[1], g_flat, 0}}, 3));
+  PGOC(reduce_to_scal({{part[1], plan.own.g_flat, 0}}, 3));
   PGOC(fetch_scal(2, 2));
   gmax = h_scal[2];
   xnorm2_pose = h_scal[3];
@@ -143,24 +143,24 @@ int pgo_handle::lm_iteration(bool* stop) {
   // throughout), so the handle decides from what it sees -- from iteration COUNTS, not clocks: reproducible --
   //   on PCG:    two consecutive solves dearer than a direct solve of this rank  -> the direct solve takes over;
   //   on direct: every DIRECT_PROBE_EVERY-th LM iteration is solved by PCG; if that was cheaper, PCG takes over again.
-  const bool probe = direct && dl_possible && iter - dl_last_probe >= DIRECT_PROBE_EVERY;
-  const bool run_direct = direct && !probe;
+  const bool probe = direct() && takeover() && iter - dl_last_probe >= pgo::DIRECT_PROBE_EVERY;
+  const bool run_direct = direct() && !probe;
   if (run_direct) {
     PGOC(direct_solve());
   } else {
-    if (direct) PGOC(prepare_preconditioner());
+    if (direct()) PGOC(prepare_preconditioner());
     PGOC(pcg(&k_it, &rel));
   }
   if (probe) dl_retry = true;   // (this iteration's step is PCG's: no direct-solve residual, no fallback)
   const int st_tail = lm_iteration_tail(stop, R, it0, t0, k_it, rel);
   if (probe) dl_retry = false;
-  if (st_tail == PGO_OK && dl_possible && !run_direct && !*stop) {
+  if (st_tail == PGO_OK && takeover() && !run_direct && !*stop) {
     // a PCG iteration: 14 us on graphs of a few thousand poses (two launches), 39 us at 100k poses
-    const bool dear = (double)k_it * (PCG_SECONDS_PER_ITER_SMALL + 0.25e-9 * S.n_poses) > dl_est_seconds;
+    const bool dear = (double)k_it * (pgo::PCG_SECONDS_PER_ITER_SMALL + 0.25e-9 * S.n_poses) > plan.dl.dl_est_seconds;
     if (probe) {
       dl_last_probe = iter;
       if (!dear) {
-        direct = false;
+        on_direct = false;
         dl_dear_run = 0;
         if (opt.verbose) printf("pgo: %d PCG iterations in LM iteration %d: back to PCG\n", k_it, iter);
       }
@@ -174,25 +174,24 @@ int pgo_handle::lm_iteration(bool* stop) {
         if (!dl_ready) {
           const size_t mark = allocs.size();
           const int64_t bytes_mark = device_bytes;
-          if (direct_setup(S.n_poses, true) != PGO_OK || !dl_ready) {
+          if (direct_build() != PGO_OK || !dl_ready) {
             (void)hipStreamSynchronize(stream);   // uploads into the buffers about to be freed
             (void)hipGetLastError();
             for (size_t k = mark; k < allocs.size(); ++k) (void)hipFree(allocs[k]);
             allocs.resize(mark);
             device_bytes = bytes_mark;
             clear_direct_buffers();
-            dl_possible = false;
-            direct = false;
+            dl_gave_up = true;
             ok = false;
             (void)fail(PGO_OK, "");
             if (opt.verbose) printf("pgo: the direct solver could not be set up (LM iteration %d): staying on PCG\n", iter);
           }
         }
         if (ok) {
-          direct = true;
+          on_direct = true;
           dl_last_probe = iter;
           if (dl_switched_at == 0) dl_switched_at = iter;
-          if (opt.verbose) printf("pgo: %d PCG iterations in LM iteration %d: the direct solve takes over (rank %d)\n", k_it, iter, dl_K);
+          if (opt.verbose) printf("pgo: %d PCG iterations in LM iteration %d: the direct solve takes over (rank %d)\n", k_it, iter, plan.dl.dl_K);
         }
       }
     }
@@ -212,7 +211,7 @@ int pgo_handle::lm_iteration_tail(bool* stop, pgo_iter_record& R, double it0, do
   // (rtol 0.1, ~100 iterations) keeps the recurrence residual; the direct solve writes the true residual itself.
   const bool true_residual = k_it > 0 && (opt.pcg_rtol < 1e-6 || k_it > 1000);
   if (has_sw || true_residual) {  // (the switch back-substitution below reads y of both endpoints from the gather vector)
-    hipLaunchKernelGGL(dev::k_scatter_owned<>, dim3(g_flat), dim3(dev::WG), 0, stream, S.n_loc, S.lo, y, p_full);
+    hipLaunchKernelGGL(dev::k_scatter_owned<>, dim3(plan.own.g_flat), dim3(dev::WG), 0, stream, S.n_loc, S.lo, y, p_full);
     PGOC(check_launch("k_scatter_owned"));
     PGOC(share_gather_vector(p_full));
   }
@@ -223,12 +222,12 @@ int pgo_handle::lm_iteration_tail(bool* stop, pgo_iter_record& R, double it0, do
     PGOC(check_launch("k_dlr_resid"));
   }
   // y.(H y) = y.b - y.r - y.(D y) from the residual (no further product by H): part[1] = y.b, part[0] = y.r, part[5] = y.(D y)
-  hipLaunchKernelGGL(dev::k_model_terms<>, dim3(g_flat), dim3(dev::WG), 0, stream, (int64_t)3 * S.n_loc, (const double*)y, (const double*)gs,
+  hipLaunchKernelGGL(dev::k_model_terms<>, dim3(plan.own.g_flat), dim3(dev::WG), 0, stream, (int64_t)3 * S.n_loc, (const double*)y, (const double*)gs,
                      (const double*)r, (const double*)d2, part[1], part[0], part[5]);
   PGOC(check_launch("k_model_terms"));
   // candidate x + d and |d|^2
   double* x_old = poses;
-  hipLaunchKernelGGL(dev::k_candidate<>, dim3(g_flat), dim3(dev::WG), 0, stream, S.n_loc, S.lo, x_old, scale, y, cand, part[3]);
+  hipLaunchKernelGGL(dev::k_candidate<>, dim3(plan.own.g_flat), dim3(dev::WG), 0, stream, S.n_loc, S.lo, x_old, scale, y, cand, part[3]);
   PGOC(check_launch("k_candidate"));
   double model_sw = 0.0, step2_sw = 0.0;
   if (has_sw) {  // back-substitute the switches (needs y of both endpoints: in the gather vector after the share above)
@@ -238,7 +237,7 @@ int pgo_handle::lm_iteration_tail(bool* stop, pgo_iter_record& R, double it0, do
     PGOC(check_launch("k_switch_backsub"));
     PGOC(reduce_to_scal({{part[2], g_sw, 0}, {part[4], g_sw, 0}}, 13));
   }
-  PGOC(reduce_to_scal({{part[1], g_flat, 0}, {part[0], g_flat, 0}, {part[3], g_flat, 0}, {part[5], g_flat, 0}}, 0));
+  PGOC(reduce_to_scal({{part[1], plan.own.g_flat, 0}, {part[0], plan.own.g_flat, 0}, {part[3], plan.own.g_flat, 0}, {part[5], plan.own.g_flat, 0}}, 0));
   // the candidate's cost is evaluated in the same breath (scal[6..7]; wasted only when the step turns out invalid): one
   // host synchronisation for the model terms AND the candidate instead of two
   PGOC(allgather(cand));
@@ -249,7 +248,7 @@ int pgo_handle::lm_iteration_tail(bool* stop, pgo_iter_record& R, double it0, do
     if (h_scal[15] == 0.0) ++co_off_iters;
     co_flag_pending = false;
   }
-  if (direct && !dl_retry) R.pcg_rel_residual = dl_rel = (h_scal[9] > 0.0) ? std::sqrt(h_scal[8] / h_scal[9]) : 0.0;
+  if (direct() && !dl_retry) R.pcg_rel_residual = dl_rel = (h_scal[9] > 0.0) ? std::sqrt(h_scal[8] / h_scal[9]) : 0.0;
   if (has_sw) {
     model_sw = h_scal[13];
     step2_sw = h_scal[14];
@@ -258,7 +257,7 @@ int pgo_handle::lm_iteration_tail(bool* stop, pgo_iter_record& R, double it0, do
   const double ydotg = h_scal[0], yHy = h_scal[1], step2 = h_scal[2] + step2_sw;
   const double model = ydotg - 0.5 * yHy + model_sw;
   if (!pgo::tr_step_usable(model, step2)) {  // invalid step
-    if (direct && !dl_retry) {
+    if (direct() && !dl_retry) {
       // the direct solve produced no usable step (a capacitance matrix that lost positive definiteness to rounding, a
       // residual the refinement could not repair): this LM iteration is redone by PCG before Ceres' invalid-step rule applies
       dl_retry = true;
@@ -310,9 +309,9 @@ int pgo_handle::lm_iteration_tail(bool* stop, pgo_iter_record& R, double it0, do
   if (rho > opt.min_relative_decrease) {  // HandleSuccessfulStep
     std::swap(poses, cand);
     if (has_sw) std::swap(sw, sw_cand);
-    hipLaunchKernelGGL(dev::k_xnorm<>, dim3(g_flat), dim3(dev::WG), 0, stream, S.n_loc, S.lo, poses, scale, part[1]);
+    hipLaunchKernelGGL(dev::k_xnorm<>, dim3(plan.own.g_flat), dim3(dev::WG), 0, stream, S.n_loc, S.lo, poses, scale, part[1]);
     PGOC(check_launch("k_xnorm"));
-    PGOC(reduce_to_scal({{part[1], g_flat, 0}}, 3));
+    PGOC(reduce_to_scal({{part[1], plan.own.g_flat, 0}}, 3));
     // pgo::tr_accept is applied only once the accepted point has been re-linearised: a failure there records the old radius
     // (k_window_solve and pgo_batch update the radius first)
     if (has_sw) {
@@ -334,9 +333,9 @@ int pgo_handle::lm_iteration_tail(bool* stop, pgo_iter_record& R, double it0, do
       const double tl0 = wall_s();
       PGOC(eval_enqueue(poses, sw, 1, true, 0));
       PGOC(assemble_enqueue());
-      hipLaunchKernelGGL(dev::k_grad_max<>, dim3(g_flat), dim3(dev::WG), 0, stream, gs, scale, S.n_loc, S.lo, part[0]);
+      hipLaunchKernelGGL(dev::k_grad_max<>, dim3(plan.own.g_flat), dim3(dev::WG), 0, stream, gs, scale, S.n_loc, S.lo, part[0]);
       PGOC(check_launch("k_grad_max"));
-      PGOC(reduce_to_scal({{part[0], g_flat, 1}}, 2, true));
+      PGOC(reduce_to_scal({{part[0], plan.own.g_flat, 1}}, 2, true));
       PGOC(fetch_scal(0, 4));
       t_eval += wall_s() - tl0;  // (K2 and the norms included: no host synchronisation separates them any more)
       if (h_scal[1] > 0.0 || !std::isfinite(h_scal[0])) {

@@ -6,10 +6,10 @@
 int pgo_handle::coarse_factor() {
   dev::CoarseArgs A;
   A.n_loc = S.n_loc;
-  A.agg = co_agg;
-  A.n_agg = co_nagg;
-  A.K = co_K;
-  A.Kp = co_Kp;
+  A.agg = CO().co_agg;
+  A.n_agg = CO().co_nagg;
+  A.K = CO().co_K;
+  A.Kp = CO().co_Kp;
   A.poses = poses;
   A.scale = scale;
   A.pb = co_pb;
@@ -25,41 +25,41 @@ int pgo_handle::coarse_factor() {
   A.n_cb = co_ncb;
   A.cap = co_cap;
   A.dwork = co_dwork;
-  if (co_multi) PGOC(coarse_assemble_multi());
+  if (co_multi()) PGOC(coarse_assemble_multi());
   else {
-    hipLaunchKernelGGL(dev::k_coarse_basis<>, dim3((co_nagg + 3) / 4), dim3(256), 0, stream, A);
+    hipLaunchKernelGGL(dev::k_coarse_basis<>, dim3((CO().co_nagg + 3) / 4), dim3(256), 0, stream, A);
     PGOC(check_launch("k_coarse_basis"));
-    HIPC(hipMemsetAsync(co_cap, 0, (size_t)co_Kp * co_Kp * sizeof(double), stream));
-    HIPC(hipMemsetAsync(co_dwork, 0, (size_t)(co_Kp / 32) * 1024 * sizeof(double), stream));
+    HIPC(hipMemsetAsync(co_cap, 0, (size_t)CO().co_Kp * CO().co_Kp * sizeof(double), stream));
+    HIPC(hipMemsetAsync(co_dwork, 0, (size_t)(CO().co_Kp / 32) * 1024 * sizeof(double), stream));
     hipLaunchKernelGGL(dev::k_coarse_assemble<>, dim3((co_ncb + 3) / 4), dim3(256), 0, stream, A);
     PGOC(check_launch("k_coarse_assemble"));
   }
-  if (co_Kp > co_K) {
-    hipLaunchKernelGGL(dev::k_coarse_pad<>, dim3(1), dim3(32), 0, stream, co_cap, co_dwork, co_K, co_Kp);
+  if (CO().co_Kp > CO().co_K) {
+    hipLaunchKernelGGL(dev::k_coarse_pad<>, dim3(1), dim3(32), 0, stream, co_cap, co_dwork, CO().co_K, CO().co_Kp);
     PGOC(check_launch("k_coarse_pad"));
   }
   if (co_ndead > 0) {
     hipLaunchKernelGGL(dev::k_coarse_dead<>, dim3((3 * co_ndead + 255) / 256), dim3(256), 0, stream, co_cap, co_dwork, (const int32_t*)co_dead,
-                       co_ndead, co_Kp);
+                       co_ndead, CO().co_Kp);
     PGOC(check_launch("k_coarse_dead"));
   }
-  const int nb = co_Kp / 32;
+  const int nb = CO().co_Kp / 32;
   for (int kb = 0; kb < nb; ++kb) {
-    hipLaunchKernelGGL(dev::k_chol_panel<>, dim3(std::max(1, nb - 1)), dim3(dev::CHOL_THREADS), dev::CHOL_LDS_BYTES, stream, co_cap, co_nm, co_dwork, co_Kp, nb, kb);
+    hipLaunchKernelGGL(dev::k_chol_panel<>, dim3(std::max(1, nb - 1)), dim3(dev::CHOL_THREADS), dev::CHOL_LDS_BYTES, stream, co_cap, co_nm, co_dwork, CO().co_Kp, nb, kb);
     PGOC(check_launch("k_chol_panel (coarse level)"));
   }
   // usable?  a probe through the factor: x = A_c^-1 1 must be finite (a pivot lost to rounding leaves NaNs behind it)
-  hipLaunchKernelGGL(dev::k_fill<>, dim3((co_Kp + 255) / 256), dim3(256), 0, stream, co_rc, (int64_t)co_Kp, 1.0);
+  hipLaunchKernelGGL(dev::k_fill<>, dim3((CO().co_Kp + 255) / 256), dim3(256), 0, stream, co_rc, (int64_t)CO().co_Kp, 1.0);
   if (co_ainv) {
-    hipLaunchKernelGGL(dev::k_coarse_ainv<>, dim3((co_Kp + 255) / 256, co_Kp), dim3(256), 0, stream, (const double*)co_nm, co_Kp, co_ainv);
-    hipLaunchKernelGGL(dev::k_tri_apply<>, dim3(nb), dim3(256), 0, stream, (const double*)co_ainv, co_Kp, nb, (const double*)co_rc, co_ec, 0);
+    hipLaunchKernelGGL(dev::k_coarse_ainv<>, dim3((CO().co_Kp + 255) / 256, CO().co_Kp), dim3(256), 0, stream, (const double*)co_nm, CO().co_Kp, co_ainv);
+    hipLaunchKernelGGL(dev::k_tri_apply<>, dim3(nb), dim3(256), 0, stream, (const double*)co_ainv, CO().co_Kp, nb, (const double*)co_rc, co_ec, 0);
   } else {
-    hipLaunchKernelGGL(dev::k_tri_apply<>, dim3(nb), dim3(256), 0, stream, (const double*)co_nm, co_Kp, nb, (const double*)co_rc, co_cy, 0);
-    hipLaunchKernelGGL(dev::k_tri_apply<>, dim3(nb), dim3(256), 0, stream, (const double*)co_nm, co_Kp, nb, (const double*)co_cy, co_ec, 1);
+    hipLaunchKernelGGL(dev::k_tri_apply<>, dim3(nb), dim3(256), 0, stream, (const double*)co_nm, CO().co_Kp, nb, (const double*)co_rc, co_cy, 0);
+    hipLaunchKernelGGL(dev::k_tri_apply<>, dim3(nb), dim3(256), 0, stream, (const double*)co_nm, CO().co_Kp, nb, (const double*)co_cy, co_ec, 1);
   }
-  hipLaunchKernelGGL(dev::k_coarse_check<>, dim3(1), dim3(256), 0, stream, (const double*)co_ec, co_Kp, co_ok);
+  hipLaunchKernelGGL(dev::k_coarse_check<>, dim3(1), dim3(256), 0, stream, (const double*)co_ec, CO().co_Kp, co_ok);
   // (the restriction writes the K coarse unknowns only: the padding entries K .. Kp-1 of r_c must read 0 again)
-  hipLaunchKernelGGL(dev::k_fill<>, dim3((co_Kp + 255) / 256), dim3(256), 0, stream, co_rc, (int64_t)co_Kp, 0.0);
+  hipLaunchKernelGGL(dev::k_fill<>, dim3((CO().co_Kp + 255) / 256), dim3(256), 0, stream, co_rc, (int64_t)CO().co_Kp, 0.0);
   return check_launch("coarse level probe");
 }
 
@@ -70,8 +70,8 @@ int pgo_handle::coarse_assemble_multi() {
   M.n = S.n_poses;
   M.lo = S.lo;
   M.n_loc = S.n_loc;
-  M.agg = co_agg;
-  M.n_agg = co_nagg;
+  M.agg = CO().co_agg;
+  M.n_agg = CO().co_nagg;
   M.poses = poses;
   M.scale = scale;
   M.live = co_live;
@@ -87,10 +87,10 @@ int pgo_handle::coarse_assemble_multi() {
   M.cb_row = co_cb_row;
   M.n_cb = co_ncb;
   M.vals = co_gvals + (int64_t)comm->rank * co_ncb_max * 9;
-  hipLaunchKernelGGL(dev::k_coarse_basis_m<>, dim3((co_nagg + 3) / 4), dim3(256), 0, stream, M);
+  hipLaunchKernelGGL(dev::k_coarse_basis_m<>, dim3((CO().co_nagg + 3) / 4), dim3(256), 0, stream, M);
   PGOC(check_launch("k_coarse_basis_m"));
-  HIPC(hipMemsetAsync(co_cap, 0, (size_t)co_Kp * co_Kp * sizeof(double), stream));
-  HIPC(hipMemsetAsync(co_dwork, 0, (size_t)(co_Kp / 32) * 1024 * sizeof(double), stream));
+  HIPC(hipMemsetAsync(co_cap, 0, (size_t)CO().co_Kp * CO().co_Kp * sizeof(double), stream));
+  HIPC(hipMemsetAsync(co_dwork, 0, (size_t)(CO().co_Kp / 32) * 1024 * sizeof(double), stream));
   if (co_ncb > 0) {
     hipLaunchKernelGGL(dev::k_coarse_assemble_m<>, dim3((co_ncb + 3) / 4), dim3(256), 0, stream, M);
     PGOC(check_launch("k_coarse_assemble_m"));
@@ -100,7 +100,7 @@ int pgo_handle::coarse_assemble_multi() {
   const int64_t nblk = (int64_t)comm->world * co_ncb_max;
   if (nblk > 0) {
     hipLaunchKernelGGL(dev::k_coarse_scatter<>, dim3((unsigned)((9 * nblk + 255) / 256)), dim3(256), 0, stream, (const double*)co_gvals,
-                       (const int32_t*)co_gi, (const int32_t*)co_gj, nblk, co_cap, co_dwork, co_Kp);
+                       (const int32_t*)co_gi, (const int32_t*)co_gj, nblk, co_cap, co_dwork, CO().co_Kp);
     PGOC(check_launch("k_coarse_scatter"));
   }
   return PGO_OK;
@@ -109,25 +109,25 @@ int pgo_handle::coarse_assemble_multi() {
 // several ranks: r_c = P'r of the own aggregates into the zeroed global vector, and the partial sums of r.z and r.r next to it,
 // all in ONE all-reduce -- afterwards every rank holds the whole r_c and the reduced (r.z, r.r) at co_red + Kp
 int pgo_handle::coarse_restrict_reduce(const double* rz_part, int n_rz, const double* rr_part, int n_rr, const int32_t* done) {
-  const int slots = (co_Kp + 2) / 3;
-  hipLaunchKernelGGL(dev::k_coarse_restrict_m<>, dim3((slots + 3) / 4), dim3(256), 0, stream, (int)S.n_loc, (int)S.lo, co_agg, co_aoff, co_nown,
-                     co_Kp, (const double*)co_pb, (int64_t)S.n_poses, (const double*)r, co_red, done);
+  const int slots = (CO().co_Kp + 2) / 3;
+  hipLaunchKernelGGL(dev::k_coarse_restrict_m<>, dim3((slots + 3) / 4), dim3(256), 0, stream, (int)S.n_loc, (int)S.lo, CO().co_agg, CO().co_aoff, CO().co_nown,
+                     CO().co_Kp, (const double*)co_pb, (int64_t)S.n_poses, (const double*)r, co_red, done);
   PGOC(check_launch("k_coarse_restrict_m"));
-  return reduce_parts({{rz_part, n_rz, 0}, {rr_part, n_rr, 0}}, co_red + co_Kp, co_red, co_Kp + 2, false);
+  return reduce_parts({{rz_part, n_rz, 0}, {rr_part, n_rr, 0}}, co_red + CO().co_Kp, co_red, CO().co_Kp + 2, false);
 }
 
 int pgo_handle::coarse_solve(double* dot_part, const int32_t* done) {
-  const int nb = co_Kp / 32;
-  if (!co_multi)   // (several ranks: r_c came with the all-reduce, coarse_restrict_reduce)
-    hipLaunchKernelGGL(dev::k_coarse_restrict<>, dim3((co_nagg + 3) / 4), dim3(256), 0, stream, (int)S.n_loc, co_agg, co_nagg, (const double*)co_pb,
+  const int nb = CO().co_Kp / 32;
+  if (!co_multi())   // (several ranks: r_c came with the all-reduce, coarse_restrict_reduce)
+    hipLaunchKernelGGL(dev::k_coarse_restrict<>, dim3((CO().co_nagg + 3) / 4), dim3(256), 0, stream, (int)S.n_loc, CO().co_agg, CO().co_nagg, (const double*)co_pb,
                        (const double*)r, co_rc, done);
   if (co_ainv) {
-    hipLaunchKernelGGL(dev::k_coarse_matvec<>, dim3(co_ndot), dim3(256), 0, stream, (const double*)co_ainv, co_Kp, (const double*)co_rc, co_ec,
+    hipLaunchKernelGGL(dev::k_coarse_matvec<>, dim3(CO().co_ndot), dim3(256), 0, stream, (const double*)co_ainv, CO().co_Kp, (const double*)co_rc, co_ec,
                        dot_part, (const int32_t*)co_ok, done);
   } else {
-    hipLaunchKernelGGL(dev::k_tri_apply<>, dim3(nb), dim3(256), 0, stream, (const double*)co_nm, co_Kp, nb, (const double*)co_rc, co_cy, 0);
-    hipLaunchKernelGGL(dev::k_tri_apply<>, dim3(nb), dim3(256), 0, stream, (const double*)co_nm, co_Kp, nb, (const double*)co_cy, co_ec, 1);
-    hipLaunchKernelGGL(dev::k_coarse_dot<>, dim3(co_ndot), dim3(256), 0, stream, co_Kp, (const double*)co_rc, co_ec, dot_part,
+    hipLaunchKernelGGL(dev::k_tri_apply<>, dim3(nb), dim3(256), 0, stream, (const double*)co_nm, CO().co_Kp, nb, (const double*)co_rc, co_cy, 0);
+    hipLaunchKernelGGL(dev::k_tri_apply<>, dim3(nb), dim3(256), 0, stream, (const double*)co_nm, CO().co_Kp, nb, (const double*)co_cy, co_ec, 1);
+    hipLaunchKernelGGL(dev::k_coarse_dot<>, dim3(CO().co_ndot), dim3(256), 0, stream, CO().co_Kp, (const double*)co_rc, co_ec, dot_part,
                        (const int32_t*)co_ok, done);
   }
   return check_launch("coarse level solve");
@@ -140,22 +140,22 @@ int pgo_handle::pcg(int* iters, double* rel) {
   const bool multi = multi_rank();
   dev::GroupPre GP;
   GP.ginv = ginv;
-  GP.B = grp_B;
-  GP.nb = grp_nb;
-  GP.nb_pad = grp_pad;
-  GP.n_groups = n_groups;
-  const bool grouped = grp_B > 1, chained = chain_len > 0;
-  const int g_u1 = chained ? g_chain : (grouped ? g_grp : g_vec);  // grid (= number of partials) of the init / update1 kernels
+  GP.B = plan.own.grp_B;
+  GP.nb = plan.own.grp_nb;
+  GP.nb_pad = plan.own.grp_pad;
+  GP.n_groups = plan.own.n_groups;
+  const bool grouped = plan.own.grp_B > 1, chained = plan.all.chain_len > 0;
+  const int g_u1 = chained ? plan.own.g_chain : (grouped ? plan.own.g_grp : plan.own.g_vec);  // grid (= number of partials) of the init / update1 kernels
   if (chained) launch_cg_init_chain(gs, part[0], part[1]);
   else if (grouped) hipLaunchKernelGGL(dev::k_cg_init_g<>, dim3(g_u1), dim3(dev::WG), 0, stream, V, GP, (const double*)gs, part[0], part[1]);
   else hipLaunchKernelGGL(dev::k_cg_init<>, dim3(g_u1), dim3(dev::WG), 0, stream, V, gs, part[0], part[1]);
   PGOC(check_launch("k_cg_init"));
-  const bool sr = use_sr && chained;
+  const bool sr = plan.all.use_sr && chained;
   // single-reduction loop: "make u visible to the peers, w = A u, reduce (gamma, rr, delta) together, new coefficients"
   auto sr_product_and_scalars = [&](int first) -> int {
-    int n_sp = g_spmv;
+    int n_sp = plan.own.g_spmv;
     const int32_t* done = first ? nullptr : &st->done;
-    if (overlap) PGOC(spmv_with_halo(p_full, ap, part[2], done, &n_sp));
+    if (plan.own.overlap) PGOC(spmv_with_halo(p_full, ap, part[2], done, &n_sp));
     else {
       PGOC(share_gather_vector(p_full));
       PGOC(spmv_enqueue(p_full, ap, part[2], 1, done));
@@ -170,40 +170,40 @@ int pgo_handle::pcg(int* iters, double* rel) {
     PGOC(sr_product_and_scalars(1));
   } else {
     // two levels: z (= p) of the start-up kernel gets the coarse correction, r.z one more partial
-    const int n_rz0 = use_coarse ? g_u1 + co_ndot : g_u1;
-    if (use_coarse && co_multi) {
+    const int n_rz0 = coarse_on() ? g_u1 + CO().co_ndot : g_u1;
+    if (coarse_on() && co_multi()) {
       // several ranks: r_c rides in the all-reduce of the start-up sums; the coarse share is added to the reduced r.z once
       PGOC(coarse_restrict_reduce(part[0], g_u1, part[1], g_u1, nullptr));
       PGOC(coarse_solve(co_dotp, nullptr));
-      hipLaunchKernelGGL(dev::k_coarse_fin<>, dim3(1), dim3(dev::WG), 0, stream, (const double*)(co_red + co_Kp), (const double*)co_dotp, co_ndot,
+      hipLaunchKernelGGL(dev::k_coarse_fin<>, dim3(1), dim3(dev::WG), 0, stream, (const double*)(co_red + CO().co_Kp), (const double*)co_dotp, CO().co_ndot,
                          scal + 4);
       PGOC(check_launch("k_coarse_fin"));
       hipLaunchKernelGGL(dev::k_coarse_prolong_m<>, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((S.n_loc + 255) / 256, 512))), dim3(256), 0,
-                         stream, (int)S.n_loc, (int)S.lo, co_agg, (const double*)co_pb, (int64_t)S.n_poses, (const double*)co_ec, z, p_full,
+                         stream, (int)S.n_loc, (int)S.lo, CO().co_agg, (const double*)co_pb, (int64_t)S.n_poses, (const double*)co_ec, z, p_full,
                          (const int32_t*)co_ok);
       PGOC(check_launch("k_coarse_prolong_m"));
       hipLaunchKernelGGL(dev::k_flag_to_double<>, dim3(1), dim3(1), 0, stream, (const int*)co_ok, scal + 15);
       PGOC(check_launch("k_flag_to_double"));
       co_flag_pending = true;
-    } else if (use_coarse) {
+    } else if (coarse_on()) {
       PGOC(coarse_solve(part[0] + g_u1, nullptr));
       hipLaunchKernelGGL(dev::k_coarse_prolong<>, dim3((unsigned)std::min<int64_t>((S.n_loc + 255) / 256, 512)), dim3(256), 0, stream, (int)S.n_loc,
-                         co_agg, (const double*)co_pb, (const double*)co_ec, z, p_full + dev::PS * (int64_t)S.lo, (const int32_t*)co_ok);
+                         CO().co_agg, (const double*)co_pb, (const double*)co_ec, z, p_full + dev::PS * (int64_t)S.lo, (const int32_t*)co_ok);
       PGOC(check_launch("k_coarse_prolong"));
       // whether this solve has the level: read back with the model terms (lm_iteration_tail), counted in co_off_iters
       hipLaunchKernelGGL(dev::k_flag_to_double<>, dim3(1), dim3(1), 0, stream, (const int*)co_ok, scal + 15);
       PGOC(check_launch("k_flag_to_double"));
       co_flag_pending = true;
     }
-    if (!(use_coarse && co_multi)) PGOC(reduce_to_scal({{part[0], n_rz0, 0}, {part[1], g_u1, 0}}, 4));
+    if (!(coarse_on() && co_multi())) PGOC(reduce_to_scal({{part[0], n_rz0, 0}, {part[1], g_u1, 0}}, 4));
     hipLaunchKernelGGL(dev::k_cg_init_fin<>, dim3(1), dim3(1), 0, stream, st, scal + 4, opt.pcg_rtol);
     PGOC(check_launch("k_cg_init_fin"));
-    if (!overlap) PGOC(share_gather_vector(p_full));
+    if (!plan.own.overlap) PGOC(share_gather_vector(p_full));
   }
   const int max_it = std::max(0, opt.pcg_max_iters);
   int every = std::max(1, opt.pcg_check_every);
   // one PCG iteration = 3 dependent launches; `par` is the r.z double-buffer parity baked into the arguments
-  const bool fused = fused_p && !multi;
+  const bool fused = plan.all.fused_p && !multi;
   double* pbuf[2] = {p_full, p_full2};
   if (fused) HIPC(hipMemsetAsync(p_full2, 0, (size_t)dev::PS * n_full * sizeof(double), stream));  // "p_old" of iteration 0
   auto enqueue_iteration = [&](int par) -> int {
@@ -212,7 +212,7 @@ int pgo_handle::pcg(int* iters, double* rel) {
       PGOC(check_launch("k_cg_sr_cl"));
       return sr_product_and_scalars(0);
     }
-    int n_sp = g_spmv;
+    int n_sp = plan.own.g_spmv;
     dev::CgVec Vi = V;
     if (fused) {
       // the previous iteration's direction update happens inside this SpMV: p_old = pbuf[par ^ 1] -> p_new = pbuf[par]
@@ -224,11 +224,11 @@ int pgo_handle::pcg(int* iters, double* rel) {
       A.n_rz = A.n_rr = g_u1;
       A.parity = par ^ 1;
       A.st = st;
-      hipLaunchKernelGGL(dev::k_spmv_t<5>, dim3(g_spmv), dim3(dev::WG), 0, stream, A);
+      hipLaunchKernelGGL(dev::k_spmv_t<5>, dim3(plan.own.g_spmv), dim3(dev::WG), 0, stream, A);
       PGOC(check_launch("k_spmv (fused direction update)"));
       Vi.p = pbuf[par];
       Vi.fused = 1;
-    } else if (overlap) PGOC(spmv_with_halo(p_full, ap, part[0], &st->done, &n_sp));  // p reaches the peers inside
+    } else if (plan.own.overlap) PGOC(spmv_with_halo(p_full, ap, part[0], &st->done, &n_sp));  // p reaches the peers inside
     else PGOC(spmv_enqueue(p_full, ap, part[0], 1, &st->done));
     // p.Ap: every workgroup of the update kernel re-sums the product's partials itself -- up to 2048 of them; more (k_spmv_1:
     // one per tile) are folded to 16 first (k_fold_partials); several ranks: k_finalize + all-reduce
@@ -245,28 +245,28 @@ int pgo_handle::pcg(int* iters, double* rel) {
     else hipLaunchKernelGGL(dev::k_cg_update1<>, dim3(g_u1), dim3(dev::WG), 0, stream, Vi, par, pap, n_pap, part[1], part[2]);
     PGOC(check_launch("k_cg_update1"));
     if (fused) return PGO_OK;  // its r.z / r.r partials are booked by the next SpMV, or by k_cg_book at the end of the slice
-    if (use_coarse && co_multi) {   // second level, several ranks: r_c in the all-reduce of (r.z, r.r), replicated coarse solve
+    if (coarse_on() && co_multi()) {   // second level, several ranks: r_c in the all-reduce of (r.z, r.r), replicated coarse solve
       PGOC(coarse_restrict_reduce(part[1], g_u1, part[2], g_u1, &st->done));
       PGOC(coarse_solve(co_dotp, &st->done));
-      hipLaunchKernelGGL(dev::k_cg_update2cm<>, dim3(g_vec), dim3(dev::WG), 0, stream, V, par, (const double*)(co_red + co_Kp), (const double*)co_dotp,
-                         co_ndot, co_agg, (const double*)co_pb, (int64_t)S.n_poses, (const double*)co_ec);
+      hipLaunchKernelGGL(dev::k_cg_update2cm<>, dim3(plan.own.g_vec), dim3(dev::WG), 0, stream, V, par, (const double*)(co_red + CO().co_Kp), (const double*)co_dotp,
+                         CO().co_ndot, CO().co_agg, (const double*)co_pb, (int64_t)S.n_poses, (const double*)co_ec);
       PGOC(check_launch("k_cg_update2cm"));
-      if (!overlap) PGOC(share_gather_vector(p_full));
+      if (!plan.own.overlap) PGOC(share_gather_vector(p_full));
       return PGO_OK;
     }
-    if (use_coarse) {   // second level (single rank): e_c, its share of r.z as more partials, prolongation inside the direction update
+    if (coarse_on()) {   // second level (single rank): e_c, its share of r.z as more partials, prolongation inside the direction update
       PGOC(coarse_solve(part[1] + g_u1, &st->done));
-      hipLaunchKernelGGL(dev::k_cg_update2c<>, dim3(g_vec), dim3(dev::WG), 0, stream, V, par, (const double*)part[1], g_u1 + co_ndot,
-                         (const double*)part[2], g_u1, co_agg, (const double*)co_pb, (const double*)co_ec);
+      hipLaunchKernelGGL(dev::k_cg_update2c<>, dim3(plan.own.g_vec), dim3(dev::WG), 0, stream, V, par, (const double*)part[1], g_u1 + CO().co_ndot,
+                         (const double*)part[2], g_u1, CO().co_agg, (const double*)co_pb, (const double*)co_ec);
       return check_launch("k_cg_update2c");
     }
     if (multi) {
       PGOC(reduce_to_scal({{part[1], g_u1, 0}, {part[2], g_u1, 0}}, 7));
-      hipLaunchKernelGGL(dev::k_cg_update2<>, dim3(g_flat), dim3(dev::WG), 0, stream, V, par, scal + 7, 1, scal + 8, 1);
+      hipLaunchKernelGGL(dev::k_cg_update2<>, dim3(plan.own.g_flat), dim3(dev::WG), 0, stream, V, par, scal + 7, 1, scal + 8, 1);
       PGOC(check_launch("k_cg_update2"));
-      if (!overlap) PGOC(share_gather_vector(p_full));
+      if (!plan.own.overlap) PGOC(share_gather_vector(p_full));
     } else {
-      hipLaunchKernelGGL(dev::k_cg_update2<>, dim3(g_flat), dim3(dev::WG), 0, stream, V, par, part[1], g_u1, part[2], g_u1);
+      hipLaunchKernelGGL(dev::k_cg_update2<>, dim3(plan.own.g_flat), dim3(dev::WG), 0, stream, V, par, part[1], g_u1, part[2], g_u1);
       PGOC(check_launch("k_cg_update2"));
     }
     return PGO_OK;
@@ -283,7 +283,7 @@ int pgo_handle::pcg(int* iters, double* rel) {
   // a real peer (no multi-GPU lease yet), and a group of p2p calls inside a graph is the less travelled road -- its
   // first execution should be the plain one.  PGO_GRAPH_COLLECTIVES=2 captures it too.
   bool use_graph = opt.use_graphs && !graph_failed &&
-                   (!multi || (comm->capturable() && !overlap && graph_collectives > 0 && (!use_halo || graph_collectives > 1)));
+                   (!multi || (comm->capturable() && !plan.own.overlap && graph_collectives > 0 && (!plan.all.use_halo || graph_collectives > 1)));
   if (use_graph) {
     every += every & 1;
     if (!cg_graph_exec || cg_graph_len != every) {
@@ -353,16 +353,16 @@ int pgo_handle::pcg(int* iters, double* rel) {
   last_pcg_iters = h_st->iters;
   *iters = h_st->iters;
   *rel = (h_st->bb > 0.0) ? std::sqrt(h_st->rr / h_st->bb) : 0.0;
-  if (verify_residual) {
+  if (plan.all.verify_residual) {
     // test hook: report |b - A y| / |b| of the solution instead of the recurrence residual the loop stopped on (one more
     // product; the recurrences of either loop drift from it on ill-conditioned systems)
-    hipLaunchKernelGGL(dev::k_scatter_owned<>, dim3(g_flat), dim3(dev::WG), 0, stream, (int)S.n_loc, (int)S.lo, (const double*)V.y, p_full);
+    hipLaunchKernelGGL(dev::k_scatter_owned<>, dim3(plan.own.g_flat), dim3(dev::WG), 0, stream, (int)S.n_loc, (int)S.lo, (const double*)V.y, p_full);
     PGOC(check_launch("k_scatter_owned"));
     PGOC(share_gather_vector(p_full));
     PGOC(spmv_enqueue(p_full, ap, part[0], 1, nullptr));
-    hipLaunchKernelGGL(dev::k_residual_norm<>, dim3(g_flat), dim3(dev::WG), 0, stream, (int64_t)3 * S.n_loc, (const double*)gs, (const double*)ap, part[1], part[2]);
+    hipLaunchKernelGGL(dev::k_residual_norm<>, dim3(plan.own.g_flat), dim3(dev::WG), 0, stream, (int64_t)3 * S.n_loc, (const double*)gs, (const double*)ap, part[1], part[2]);
     PGOC(check_launch("k_residual_norm"));
-    PGOC(reduce_to_scal({{part[1], g_flat, 0}, {part[2], g_flat, 0}}, 4));
+    PGOC(reduce_to_scal({{part[1], plan.own.g_flat, 0}, {part[2], plan.own.g_flat, 0}}, 4));
     double h2[2] = {0.0, 0.0};
     HIPC(hipMemcpyAsync(h2, scal + 4, sizeof h2, hipMemcpyDeviceToHost, stream));
     PGOC(sync());
@@ -373,7 +373,7 @@ int pgo_handle::pcg(int* iters, double* rel) {
 
 // the PCG preconditioner for the current LM diagonal: dense pose-group inverses or the chain factorisation
 int pgo_handle::prepare_preconditioner() {
-  if (grp_B > 1) {
+  if (plan.own.grp_B > 1) {
     dev::GroupPrepArgs GA;
     GA.inc_ptr = inc_ptr;
     GA.inc_col = inc_col;
@@ -383,42 +383,42 @@ int pgo_handle::prepare_preconditioner() {
     GA.ginv = ginv;
     GA.n_loc = S.n_loc;
     GA.lo = S.lo;
-    GA.B = grp_B;
-    GA.nb = grp_nb;
-    GA.n_groups = n_groups;
-    hipLaunchKernelGGL(dev::k_prepare_groups<>, dim3(grp_prep_grid), dim3(dev::WG), grp_lds, stream, GA);
+    GA.B = plan.own.grp_B;
+    GA.nb = plan.own.grp_nb;
+    GA.n_groups = plan.own.n_groups;
+    hipLaunchKernelGGL(dev::k_prepare_groups<>, dim3(plan.own.grp_prep_grid), dim3(dev::WG), plan.own.grp_lds, stream, GA);
     PGOC(check_launch("k_prepare_groups"));
   }
-  if (chain_len) PGOC(factor_chain());
-  if (use_coarse) PGOC(coarse_factor());
+  if (plan.all.chain_len) PGOC(factor_chain());
+  if (coarse_on()) PGOC(coarse_factor());
   return PGO_OK;
 }
 
 // block LDL' of the chain preconditioner's segments (the records are complete: C part from k_assemble, M part from k_prepare)
 int pgo_handle::factor_chain() {
-  const int n_seg = (S.n_loc + chain_len - 1) / chain_len;
+  const int n_seg = (S.n_loc + plan.all.chain_len - 1) / plan.all.chain_len;
   // One THREAD per segment runs the recurrence (64 .. 256 dependent steps), 64 segments per wavefront: 244 wavefronts at 1M
   // poses.  Fewer segments per wavefront (16: four wavefronts per compute unit, each with its own queue of outstanding loads)
   // were measured SLOWER -- 233 us against 123 us: the same 128-byte-per-lane record loads then take four times as many
   // wave instructions through the address coalescer, and 174 instead of 122 MB are written.
   const int spw = 64;
   if (n_seg == 0) return PGO_OK;   // a rank that owns no rows
-  if (chain_chunk == 2)
-    hipLaunchKernelGGL(dev::k_chain_factor<2>, dim3((n_seg + spw - 1) / spw), dim3(spw), 0, stream, (const double*)chain_c, S.n_loc, chain_pad,
-                       chain_len, chain_w, chain_s);
+  if (plan.all.chain_chunk == 2)
+    hipLaunchKernelGGL(dev::k_chain_factor<2>, dim3((n_seg + spw - 1) / spw), dim3(spw), 0, stream, (const double*)chain_c, S.n_loc, plan.own.chain_pad,
+                       plan.all.chain_len, chain_w, chain_s);
   else
-    hipLaunchKernelGGL(dev::k_chain_factor<4>, dim3((n_seg + spw - 1) / spw), dim3(spw), 0, stream, (const double*)chain_c, S.n_loc, chain_pad,
-                       chain_len, chain_w, chain_s);
+    hipLaunchKernelGGL(dev::k_chain_factor<4>, dim3((n_seg + spw - 1) / spw), dim3(spw), 0, stream, (const double*)chain_c, S.n_loc, plan.own.chain_pad,
+                       plan.all.chain_len, chain_w, chain_s);
   return check_launch("k_chain_factor");
 }
 
 // LM diagonal for the current radius (per problem in a batched handle) + the preconditioner's set-up
 int pgo_handle::prepare_system() {
-  hipLaunchKernelGGL(dev::k_prepare<>, dim3(g_rows), dim3(dev::WG), 0, stream, hd, (const double*)diag_full, S.n_loc, S.lo, fixed_internal, tr.radius,
+  hipLaunchKernelGGL(dev::k_prepare<>, dim3(plan.own.g_rows), dim3(dev::WG), 0, stream, hd, (const double*)diag_full, S.n_loc, S.lo, fixed_internal, tr.radius,
                      opt.min_lm_diagonal, opt.max_lm_diagonal, d2, minv, (const uint8_t*)fixed_mask, (const int32_t*)prob_of_256,
-                     (const double*)prob_radius, chain_len ? chain_c : (double*)nullptr, hdd);
+                     (const double*)prob_radius, plan.all.chain_len ? chain_c : (double*)nullptr, hdd);
   PGOC(check_launch("k_prepare"));
-  if (!direct) PGOC(prepare_preconditioner());   // (the direct solve does not need it; its PCG fallback sets it up on demand)
+  if (!direct()) PGOC(prepare_preconditioner());   // (the direct solve does not need it; its PCG fallback sets it up on demand)
   return PGO_OK;
 }
 
