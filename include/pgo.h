@@ -937,8 +937,8 @@ int  pgo_loop_support(pgo_t* h, const pgo_loop_support_options* opt, const uint8
  *   edge e = (a, b, m) that is not a chain edge and has a / S != b / S, in the caller's edge order, as
  *   (a / S, b / S, C_a o m o C_b^-1) with orientation and kind kept and origin = e.  Theta of every coarse measurement is wrapped
  *   with atan2(sin, cos).  Edges inside one segment are dropped; parallel coarse edges are not merged.
- * - The coarse graph carries NO information matrices (unit information): propagating covariances through the composition is
- *   out of scope.  The pgo_set_active mask is ignored, as pgo_edge_chi2 ignores it; origin lets the caller mask the coarse graph.
+ * - The coarse graph of pgo_coarsen / pgo_coarsen_plan carries NO information matrices (unit information); "with information"
+ *   below propagates them.  The pgo_set_active mask is ignored, as pgo_edge_chi2 ignores it; origin lets the caller mask the coarse graph.
  * - A measurement that is not finite: PGO_ERR_NUMERIC, pgo_last_error names the smallest such edge.
  * - Prolongation of coarse poses X (K x 3), with t = (i - kS) / S: F_i = X_k o C_i; for k < K - 1, B_i = X_{k+1} o Cend_k^-1 o C_i
  *   and P_i = ((1-t) F_x + t B_x, (1-t) F_y + t B_y, F_th + t wrap(B_th - F_th)); the last segment is forward only, P_i = F_i.
@@ -975,6 +975,50 @@ int pgo_prolong_eval(int32_t n_poses, int32_t stride, const double* C /* N x 3 *
 int pgo_coarsen(pgo_t* h, int32_t stride, pgo_graph** coarse_out, int32_t* origin_or_null, int32_t origin_cap,
                 int32_t* n_coarse_edges_or_null);                                                                /* [gpu] */
 int pgo_prolong(pgo_t* h, int32_t stride, const double* coarse_xyt /* K x 3 */);                                 /* [gpu] */
+/* With information.  pgo_coarsen_info_plan and pgo_coarsen_info are pgo_coarsen_plan and pgo_coarsen with the edges' information
+ * matrices carried through the composition: same key poses, same coarse edges in the same order, same measurements.
+ * - A pair (A, Sigma_A) couples a motion with the covariance of ADDITIVE noise on its own triple (x, y, theta) -- what a g2o
+ *   information matrix is the inverse of.  Covariances are six doubles in the order of info6 (xx, xy, xt, yy, yt, tt).
+ *     (A, Sigma_A) o (B, Sigma_B) = (A o B, F Sigma_A F' + G Sigma_B G')
+ *        F = [1 0 -(s_A B.x + c_A B.y); 0 1 c_A B.x - s_A B.y; 0 0 1],  G = [c_A -s_A 0; s_A c_A 0; 0 0 1]
+ *     (A, Sigma_A)^-1 = (B, H Sigma_A H'),  B = A^-1,  H = [-c_A -s_A B.y; s_A -c_A -B.x; 0 0 -1]
+ *   First order in the noise; the identity pair is ((0, 0, 0), 0).  The covariance of a product does not depend on how it is
+ *   associated (chain rule), so the device's trees and the plan's serial fold agree up to rounding.
+ * - Z_i is the pair (m, Omega^-1) of its chain edge, inverted for an edge stored as (i + 1, i); C_i and Cend_k follow as above,
+ *   as pairs.  Composite k carries the information Sigma(Cend_k)^-1.  A kept edge e = (a, b, m, Omega) carries the inverse of the
+ *   covariance of pair(C_a) o (m, Omega^-1) o pair(C_b)^-1 (a and b lie in different segments: three independent factors).
+ *   Omega^-1 and Sigma^-1 are formed by Cholesky factorisation (the edge gate's), inverting the factor and multiplying.
+ *   Wrapping an angle does not touch a covariance.  A handle created without information matrices, or info6_or_null = NULL,
+ *   uses Omega = I on every edge.
+ * - Coarse edges that share chain motions -- the edges that leave or enter one segment, and that segment's composite -- are
+ *   CORRELATED.  The coarse graph treats them as independent: that correlation is ignored.
+ * - The coarse objective is in units of the fine information.  A robust kernel's scale on the coarse graph is the caller's to
+ *   choose: with info_weighting = 1 the DCS parameter phi of METHOD 1 acts on chi2 (on synth_manhattan(2000, 4.0, 0.1, 3),
+ *   stride 16, unit fine information: phi 0.5 leaves a prolonged start 10.4 m off, phi 5 gives 0.208 m).
+ * - PGO_ERR_NUMERIC, pgo_last_error naming the smallest such edge: a chain edge, or a kept edge of this stride, whose information
+ *   matrix is not finite and positive definite -- found before anything is written.  An edge this stride drops may hold
+ *   anything.  (A g2o EDGE2 file read positionally gives indefinite matrices: an error, not a graph.)  A coarse covariance that
+ *   lost positive definiteness to rounding is PGO_ERR_NUMERIC as well.
+ * pgo_coarsen_info_plan: pgo_coarsen_plan's arguments, info6_or_null (E x 6) in; coarse_info and coarse_cov (edge_cap x 6, either
+ * may be NULL) and, optionally, the covariances of C (N x 6) and of Cend ((K - 1) x 6) out.  Serial, folded left to right.
+ * pgo_coarsen_info: pgo_coarsen's arguments and cov_or_null (cap x 6; cap counts the entries of origin_or_null and of
+ * cov_or_null alike).  The graph it returns carries the propagated information.  It leaves C and Cend of that stride on the
+ * handle exactly as pgo_coarsen does: pgo_prolong works after either.  Kernels of its own -- one wavefront per segment scans
+ * pairs in pgo_coarsen's tree (the lane's motions are folded once for the scan and again for the write-out), one lane per kept
+ * edge writes measurement, covariance and information to pgo_coarsen's slots -- and still one copy-out.  The information
+ * matrices are checked on the host, once per handle: the handle keeps no host copy of them, so the FIRST pgo_coarsen_info on a
+ * handle copies the six planes back (48 bytes per edge, about 190 MB at 4M edges) and factors every matrix; later calls, at
+ * any stride, read one flag per edge.  Everything pgo_coarsen promises holds: no atomics, two calls bitwise
+ * equal, pose_ordering and "coarsen_grid" play no part, the LM state is untouched, buffers grown on demand and kept.          */
+int pgo_coarsen_info_plan(int32_t n_poses, int32_t n_edges, const int32_t* ia, const int32_t* ib, const double* meas_xyt,
+                          const uint8_t* kind, const double* info6_or_null /* E x 6 */, int32_t stride, int32_t* n_coarse_poses_out,
+                          int32_t edge_cap, int32_t* coarse_ia, int32_t* coarse_ib, double* coarse_meas /* cap x 3 */,
+                          uint8_t* coarse_kind, int32_t* coarse_origin, double* coarse_info_or_null /* cap x 6 */,
+                          double* coarse_cov_or_null /* cap x 6 */, int32_t* n_coarse_edges_out,
+                          double* C_or_null /* N x 3 */, double* Cend_or_null /* (K - 1) x 3 */,
+                          double* Ccov_or_null /* N x 6 */, double* Cendcov_or_null /* (K - 1) x 6 */);           /* [host] */
+int pgo_coarsen_info(pgo_t* h, int32_t stride, pgo_graph** coarse_out, int32_t* origin_or_null, double* cov_or_null /* cap x 6 */,
+                     int32_t cap, int32_t* n_coarse_edges_or_null);                                               /* [gpu] */
 
 /* ------------------------------------------------ kernel-level entry points
  * Used by the parity tests and by bench.py's roofline leg: each launches exactly

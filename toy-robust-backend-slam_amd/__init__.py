@@ -26,7 +26,7 @@ __all__ = ["PgoError", "Options", "Summary", "IterRecord", "ReadG2O", "Graph", "
            "GateJointOptions", "GateJointResult", "GateJointSummary", "gate_joint_evaluate", "GATE_JOINT_MAX",
            "window_plan", "WindowResult", "WINDOW_MAX_POSES", "WINDOW_MAX_EDGES", "WINDOW_MAX_ITERS",
            "synth_manhattan_truth", "trajectory_error", "TrajOptions", "TrajError", "EdgeWeight", "SCORE_POSES_PER_WG",
-           "coarsen_plan", "prolong_eval", "COARSEN_MIN_STRIDE", "COARSEN_MAX_STRIDE",
+           "coarsen_plan", "coarsen_info_plan", "prolong_eval", "COARSEN_MIN_STRIDE", "COARSEN_MAX_STRIDE",
            "gnc_weight_eval", "GncStats", "GncOptions", "GncRound", "GncSummary",
            "loop_support_plan", "LoopSupportOptions", "LoopSupportRecord", "LoopSupportStats", "LOOP_SUPPORT_MAX_WINDOW"]
 
@@ -58,7 +58,7 @@ EXPORTS = [
     "pgo_gate_joint_options_default", "pgo_gate_joint_evaluate", "pgo_edge_gate_joint",
     "pgo_window_plan", "pgo_window_solve", "pgo_batch_window_solve",
     "pgo_synth_manhattan_truth", "pgo_traj_options_default", "pgo_trajectory_error_eval", "pgo_trajectory_error", "pgo_edge_weights",
-    "pgo_coarsen_plan", "pgo_prolong_eval", "pgo_coarsen", "pgo_prolong",
+    "pgo_coarsen_plan", "pgo_prolong_eval", "pgo_coarsen", "pgo_prolong", "pgo_coarsen_info_plan", "pgo_coarsen_info",
     "pgo_set_edge_weights", "pgo_get_edge_weights", "pgo_gnc_options_default", "pgo_gnc_weight_eval", "pgo_gnc_update", "pgo_gnc_solve",
     "pgo_loop_support_options_default", "pgo_loop_support_plan", "pgo_loop_support",
 ]
@@ -475,6 +475,9 @@ def lib():
     L.pgo_edge_weights.argtypes = [vp, dp, C.POINTER(EdgeWeight)]
     L.pgo_coarsen_plan.argtypes = [C.c_int32, C.c_int32, ip, ip, dp, bp, C.c_int32, ip, C.c_int32, ip, ip, dp, bp, ip, ip, dp, dp]
     L.pgo_prolong_eval.argtypes = [C.c_int32, C.c_int32, dp, dp, dp, dp]
+    L.pgo_coarsen_info_plan.argtypes = [C.c_int32, C.c_int32, ip, ip, dp, bp, dp, C.c_int32, ip, C.c_int32, ip, ip, dp, bp, ip, dp, dp, ip,
+                                        dp, dp, dp, dp]
+    L.pgo_coarsen_info.argtypes = [vp, C.c_int32, C.POINTER(vp), ip, dp, C.c_int32, ip]
     L.pgo_coarsen.argtypes = [vp, C.c_int32, C.POINTER(vp), ip, C.c_int32, ip]
     L.pgo_prolong.argtypes = [vp, C.c_int32, dp]
     L.pgo_set_edge_weights.argtypes = [vp, dp]
@@ -794,6 +797,46 @@ def coarsen_plan(n_poses, ia, ib, meas, kind, stride, edge_cap=None, want_compos
            "origin": co[:n].copy()}
     if want_composites:
         out["C"], out["Cend"] = Cc[:int(n_poses)], Ce[:K - 1].copy()
+    return out
+
+
+def coarsen_info_plan(n_poses, ia, ib, meas, kind, stride, info=None, edge_cap=None, want_composites=True):
+    """pgo_coarsen_info_plan (host only): coarsen_plan with the information matrices carried through the composition.  info
+    (E, 6) in the order of info6, or None = unit matrices.  Returns coarsen_plan's dict with "info" and "cov" (n, 6) of the
+    coarse edges and, with want_composites, "Ccov" (n_poses, 6) and "Cendcov" (K - 1, 6).  An information matrix of a chain
+    edge or a kept edge that is not finite and positive definite raises PgoError (NUMERIC) naming the edge."""
+    ia = np.ascontiguousarray(ia, np.int32)
+    ib = np.ascontiguousarray(ib, np.int32)
+    meas = np.ascontiguousarray(meas, np.float64).reshape(-1, 3)
+    kind = np.ascontiguousarray(kind, np.uint8)
+    if not (len(ia) == len(ib) == len(kind) == len(meas)):
+        raise ValueError("coarsen_info_plan: ia, ib, meas and kind must have one entry per edge")
+    if info is not None:
+        info = np.ascontiguousarray(info, np.float64).reshape(-1, 6)
+        if len(info) != len(ia):
+            raise ValueError("coarsen_info_plan: info must be (n_edges, 6)")
+    cap = len(ia) if edge_cap is None else int(edge_cap)
+    m = max(cap, 1)
+    cia, cib, cm, ck, co = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros((m, 3)), np.zeros(m, np.uint8), np.zeros(m, np.int32)
+    ci, cc = np.zeros((m, 6)), np.zeros((m, 6))
+    nK, nE = C.c_int32(-1), C.c_int32(-1)
+    n1 = max(int(n_poses), 1)
+    Cc, Ce, Cw, Cew = ((np.zeros((n1, 3)), np.zeros((n1, 3)), np.zeros((n1, 6)), np.zeros((n1, 6))) if want_composites
+                       else (None, None, None, None))
+    st = lib().pgo_coarsen_info_plan(n_poses, len(ia), _ip(ia), _ip(ib), _dp(meas), _bp(kind), _dp(info), int(stride), C.byref(nK), cap,
+                                     _ip(cia), _ip(cib), _dp(cm), _bp(ck), _ip(co), _dp(ci), _dp(cc), C.byref(nE), _dp(Cc), _dp(Ce),
+                                     _dp(Cw), _dp(Cew))
+    if st != 0:
+        try:
+            _check(st)
+        except PgoError as e:
+            e.n_poses, e.n_edges = nK.value, nE.value
+            raise
+    n, K = nE.value, nK.value
+    out = {"n_poses": K, "ia": cia[:n].copy(), "ib": cib[:n].copy(), "meas": cm[:n].copy(), "kind": ck[:n].copy(),
+           "origin": co[:n].copy(), "info": ci[:n].copy(), "cov": cc[:n].copy()}
+    if want_composites:
+        out["C"], out["Cend"], out["Ccov"], out["Cendcov"] = Cc[:int(n_poses)], Ce[:K - 1].copy(), Cw[:int(n_poses)], Cew[:K - 1].copy()
     return out
 
 
@@ -1158,14 +1201,20 @@ class Solver:
         _check(lib().pgo_loop_support(self._h, C.byref(o), _bp(m) if m is not None else None, res, C.byref(st)))
         return _support_records(res, self.n_edges), st.as_dict()
 
-    def coarsen(self, stride: int):
+    def coarsen(self, stride: int, information: bool = False):
         """pgo_coarsen: the coarse graph of the handle's measurements at `stride` (see coarsen_plan), with the handle's current
         poses at the key poses as its initial poses.  Returns (Graph, origin): origin[e] = the fine edge behind coarse edge e,
         -1 for a composite of the odometry chain.  The handle keeps the composites of this stride for prolong and is
-        otherwise left as it was."""
+        otherwise left as it was.  information=True: pgo_coarsen_info -- the information matrices carried through the
+        composition (coarsen_info_plan); returns (Graph, origin, cov) with cov (n, 6) the coarse edges' covariances, the
+        graph carrying their inverses."""
         g = C.c_void_p()
         origin = np.zeros(max(self.n_edges, 1), np.int32)   # (a coarse graph never has more edges than the fine one)
         n = C.c_int32(-1)
+        if information:
+            cov = np.zeros((max(self.n_edges, 1), 6))
+            _check(lib().pgo_coarsen_info(self._h, int(stride), C.byref(g), _ip(origin), _dp(cov), self.n_edges, C.byref(n)))
+            return Graph(g), origin[:n.value].copy(), cov[:n.value].copy()
         _check(lib().pgo_coarsen(self._h, int(stride), C.byref(g), _ip(origin), self.n_edges, C.byref(n)))
         return Graph(g), origin[:n.value].copy()
 
@@ -1179,23 +1228,36 @@ class Solver:
         _check(lib().pgo_prolong(self._h, s, _dp(X)))
 
     def initialize_hierarchical(self, stride: int, coarse_options: "Options | None" = None, device: int = 0,
-                                carry_weights: bool = False) -> Summary:
+                                carry_weights: bool = False, information: bool = False) -> Summary:
         """coarsen -> a solver on the coarse graph -> solve -> prolong: the handle's poses start the fine solve near the answer
         of the coarse one.  coarse_options (default: the handle's method, pcg_rtol 1e-10 -- the exact mode --, everything else
         left to the library; a fixed pose that is a key pose stays the fixed pose).  carry_weights: every coarse edge takes the
         weight its fine edge has in the handle's weight plane (after loop_support(apply=True): the coarse solve runs without
-        the dropped loops); the composites of the chain have weight 1.  Returns the coarse solve's Summary."""
+        the dropped loops); the composites of the chain have weight 1.  information=True: the coarse graph carries the
+        propagated information matrices (coarsen(stride, information=True)) and the default coarse options set
+        info_weighting = 1, so the coarse objective is the fine one's; a robust kernel's scale (phi of METHOD 1) then acts on
+        chi2 and is the caller's to set through coarse_options.  The weight plane refuses info_weighting = 1, so carried
+        weights must be 0 or 1 (ValueError otherwise) and are passed as set_active(edge_active=...).  Returns the coarse
+        solve's Summary."""
         s = int(stride)
-        graph, origin = self.coarsen(s)
+        graph, origin = self.coarsen(s, information=True)[:2] if information else self.coarsen(s)
         if coarse_options is None:
             f = int(self.options.fixed_pose)
             coarse_options = Options(method=int(self.options.method), pcg_rtol=1e-10,
-                                     fixed_pose=(f if f < 0 else (f // s if f % s == 0 else 0)))
+                                     fixed_pose=(f if f < 0 else (f // s if f % s == 0 else 0)),
+                                     info_weighting=1 if information else 0)
+        w = None
+        if carry_weights:
+            w = self.get_edge_weights()
+            w = np.where(origin >= 0, w[np.maximum(origin, 0)], 1.0)
+            if information and not np.isin(w, (0.0, 1.0)).all():
+                raise ValueError("initialize_hierarchical: information=True carries weights 0 and 1 only")
         coarse = Solver(graph, coarse_options, device=device)
         try:
-            if carry_weights:
-                w = self.get_edge_weights()
-                coarse.set_edge_weights(np.where(origin >= 0, w[np.maximum(origin, 0)], 1.0))
+            if w is not None and information:
+                coarse.set_active(edge_active=w != 0.0)
+            elif w is not None:
+                coarse.set_edge_weights(w)
             summary = coarse.solve()
             self.prolong(s, coarse.poses())
         finally:

@@ -10,10 +10,29 @@
 //   edge (a, b, m)  ->  (a / S, b / S, C_a o m o C_b^-1)  theta wrapped
 //   P_i      = blend of F_i = X_k o C_i and B_i = X_{k+1} o Cend_k^-1 o C_i at t = (i - kS) / S
 // Angles are wrapped (atan2(sin, cos)) in two places only: theta of a coarse measurement, and B_th - F_th in the blend.
+// Information matrices ("with information": pgo_coarsen_info_plan, pgo_coarsen_info) ride along as covariances.  A pair
+// (A, Sigma_A) couples a motion with the covariance of ADDITIVE noise on its own triple (x, y, theta) -- what a g2o information
+// matrix is the inverse of --, six doubles in the order of info6 (xx, xy, xt, yy, yt, tt):
+//   identity   (se2_identity(), 0)
+//   compose    (A, Sigma_A) o (B, Sigma_B) = (A o B, F Sigma_A F' + G Sigma_B G')
+//                F = [1 0 -(s_A B.x + c_A B.y); 0 1 c_A B.x - s_A B.y; 0 0 1]      G = [c_A -s_A 0; s_A c_A 0; 0 0 1]
+//   inverse    B = A^-1: (B, H Sigma_A H'),  H = [-c_A -s_A B.y; s_A -c_A -B.x; 0 0 -1]
+// first order in the noise.  The covariance of a product is sum_i D_i Sigma_i D_i' with D_i the derivative of the whole product
+// in its i-th factor: the chain rule makes it independent of the association, so trees and serial folds agree up to rounding.
+//   Z_i      as a pair: (m, Omega^-1) of the chain edge, the pair inverted for an edge stored as (i + 1, i); Omega = I without
+//            information matrices.  C_i and Cend_k follow as above, as pairs.
+//   composite edge k:  information = Sigma(Cend_k)^-1
+//   edge (a, b, m, Omega):  pair(C_a) o (m, Omega^-1) o pair(C_b)^-1 -- a and b lie in different segments, so the three factors
+//            are independent; its mean, wrapped, is the measurement above; information = the inverse of its covariance
+// Omega^-1 and Sigma^-1 go through gate_chol3: factor, invert the factor, multiply.  Wrapping an angle does not touch Sigma.
+// Coarse edges that share chain motions (the edges that leave or enter one segment, and that segment's composite) are
+// CORRELATED; the coarse graph treats them as independent.  That correlation is ignored.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <cmath>
+
+#include "gate.h"
 
 namespace pgo {
 
@@ -74,6 +93,119 @@ __host__ __device__ __forceinline__ void coarsen_transport(const Se2& Ca, double
   out[2] = coarsen_wrap(R.th);
 }
 
+// ------------------------------------------------------------------ pairs (motion, covariance)
+struct Se2Cov {
+  Se2 m;
+  double v[6];   // xx xy xt yy yt tt
+};
+__host__ __device__ __forceinline__ Se2Cov pair_identity() { return Se2Cov{se2_identity(), {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}}; }
+// R Sigma R' with R = [c -s 0; s c 0; 0 0 1]; (c, s) = (1, 0) returns Sigma bitwise
+__host__ __device__ __forceinline__ void cov_rotate(const double v[6], double c, double s, double o[6]) {
+  const double t1 = c * v[0] - s * v[1], t2 = c * v[1] - s * v[3];
+  const double t3 = s * v[0] + c * v[1], t4 = s * v[1] + c * v[3];
+  o[0] = t1 * c - t2 * s;
+  o[1] = t1 * s + t2 * c;
+  o[2] = c * v[2] - s * v[4];
+  o[3] = t3 * s + t4 * c;
+  o[4] = s * v[2] + c * v[4];
+  o[5] = v[5];
+}
+// F Sigma F' with F = [1 0 fx; 0 1 fy; 0 0 1]
+__host__ __device__ __forceinline__ void cov_shear(const double v[6], double fx, double fy, double o[6]) {
+  o[0] = v[0] + (2.0 * fx * v[2] + fx * fx * v[5]);
+  o[1] = v[1] + (fx * v[4] + fy * v[2] + fx * fy * v[5]);
+  o[2] = v[2] + fx * v[5];
+  o[3] = v[3] + (2.0 * fy * v[4] + fy * fy * v[5]);
+  o[4] = v[4] + fy * v[5];
+  o[5] = v[5];
+}
+// the mean is se2_compose itself; composing with pair_identity() on either side leaves a pair bitwise unchanged (a covariance
+// holds no negative zero: cov_invert does not produce one, and a sum with +0 removes it)
+__host__ __device__ __forceinline__ Se2Cov pair_compose(const Se2Cov& A, const Se2Cov& B) {
+  Se2Cov R;
+  R.m = se2_compose(A.m, B.m);
+  double f[6], g[6];
+  cov_shear(A.v, -(A.m.s * B.m.x + A.m.c * B.m.y), A.m.c * B.m.x - A.m.s * B.m.y, f);
+  cov_rotate(B.v, A.m.c, A.m.s, g);
+#pragma unroll
+  for (int i = 0; i < 6; ++i) R.v[i] = f[i] + g[i];
+  return R;
+}
+// the mean is se2_inverse itself.  H = -F G with G the rotation by -theta_A and F the shear by (-B.y, B.x): H Sigma H' = F G Sigma G' F'
+__host__ __device__ __forceinline__ Se2Cov pair_inverse(const Se2Cov& A) {
+  Se2Cov R;
+  R.m = se2_inverse(A.m);
+  double g[6];
+  cov_rotate(A.v, A.m.c, -A.m.s, g);
+  cov_shear(g, -R.m.y, R.m.x, R.v);
+  return R;
+}
+// o = w^-1 of a symmetric 3x3 (either way between information and covariance): w = L L' (gate_chol3), M = L^-1, o = M' M.
+// false -- o is not written -- when w is not finite and positive definite.  o holds no negative zero.
+__host__ __device__ __forceinline__ bool cov_invert(const double w[6], double o[6]) {
+  double l[6];
+  if (!gate_chol3(w, l)) return false;
+  const double m0 = 1.0 / l[0], m2 = 1.0 / l[2], m5 = 1.0 / l[5];
+  const double m1 = -(l[1] * m0) / l[2];
+  const double m3 = -(l[3] * m0 + l[4] * m1) / l[5];
+  const double m4 = -(l[4] * m2) / l[5];
+  o[0] = m0 * m0 + m1 * m1 + m3 * m3 + 0.0;
+  o[1] = m1 * m2 + m3 * m4 + 0.0;
+  o[2] = m3 * m5 + 0.0;
+  o[3] = m2 * m2 + m4 * m4 + 0.0;
+  o[4] = m4 * m5 + 0.0;
+  o[5] = m5 * m5;
+  return true;
+}
+// Z_i as a pair.  w: the chain edge's information, read only when has_info (else the identity).  false: it is not finite and
+// positive definite.  (The kernels pass w in registers: a pointer that may be null would put it in scratch.)
+__host__ __device__ __forceinline__ bool coarsen_chain_pair_w(double mx, double my, double mt, bool has_info, const double w[6], bool reversed,
+                                                              Se2Cov* out) {
+  Se2Cov P;
+  P.m = se2_make(mx, my, mt);
+  if (has_info) {
+    if (!cov_invert(w, P.v)) return false;
+  } else {
+    P.v[0] = P.v[3] = P.v[5] = 1.0;
+    P.v[1] = P.v[2] = P.v[4] = 0.0;
+  }
+  *out = reversed ? pair_inverse(P) : P;
+  return true;
+}
+// info6: the information, nullptr = the identity
+__host__ __device__ __forceinline__ bool coarsen_chain_pair(double mx, double my, double mt, const double* info6, bool reversed, Se2Cov* out) {
+  double w[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (info6)
+    for (int i = 0; i < 6; ++i) w[i] = info6[i];
+  return coarsen_chain_pair_w(mx, my, mt, info6 != nullptr, w, reversed, out);
+}
+// the transport with information: pair(C_a) o (m, Omega^-1) o pair(C_b)^-1.  meas = coarsen_transport's; cov its covariance.
+// false: Omega is not finite and positive definite (nothing written)
+__host__ __device__ __forceinline__ bool coarsen_transport_pair_w(const Se2Cov& Ca, double mx, double my, double mt, bool has_info,
+                                                                  const double w[6], const Se2Cov& Cb, double meas[3], double cov[6]) {
+  Se2Cov M;
+  if (!coarsen_chain_pair_w(mx, my, mt, has_info, w, false, &M)) return false;
+  const Se2Cov R = pair_compose(pair_compose(Ca, M), pair_inverse(Cb));
+  meas[0] = R.m.x;
+  meas[1] = R.m.y;
+  meas[2] = coarsen_wrap(R.m.th);
+#pragma unroll
+  for (int i = 0; i < 6; ++i) cov[i] = R.v[i];
+  return true;
+}
+__host__ __device__ __forceinline__ bool coarsen_transport_pair(const Se2Cov& Ca, double mx, double my, double mt, const double* info6,
+                                                                const Se2Cov& Cb, double meas[3], double cov[6]) {
+  double w[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (info6)
+    for (int i = 0; i < 6; ++i) w[i] = info6[i];
+  return coarsen_transport_pair_w(Ca, mx, my, mt, info6 != nullptr, w, Cb, meas, cov);
+}
+// the information of a coarse covariance; NaN throughout when the covariance has lost positive definiteness to rounding
+__host__ __device__ __forceinline__ void coarsen_info_of(const double cov[6], double info[6]) {
+  if (!cov_invert(cov, info))
+    for (int i = 0; i < 6; ++i) info[i] = NAN;
+}
+
 // The prolongation of fine pose i = kS + r (0 <= r < S): Xk the coarse pose of its segment, Xn the next one (read only when
 // has_next), Ci its composite, Cend the segment's closing composite (read only when has_next).  r = 0 returns Xk bitwise.
 __host__ __device__ __forceinline__ void coarsen_prolong_pose(const double Xk[3], const double* Xn, const double Ci[3], const double* Cend,
@@ -123,6 +255,41 @@ inline void coarsen_composites_serial(int64_t N, int64_t S, const int32_t* chain
       }
     }
   }
+}
+
+// the same with information: info6 (E x 6) or nullptr = the identity; Ccov: N x 6, Cendcov: (K - 1) x 6 (either pair of outputs
+// may be nullptr).  The means are coarsen_composites_serial's bitwise.  Returns the chain edge whose information is not finite
+// and positive definite (the first along the chain; the outputs are unfinished then), or -1.
+inline int64_t coarsen_composites_info_serial(int64_t N, int64_t S, const int32_t* chain, const int32_t* ia, const double* meas,
+                                              const double* info6, double* C, double* Cend, double* Ccov, double* Cendcov) {
+  Se2Cov A = pair_identity();
+  for (int64_t i = 0; i < N; ++i) {
+    if (i % S == 0) A = pair_identity();
+    if (C) {
+      C[3 * i] = A.m.x;
+      C[3 * i + 1] = A.m.y;
+      C[3 * i + 2] = A.m.th;
+    }
+    if (Ccov)
+      for (int c = 0; c < 6; ++c) Ccov[6 * i + c] = A.v[c];
+    if (i + 1 < N) {
+      const int64_t e = chain[i];
+      Se2Cov Z;
+      if (!coarsen_chain_pair(meas[3 * e], meas[3 * e + 1], meas[3 * e + 2], info6 ? info6 + 6 * e : nullptr, ia[e] != (int32_t)i, &Z)) return e;
+      A = pair_compose(A, Z);
+      if ((i + 1) % S == 0) {
+        const int64_t k = i / S;
+        if (Cend) {
+          Cend[3 * k] = A.m.x;
+          Cend[3 * k + 1] = A.m.y;
+          Cend[3 * k + 2] = A.m.th;
+        }
+        if (Cendcov)
+          for (int c = 0; c < 6; ++c) Cendcov[6 * k + c] = A.v[c];
+      }
+    }
+  }
+  return -1;
 }
 
 // coarse poses X (K x 3) -> fine poses out (N x 3)

@@ -587,7 +587,14 @@ struct pgo_handle {
   std::vector<uint8_t> cs_host;   // host image of a call's outputs
   int64_t cs_bad = -1;            // the smallest edge whose measurement is not finite (-1: none), found when the tables were built
   int coarsen_tables(const char* who, bool all_finite = true);   // all_finite: such an edge is PGO_ERR_NUMERIC
-  int coarsen(int32_t stride, pgo_graph** coarse_out, int32_t* origin, int32_t origin_cap, int32_t* n_coarse_edges);
+  // with_info (pgo_coarsen_info): cs_cov = the covariances of C | of Cend, cs_wbad[e] = the information of caller's edge e fails
+  // gate_chol3 (found once, on the host)
+  pgo::Scratch cs_cov;
+  std::vector<uint8_t> cs_wbad;
+  bool cs_wbad_ready = false;
+  int coarsen_info_check();
+  int coarsen(int32_t stride, pgo_graph** coarse_out, int32_t* origin, int32_t origin_cap, int32_t* n_coarse_edges, bool with_info = false,
+              double* cov = nullptr);
   int prolong(int32_t stride, const double* coarse_xyt);
 
   // loop support (pgo_loop_support; solver_support.hip).  It walks the tables of pgo_coarsen (cs_tab).  ls_traj = the trajectory

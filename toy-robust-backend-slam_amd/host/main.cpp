@@ -1,6 +1,6 @@
 // Command-line front end with the reference's run contract (DCS-ceres/main.cpp:22-40, do_build.sh:10):
 //     ./main DATASET NUM_OUTLIER_LOOPS METHOD [--seed S] [--data DIR] [--save DIR] [--device D] [--precision P]
-//            [--loss NAME[:A]] [--loop-loss NAME[:A]] [--score FILE [--align]] [--init-stride S] [--gnc CBAR [--gnc-inner K]]
+//            [--loss NAME[:A]] [--loop-loss NAME[:A]] [--score FILE [--align]] [--init-stride S [--init-info]] [--gnc CBAR [--gnc-inner K]]
 //            [--loop-support MIN[:WINDOW[:TOL_XY[:TOL_TH]]]]
 // METHOD 0 = baseline, 1 = DCS, 2 = switchable constraints run on the MI355X backend; 3/4 are outside it (exit code 3).
 // Reads DIR/DATASET.g2o (default ../data, as the reference), writes init_/opt_ nodes+edges text files that
@@ -46,6 +46,8 @@ int main(int argc, char* argv[]) {
               << "       [--score FILE [--align]]  (FILE: reference poses as writePoseGraph_nodes writes them, <index> <x> <y> <theta>; prints\n"
               << "       the trajectory error of the result against it, --align after a rigid fit; a wrong pose count: exit code 2)\n"
               << "       [--init-stride S]  (2..256: start the solve from the prolonged solution of the graph coarsened at stride S)\n"
+              << "       [--init-info]  (with --init-stride: the coarse graph carries information matrices propagated along the odometry chain --\n"
+              << "       unit fine information -- and is solved with info_weighting = 1; without --init-stride: exit code 2)\n"
               << "       [--gnc CBAR [--gnc-inner K]]  (METHOD 0 only: graduated non-convexity with the TLS surrogate over the closure and bogus\n"
               << "       blocks, CBAR = the residual norm above which a block is an outlier, K LM iterations per round, default 5; prints the\n"
               << "       rounds and writes weights.txt, one weight per edge in the order of the edges files)\n"
@@ -61,11 +63,16 @@ int main(int argc, char* argv[]) {
   long long seed = -1;
   int device = 0, precision = 0, score_align = 0, init_stride = 0, gnc_inner = 5;
   double gnc_cbar = 0.0;
-  bool gnc_on = false, support_on = false;
+  bool gnc_on = false, support_on = false, init_info = false;
   pgo::LoopSupportOptions support;
   for (int i = 4; i < argc; i += 2) {
     if (!strcmp(argv[i], "--align")) {   // (the one option without a value)
       score_align = 1;
+      --i;
+      continue;
+    }
+    if (!strcmp(argv[i], "--init-info")) {
+      init_info = true;
       --i;
       continue;
     }
@@ -111,6 +118,10 @@ int main(int argc, char* argv[]) {
   if (method < 0 || method > 2) {
     std::cerr << "METHOD " << method << " is not part of the MI355X backend (METHOD 0, 1 and 2 only)\n";
     return 3;
+  }
+  if (init_info && init_stride == 0) {
+    std::cerr << "--init-info goes with --init-stride\n";
+    return 2;
   }
   if (gnc_on && method != 0) {
     std::cerr << "--gnc runs on METHOD 0 only (the weights take the place of DCS / the switches)\n";
@@ -180,8 +191,8 @@ int main(int argc, char* argv[]) {
       pgo::Solver::Options coarse_options;
       coarse_options.device = device;
       pgo::Solver::Summary coarse;
-      pgo::InitializeHierarchical(&problem, init_stride, coarse_options, &coarse);
-      std::cout << "init-stride " << init_stride << ": coarse graph of " << coarse.num_parameter_blocks << " poses and " << coarse.num_residual_blocks
+      pgo::InitializeHierarchical(&problem, init_stride, coarse_options, &coarse, init_info);
+      std::cout << "init-stride " << init_stride << (init_info ? " (propagated information)" : "") << ": coarse graph of " << coarse.num_parameter_blocks << " poses and " << coarse.num_residual_blocks
                 << " edges, cost " << coarse.s.initial_cost << " -> " << coarse.s.final_cost << " in " << coarse.s.iterations << " iterations"
                 << std::endl;
     }

@@ -359,8 +359,10 @@ struct SolverAccess {
   // Hierarchical initialisation (include/pgo.h): the problem's graph coarsened at `stride`, the coarse graph solved exactly (the
   // problem's METHOD, pcg_rtol 1e-10, everything else left to the library; a constant block that is a key pose stays the
   // constant one), the result prolonged and written into the caller's parameter blocks in place -- the start of the Solve
-  // that follows.  Constant blocks are not moved.
-  static void InitializeHierarchical(const Solver::Options& opt, Problem* pr, int stride, Solver::Summary* coarse_sum) {
+  // that follows.  Constant blocks are not moved.  information: pgo_coarsen_info -- the coarse graph carries the information
+  // matrices propagated through the composition (unit fine information: a Problem holds none) and the coarse solve runs with
+  // info_weighting = 1; residual block weights must then be 0 or 1 and are passed as pgo_set_active.
+  static void InitializeHierarchical(const Solver::Options& opt, Problem* pr, int stride, Solver::Summary* coarse_sum, bool information) {
     pgo_t* h = Prepare(opt, pr);
     pgo_graph* cg = nullptr;
     pgo_t* ch = nullptr;
@@ -368,7 +370,8 @@ struct SolverAccess {
     const int32_t E = (int32_t)pr->ia_.size();
     std::vector<int32_t> origin(pr->weights_.empty() ? 0 : (size_t)E);
     int32_t n_coarse = 0;
-    int st = pgo_coarsen(h, stride, &cg, origin.empty() ? nullptr : origin.data(), (int32_t)origin.size(), &n_coarse);
+    int st = information ? pgo_coarsen_info(h, stride, &cg, origin.empty() ? nullptr : origin.data(), nullptr, (int32_t)origin.size(), &n_coarse)
+                         : pgo_coarsen(h, stride, &cg, origin.empty() ? nullptr : origin.data(), (int32_t)origin.size(), &n_coarse);
     Solver::Summary local;
     Solver::Summary* cs = coarse_sum ? coarse_sum : &local;
     if (st == PGO_OK) {
@@ -377,13 +380,30 @@ struct SolverAccess {
       o.method = pr->any_sc_ ? 2 : (pr->any_dcs_ ? 1 : 0);
       o.pcg_rtol = 1e-10;
       o.fixed_pose = pr->fixed_ < 0 ? pr->fixed_ : (pr->fixed_ % stride == 0 ? pr->fixed_ / stride : 0);
+      o.info_weighting = information ? 1 : 0;
       st = pgo_create_from_graph(&ch, cg, &o, nullptr, opt.device);
     }
+    bool binary = true;
     if (st == PGO_OK && !origin.empty()) {
       std::vector<double> cw((size_t)n_coarse, 1.0);
       for (int32_t e = 0; e < n_coarse; ++e)
         if (origin[e] >= 0 && (size_t)origin[e] < pr->weights_.size()) cw[e] = pr->weights_[origin[e]];
-      st = pgo_set_edge_weights(ch, cw.data());
+      if (information) {   // (the weight plane refuses info_weighting = 1)
+        std::vector<uint8_t> on((size_t)n_coarse);
+        for (int32_t e = 0; e < n_coarse; ++e) {
+          binary = binary && (cw[e] == 0.0 || cw[e] == 1.0);
+          on[e] = cw[e] != 0.0;
+        }
+        if (binary) st = pgo_set_active(ch, on.data(), nullptr);
+      } else {
+        st = pgo_set_edge_weights(ch, cw.data());
+      }
+    }
+    if (!binary) {
+      pgo_destroy(ch);
+      pgo_graph_free(cg);
+      pgo_destroy(h);
+      throw std::invalid_argument("InitializeHierarchical: information = true carries residual block weights 0 and 1 only");
     }
     if (st == PGO_OK) st = pgo_solve(ch, &cs->s);
     std::vector<double> X;
@@ -505,10 +525,11 @@ struct SolverAccess {
 
 inline void Solve(const Solver::Options& opt, Problem* problem, Solver::Summary* summary) { SolverAccess::Solve(opt, problem, summary); }
 // the parameter blocks moved, in place, to the prolonged solution of the problem's coarse graph at `stride` (pgo_coarsen ->
-// solve -> pgo_prolong); call Solve next.  coarse_summary (or nullptr) receives the coarse solve's summary
+// solve -> pgo_prolong); call Solve next.  coarse_summary (or nullptr) receives the coarse solve's summary.  information: the
+// coarse graph carries propagated information matrices (pgo_coarsen_info) and is solved with info_weighting = 1
 inline void InitializeHierarchical(Problem* problem, int stride, const Solver::Options& opt = Solver::Options(),
-                                   Solver::Summary* coarse_summary = nullptr) {
-  SolverAccess::InitializeHierarchical(opt, problem, stride, coarse_summary);
+                                   Solver::Summary* coarse_summary = nullptr, bool information = false) {
+  SolverAccess::InitializeHierarchical(opt, problem, stride, coarse_summary, information);
 }
 // Solve with graduated non-convexity: the parameter blocks end at the final solve's poses, summary->weights at the weights
 inline void SolveGnc(const Solver::Options& opt, const GncOptions& gnc, Problem* problem, GncSummary* summary) {
