@@ -218,28 +218,14 @@ void pgo_destroy(pgo_t* h) { delete h; }
 int pgo_set_poses(pgo_t* h, const double* poses) {
   if (!h || !poses) return fail(PGO_ERR_INVALID_ARG, "pgo_set_poses: null");
   HIPC(hipSetDevice(h->device));
-  std::vector<double> tmp;
-  if (!h->perm.empty()) {
-    h->to_internal(poses, &tmp, 3);
-    poses = tmp.data();
-  }
-  HIPC(hipMemcpyAsync(h->poses, poses, (size_t)3 * h->S.n_poses * sizeof(double), hipMemcpyHostToDevice, h->stream));
   h->solve_is_stale();
-  return h->sync();
+  return h->upload_pose_vector(h->poses, poses);
 }
 
 int pgo_get_poses(pgo_t* h, double* out) {
   if (!h || !out) return fail(PGO_ERR_INVALID_ARG, "pgo_get_poses: null");
   HIPC(hipSetDevice(h->device));
-  if (h->perm.empty()) {
-    HIPC(hipMemcpyAsync(out, h->poses, (size_t)3 * h->S.n_poses * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    return h->sync();
-  }
-  std::vector<double> tmp((size_t)3 * h->S.n_poses);
-  HIPC(hipMemcpyAsync(tmp.data(), h->poses, tmp.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  PGOC(h->sync());
-  h->to_caller(tmp, out, 3);
-  return PGO_OK;
+  return h->download_pose_vector(out, h->poses);
 }
 
 int pgo_get_switches(pgo_t* h, double* switches, double* js_out) {
@@ -273,14 +259,7 @@ int pgo_eval(pgo_t* h, const double* poses_or_null, int apply_loss, double* cost
   if (want_jac && h->comm && h->comm->world > 1) return fail(PGO_ERR_UNSUPPORTED, "pgo_eval: r/J outputs need world == 1");
   const double* x = h->poses;
   if (poses_or_null) {
-    std::vector<double> tmp;
-    const double* src = poses_or_null;
-    if (!h->perm.empty()) {
-      h->to_internal(poses_or_null, &tmp, 3);
-      src = tmp.data();
-    }
-    HIPC(hipMemcpyAsync(h->cand, src, (size_t)3 * h->S.n_poses * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    PGOC(h->sync());  // tmp dies with this scope
+    PGOC(h->upload_pose_vector(h->cand, poses_or_null));
     x = h->cand;
   }
   if (want_jac) h->solve_is_stale();  // the record buffer is about to be overwritten
@@ -343,15 +322,8 @@ int pgo_edge_chi2(pgo_t* h, const double* poses_or_null, double* chi2_out) {
     PGOC(h->upload(h->e_orig, h->S.orig_edge));
   }
   const double* x = h->poses;
-  std::vector<double> tmp;
   if (poses_or_null) {
-    const double* src = poses_or_null;
-    if (!h->perm.empty()) {
-      h->to_internal(poses_or_null, &tmp, 3);
-      src = tmp.data();
-    }
-    HIPC(hipMemcpyAsync(h->cand, src, (size_t)3 * h->S.n_poses * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    PGOC(h->sync());
+    PGOC(h->upload_pose_vector(h->cand, poses_or_null));
     x = h->cand;
   }
   HIPC(hipMemsetAsync(h->chi2_buf, 0, (size_t)E * sizeof(double), h->stream));
@@ -496,9 +468,7 @@ int pgo_debug_normal_eq(pgo_t* h, double* g_out, double* hdiag_out) {
   if (h->comm && h->comm->world > 1) return fail(PGO_ERR_UNSUPPORTED, "world == 1 only");
   HIPC(hipSetDevice(h->device));
   h->lm_active = false;
-  hipLaunchKernelGGL(dev::k_jacobi_scale<>, dim3(h->plan.own.g_rows), dim3(dev::WG), 0, h->stream, h->hd, h->S.n_loc, h->S.lo,
-                     h->fixed_internal, 0, h->scale, (const uint8_t*)h->fixed_mask);
-  PGOC(h->check_launch("k_jacobi_scale"));
+  PGOC(h->launch_jacobi_scale(0));
   int st = h->linearize(false);
   h->lin_valid = false;
   PGOC(st);
@@ -529,66 +499,28 @@ int pgo_debug_spmv(pgo_t* h, const double* x, double* yout) {
   if (!h || !x || !yout) return fail(PGO_ERR_INVALID_ARG, "pgo_debug_spmv: null");
   if (h->comm && h->comm->world > 1) return fail(PGO_ERR_UNSUPPORTED, "world == 1 only");
   HIPC(hipSetDevice(h->device));
-  const int64_t N = h->S.n_poses;
-  std::vector<double> tmp;
-  const double* src = x;
-  if (!h->perm.empty()) {
-    h->to_internal(x, &tmp, 3);
-    src = tmp.data();
-  }
-  HIPC(hipMemcpyAsync(h->y, src, (size_t)3 * N * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(dev::k_scatter_owned<>, dim3(h->plan.own.g_flat), dim3(dev::WG), 0, h->stream, h->S.n_loc, h->S.lo, h->y, h->p_full);
+  PGOC(h->upload_pose_vector(h->y, x));
+  PGOC(h->scatter_owned(h->y));
   PGOC(h->spmv_enqueue(h->p_full, h->ap, h->part[0], 0, nullptr));
-  if (h->perm.empty()) {
-    HIPC(hipMemcpyAsync(yout, h->ap, (size_t)3 * N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    return h->sync();
-  }
-  std::vector<double> ytmp((size_t)3 * N);
-  HIPC(hipMemcpyAsync(ytmp.data(), h->ap, ytmp.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  PGOC(h->sync());
-  h->to_caller(ytmp, yout, 3);
-  return PGO_OK;
+  return h->download_pose_vector(yout, h->ap);
 }
 
-// The LM diagonal for the current radius and the preconditioner on the current linearisation, as the next LM iteration sets
-// them up (after an accepted step H is new and the factors are not; after a rejected one the radius changed).  Every buffer
-// written here is rewritten from H and the radius by the next iteration's prepare_system() before it is read: a solve is
-// not affected.
-static int prepare_for_debug(pgo_handle* h) {
-  PGOC(h->prepare_system());
-  if (h->direct()) PGOC(h->prepare_preconditioner());   // (a handle on the direct solve does not factorise it per LM iteration)
-  return PGO_OK;
-}
-
+// The debug / bench hooks below set up the LM diagonal for the current radius and the preconditioner on the current
+// linearisation, as the next LM iteration does (after an accepted step H is new and the factors are not; after a rejected one the
+// radius changed) -- the preconditioner also on a handle on the direct solve, which does not factorise it per LM iteration:
+// prepare_system(radius, true).  Every buffer written there is rewritten from H and the radius by the next iteration's
+// prepare_system() before it is read: a solve is not affected.
 int pgo_debug_system_spmv(pgo_t* h, const double* x, double* yout, double* d2_out) {
   if (!h || !x || !yout) return fail(PGO_ERR_INVALID_ARG, "pgo_debug_system_spmv: null");
   if (h->comm && h->comm->world > 1) return fail(PGO_ERR_UNSUPPORTED, "world == 1 only");
   if (!h->lin_valid) return fail(PGO_ERR_INVALID_ARG, "pgo_debug_system_spmv: call pgo_lm_begin first");
   HIPC(hipSetDevice(h->device));
-  PGOC(prepare_for_debug(h));
-  const int64_t N = h->S.n_poses;
-  std::vector<double> tmp;
-  const double* src = x;
-  if (!h->perm.empty()) {
-    h->to_internal(x, &tmp, 3);
-    src = tmp.data();
-  }
-  HIPC(hipMemcpyAsync(h->ap, src, (size_t)3 * N * sizeof(double), hipMemcpyHostToDevice, h->stream));   // ap: scratch input
-  hipLaunchKernelGGL(dev::k_scatter_owned<>, dim3(h->plan.own.g_flat), dim3(dev::WG), 0, h->stream, h->S.n_loc, h->S.lo, (const double*)h->ap, h->p_full);
-  PGOC(h->check_launch("k_scatter_owned"));
+  PGOC(h->prepare_system(h->tr.radius, true));
+  PGOC(h->upload_pose_vector(h->ap, x));   // ap: scratch input
+  PGOC(h->scatter_owned(h->ap));
   PGOC(h->spmv_enqueue(h->p_full, h->ap, h->part[0], 1, nullptr));
-  std::vector<double> ytmp((size_t)3 * N), dtmp(d2_out ? (size_t)3 * N : 0);
-  HIPC(hipMemcpyAsync(ytmp.data(), h->ap, ytmp.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (d2_out) HIPC(hipMemcpyAsync(dtmp.data(), h->d2, dtmp.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  PGOC(h->sync());
-  if (h->perm.empty()) {
-    memcpy(yout, ytmp.data(), ytmp.size() * sizeof(double));
-    if (d2_out) memcpy(d2_out, dtmp.data(), dtmp.size() * sizeof(double));
-  } else {
-    h->to_caller(ytmp, yout, 3);
-    if (d2_out) h->to_caller(dtmp, d2_out, 3);
-  }
-  return PGO_OK;
+  PGOC(h->download_pose_vector(yout, h->ap));
+  return d2_out ? h->download_pose_vector(d2_out, h->d2) : PGO_OK;
 }
 
 // z = M^-1 r with the preconditioner the next LM iteration applies (whatever family the handle resolved to), through the
@@ -599,50 +531,11 @@ int pgo_debug_precond(pgo_t* h, const double* r_in, double* z_out) {
   if (h->comm && h->comm->world > 1 && !h->co_multi()) return fail(PGO_ERR_UNSUPPORTED, "world == 1 only (several ranks: with pcg_coarse_poses > 0)");
   if (!h->lin_valid || h->iter < 1) return fail(PGO_ERR_INVALID_ARG, "pgo_debug_precond: run at least one LM iteration first");
   HIPC(hipSetDevice(h->device));
-  const int64_t N = h->S.n_poses, lo = h->S.lo, NL = h->S.n_loc;
-  std::vector<double> tmp;
-  const double* src = r_in;
-  if (!h->perm.empty()) {
-    h->to_internal(r_in, &tmp, 3);
-    src = tmp.data();
-  }
-  if (NL > 0)   // ap: scratch input (the owned rows)
-    HIPC(hipMemcpyAsync(h->ap, src + 3 * lo, (size_t)3 * NL * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  PGOC(prepare_for_debug(h));
-  dev::CgVec V = h->cg_vec();
-  if (h->plan.all.chain_len) {
-    h->launch_cg_init_chain(h->ap, h->part[0], h->part[1]);
-  } else if (h->plan.own.grp_B > 1) {
-    dev::GroupPre GP;
-    GP.ginv = h->ginv;
-    GP.B = h->plan.own.grp_B;
-    GP.nb = h->plan.own.grp_nb;
-    GP.nb_pad = h->plan.own.grp_pad;
-    GP.n_groups = h->plan.own.n_groups;
-    hipLaunchKernelGGL(dev::k_cg_init_g<>, dim3(h->plan.own.g_grp), dim3(dev::WG), 0, h->stream, V, GP, (const double*)h->ap, h->part[0], h->part[1]);
-  } else {
-    hipLaunchKernelGGL(dev::k_cg_init<>, dim3(h->plan.own.g_vec), dim3(dev::WG), 0, h->stream, V, (const double*)h->ap, h->part[0], h->part[1]);
-  }
-  PGOC(h->check_launch("k_cg_init (debug)"));
-  if (h->coarse_on() && h->co_multi()) {   // several ranks: r_c through the all-reduce, the replicated coarse solve, the own rows of P e_c
-    PGOC(h->coarse_restrict_reduce(h->part[0], 1, h->part[1], 1, nullptr));
-    PGOC(h->coarse_solve(h->co_dotp, nullptr));
-    hipLaunchKernelGGL(dev::k_coarse_prolong_m<>, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((NL + 255) / 256, 512))), dim3(256), 0,
-                       h->stream, (int)NL, (int)lo, h->CO().co_agg, (const double*)h->co_pb, (int64_t)N, (const double*)h->co_ec, h->z, (double*)nullptr,
-                       (const int32_t*)h->co_ok);
-    PGOC(h->check_launch("k_coarse_prolong_m"));
-  } else if (h->coarse_on()) {   // the second level's share of z
-    PGOC(h->coarse_solve(h->part[3], nullptr));
-    hipLaunchKernelGGL(dev::k_coarse_prolong<>, dim3((unsigned)std::min<int64_t>((h->S.n_loc + 255) / 256, 512)), dim3(256), 0, h->stream,
-                       (int)h->S.n_loc, h->CO().co_agg, (const double*)h->co_pb, (const double*)h->co_ec, h->z, (double*)nullptr, (const int32_t*)h->co_ok);
-    PGOC(h->check_launch("k_coarse_prolong"));
-  }
-  std::vector<double> ztmp((size_t)3 * N, 0.0);   // (several ranks: the peers' rows stay 0)
-  if (NL > 0) HIPC(hipMemcpyAsync(ztmp.data() + 3 * lo, h->z, (size_t)3 * NL * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  PGOC(h->sync());
-  if (h->perm.empty()) memcpy(z_out, ztmp.data(), ztmp.size() * sizeof(double));
-  else h->to_caller(ztmp, z_out, 3);
-  return PGO_OK;
+  PGOC(h->upload_pose_vector(h->ap, r_in, h->S.lo, h->S.n_loc));   // ap: scratch input (the owned rows)
+  PGOC(h->prepare_system(h->tr.radius, true));
+  // (several ranks: r_c through the all-reduce, the replicated coarse solve, the own rows of P e_c)
+  PGOC(h->precondition(h->ap, nullptr, nullptr, h->co_multi() ? h->co_dotp : h->part[3]));
+  return h->download_pose_vector(z_out, h->z, h->S.lo, h->S.n_loc);   // (several ranks: the peers' rows stay 0)
 }
 
 // y = (H + D'D)^-1 b through direct_enqueue(), the launch sequence an LM iteration on the direct solve runs (eagerly: a
@@ -669,7 +562,7 @@ int pgo_debug_direct_solve(pgo_t* h, const double* b_in, int32_t refine_steps, d
     HIPC(hipMemcpyAsync(save + off_pf, h->p_full, npf * sizeof(double), d2d, h->stream));
     HIPC(hipMemcpyAsync(save + off_scal, h->scal, N_SCAL * sizeof(double), d2d, h->stream));
     HIPC(hipMemcpyAsync(save + off_b, b_in, n3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    PGOC(h->prepare_system());
+    PGOC(h->prepare_system(h->tr.radius));
     PGOC(h->direct_enqueue(save + off_b, refine_steps < 0 ? h->plan.dl.dl_refine : refine_steps));
     HIPC(hipMemcpyAsync(y_out, h->y, n3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPC(hipMemcpyAsync(h->y, save, n3 * sizeof(double), d2d, h->stream));
@@ -748,30 +641,13 @@ int pgo_bench_precond(pgo_t* h, int reps, pgo_kernel_stats* out) {
   if (!h || !out || reps < 1) return fail(PGO_ERR_INVALID_ARG, "pgo_bench_precond: bad argument");
   if (!h->lin_valid || h->iter < 1) return fail(PGO_ERR_INVALID_ARG, "pgo_bench_precond: run at least one LM iteration first");
   HIPC(hipSetDevice(h->device));
-  PGOC(prepare_for_debug(h));
-  dev::CgVec V = h->cg_vec();
+  PGOC(h->prepare_system(h->tr.radius, true));
   double ms = 0;
   const double nl = (double)h->S.n_loc;
-  if (h->plan.all.chain_len) {
-    PGOC(time_launches(h, reps, [&] { h->launch_cg_init_chain(h->gs, h->part[0], h->part[1]); }, &ms));
-    out->algorithmic_bytes = (120.0 + 24.0 + 4 * 24.0) * nl;   // W, S^-1 planes + b read; y, r, z, p written
-  } else if (h->plan.own.grp_B > 1) {
-    dev::GroupPre GP;
-    GP.ginv = h->ginv;
-    GP.B = h->plan.own.grp_B;
-    GP.nb = h->plan.own.grp_nb;
-    GP.nb_pad = h->plan.own.grp_pad;
-    GP.n_groups = h->plan.own.n_groups;
-    PGOC(time_launches(h, reps, [&] {
-      hipLaunchKernelGGL(dev::k_cg_init_g<>, dim3(h->plan.own.g_grp), dim3(dev::WG), 0, h->stream, V, GP, (const double*)h->gs, h->part[0], h->part[1]);
-    }, &ms));
-    out->algorithmic_bytes = (8.0 * 3 * h->plan.own.grp_nb + 24.0 + 4 * 24.0) * nl;
-  } else {
-    PGOC(time_launches(h, reps, [&] {
-      hipLaunchKernelGGL(dev::k_cg_init<>, dim3(h->plan.own.g_vec), dim3(dev::WG), 0, h->stream, V, (const double*)h->gs, h->part[0], h->part[1]);
-    }, &ms));
-    out->algorithmic_bytes = (48.0 + 24.0 + 4 * 24.0) * nl;
-  }
+  PGOC(time_launches(h, reps, [&] { (void)h->launch_cg_init(h->gs, nullptr, h->part[0], h->part[1]); }, &ms));
+  if (h->plan.all.chain_len) out->algorithmic_bytes = (120.0 + 24.0 + 4 * 24.0) * nl;   // W, S^-1 planes + b read; y, r, z, p written
+  else if (h->plan.own.grp_B > 1) out->algorithmic_bytes = (8.0 * 3 * h->plan.own.grp_nb + 24.0 + 4 * 24.0) * nl;
+  else out->algorithmic_bytes = (48.0 + 24.0 + 4 * 24.0) * nl;
   out->ms_avg = ms;
   out->units = h->S.n_loc;
   return PGO_OK;

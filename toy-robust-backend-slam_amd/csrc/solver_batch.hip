@@ -52,15 +52,11 @@ int pgo_batch::begin() {
   const pgo_options& o = H.opt;
   for (State& z : st) z = State();
   // iteration 0: unit scales -> column norms -> Jacobi scaling (per column, so per problem by construction)
-  hipLaunchKernelGGL(dev::k_jacobi_scale<>, dim3(H.plan.own.g_rows), dim3(dev::WG), 0, H.stream, H.hd, H.S.n_loc, H.S.lo, -1, 0, H.scale,
-                     (const uint8_t*)H.fixed_mask);
-  PGOC(H.check_launch("k_jacobi_scale"));
+  PGOC(H.launch_jacobi_scale(0));
   PGOC(H.eval_enqueue(H.poses, nullptr, 1, true, 0));
   PGOC(H.assemble_enqueue());
   if (o.jacobi_scaling) {
-    hipLaunchKernelGGL(dev::k_jacobi_scale<>, dim3(H.plan.own.g_rows), dim3(dev::WG), 0, H.stream, H.hd, H.S.n_loc, H.S.lo, -1, 1, H.scale,
-                       (const uint8_t*)H.fixed_mask);
-    PGOC(H.check_launch("k_jacobi_scale"));
+    PGOC(H.launch_jacobi_scale(1));
     PGOC(H.assemble_enqueue());
   }
   PGOC(reduce(true, true, H.poses));
@@ -106,7 +102,7 @@ int pgo_batch::iterate(bool* all_done) {
   if (n_active == 0) return PGO_OK;
   HIPC(hipMemcpyAsync(d_prob, h_prob.data(), (size_t)n * sizeof(dev::SoloProb), hipMemcpyHostToDevice, H.stream));
   HIPC(hipMemcpyAsync(H.prob_radius, h_radius.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, H.stream));
-  PGOC(H.prepare_system());
+  PGOC(H.prepare_system(0.0));   // (not read: k_prepare takes every problem's radius from prob_radius, uploaded above)
   dev::SoloArgs A;
   A.A = H.spmv_args(H.p_full, H.ap, H.part[0], 1, nullptr);
   A.V = H.cg_vec();

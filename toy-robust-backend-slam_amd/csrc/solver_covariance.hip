@@ -39,38 +39,6 @@ struct DevScratch {   // buffers of one call, freed on every return path
   }
 };
 
-// z = M^-1 b with the handle's preconditioner, through the PCG start-up kernel the LM loop runs (it also overwrites the LM
-// loop's per-solve vectors y, r and the gather vector, which every PCG solve initialises afresh)
-int precond_column(pgo_handle* h, const double* b, double* zc) {
-  double* z_saved = h->z;
-  h->z = zc;
-  const dev::CgVec V = h->cg_vec();
-  if (h->plan.all.chain_len) {
-    h->launch_cg_init_chain(b, h->part[0], h->part[1]);
-  } else if (h->plan.own.grp_B > 1) {
-    dev::GroupPre GP;
-    GP.ginv = h->ginv;
-    GP.B = h->plan.own.grp_B;
-    GP.nb = h->plan.own.grp_nb;
-    GP.nb_pad = h->plan.own.grp_pad;
-    GP.n_groups = h->plan.own.n_groups;
-    hipLaunchKernelGGL(dev::k_cg_init_g<>, dim3(h->plan.own.g_grp), dim3(dev::WG), 0, h->stream, V, GP, b, h->part[0], h->part[1]);
-  } else {
-    hipLaunchKernelGGL(dev::k_cg_init<>, dim3(h->plan.own.g_vec), dim3(dev::WG), 0, h->stream, V, b, h->part[0], h->part[1]);
-  }
-  int st = h->check_launch("k_cg_init (covariance)");
-  if (st == PGO_OK && h->coarse_on()) {   // the second level's share: restriction of r (= b), coarse solve, prolongation into z
-    st = h->coarse_solve(h->part[3], nullptr);
-    if (st == PGO_OK) {
-      hipLaunchKernelGGL(dev::k_coarse_prolong<>, dim3((unsigned)std::min<int64_t>((h->S.n_loc + 255) / 256, 512)), dim3(256), 0, h->stream,
-                         (int)h->S.n_loc, h->CO().co_agg, (const double*)h->co_pb, (const double*)h->co_ec, zc, (double*)nullptr, (const int32_t*)h->co_ok);
-      st = h->check_launch("k_coarse_prolong (covariance)");
-    }
-  }
-  h->z = z_saved;
-  return st;
-}
-
 int spmm(pgo_handle* h, int m, int64_t ld, const double* p, double* y, double* part, int g) {
   for (int c0 = 0; c0 < m; c0 += dev::COV_MC) {
     dev::SpmmArgs A;
@@ -119,32 +87,20 @@ struct CoarseOn {
 // next iteration from unchanged inputs (prepare_system; METHOD 2: refresh_switch_system), so its results do not change.
 int setup_system(pgo_handle* h, bool with_preconditioner) {
   if (!h->lin_valid) {   // (not for METHOD 2: refused earlier) Jacobi scales and J'J at the current poses, as pgo_lm_begin
-    hipLaunchKernelGGL(dev::k_jacobi_scale<>, dim3(h->plan.own.g_rows), dim3(dev::WG), 0, h->stream, h->hd, h->S.n_loc, h->S.lo, h->fixed_internal, 0, h->scale,
-                       (const uint8_t*)h->fixed_mask);
-    PGOC(h->check_launch("k_jacobi_scale"));
+    PGOC(h->launch_jacobi_scale(0));
     PGOC(h->linearize(false));
     if (h->opt.jacobi_scaling) {
-      hipLaunchKernelGGL(dev::k_jacobi_scale<>, dim3(h->plan.own.g_rows), dim3(dev::WG), 0, h->stream, h->hd, h->S.n_loc, h->S.lo, h->fixed_internal, 1,
-                         h->scale, (const uint8_t*)h->fixed_mask);
-      PGOC(h->check_launch("k_jacobi_scale"));
+      PGOC(h->launch_jacobi_scale(1));
       PGOC(h->linearize(true));
     }
   }
-  const double radius_saved = h->tr.radius;
-  h->tr.radius = std::numeric_limits<double>::infinity();
-  int st = PGO_OK;
+  const double undamped = std::numeric_limits<double>::infinity();
   if (h->has_sw) {   // switches eliminated per edge with zero damping: the pose marginal of the joint system
-    const int g_sw = std::min(std::max(1, (h->S.n_edges_local + dev::WG - 1) / dev::WG), 1024);
-    hipLaunchKernelGGL(dev::k_switch_prepare<>, dim3(g_sw), dim3(dev::WG), 0, h->stream, h->switch_arrays(), (const double*)h->jr, h->tr.radius,
-                       h->opt.min_lm_diagonal, h->opt.max_lm_diagonal, h->part[2], h->part[3]);
-    st = h->check_launch("k_switch_prepare (covariance)");
-    if (st == PGO_OK) st = h->assemble_enqueue();
     h->sw_fresh = false;   // the next LM iteration re-assembles for its radius (refresh_switch_system)
+    PGOC(h->switch_prepare(undamped));
+    PGOC(h->assemble_enqueue());
   }
-  if (st == PGO_OK) st = h->prepare_system();
-  if (st == PGO_OK && h->direct() && with_preconditioner) st = h->prepare_preconditioner();   // (a handle on the direct solve does not set it up per iteration)
-  h->tr.radius = radius_saved;
-  return st;
+  return h->prepare_system(undamped, with_preconditioner);   // (a handle on the direct solve does not set the preconditioner up per iteration)
 }
 
 // the right-hand sides of one pass: unit vectors S e_rows[c] (pgo_pose_covariance), or with rec != nullptr the sparse
@@ -332,10 +288,12 @@ struct Session {
     if (direct) return pass_direct(m, B, who);
     const int every = std::max(1, h->opt.pcg_check_every);
     // start: X = 0, R = B, Z = M^-1 R, P = Z
-    std::vector<uint8_t> hdone((size_t)m, 0);   // columns known stopped at the latest host check: no preconditioner apply
+    // columns known stopped at the latest host check: no preconditioner apply.  (The apply is the LM loop's start-up kernel: it
+    // also overwrites the loop's per-solve vectors y, r and the gather vector, which every PCG solve initialises afresh.)
+    std::vector<uint8_t> hdone((size_t)m, 0);
     auto precond_open = [&]() -> int {
       for (int c = 0; c < m; ++c)
-        if (!hdone[c]) PGOC(precond_column(h, R + c * ld, Z + c * ld));
+        if (!hdone[c]) PGOC(h->precondition(R + c * ld, Z + c * ld, nullptr, h->part[3]));
       return PGO_OK;
     };
     PGOC(launch_rhs(m, B));

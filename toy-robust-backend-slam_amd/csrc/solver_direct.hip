@@ -190,8 +190,7 @@ int pgo_handle::direct_enqueue(const double* rhs, int refine) {
                      (const double*)dl_Z, plan.dl.dl_ld, K, 3 * n, y, 0);
   PGOC(check_launch("k_dlr_combine"));
   auto residual_product = [&]() -> int {  // ap = (H + D'D) y
-    hipLaunchKernelGGL(dev::k_scatter_owned<>, dim3(plan.own.g_flat), dim3(dev::WG), 0, stream, S.n_loc, S.lo, y, p_full);
-    PGOC(check_launch("k_scatter_owned"));
+    PGOC(scatter_owned(y));
     return spmv_enqueue(p_full, ap, part[0], 1, nullptr);
   };
   for (int it = 0; it < refine; ++it) {

@@ -5,6 +5,8 @@
 //   solver_lm.hip       Ceres' TrustRegionMinimizer + LevenbergMarquardtStrategy policy (lm_begin, lm_iteration, ...)
 //   solver_pcg.hip      block-Jacobi PCG, its preconditioners' set-up, the coarse level
 //   solver_direct.hip   the direct chain + low-rank solve
+//   solver_launch.hip   the launch sequences several units need, each stated once: K1, K2, K3, the reductions, the halo exchange,
+//                       z = M^-1 b, the Jacobi scales, the switch elimination, pose vectors in and out
 //   solver_batch.hip    pgo_batch: many independent problems in one handle
 //   solver_abi.hip      the [gpu] part of the C-ABI, test hooks, debug / bench entry points
 //   solver_window.hip   pgo_window_solve: many tiny windows of the graph, one workgroup each (window.hip.h)
@@ -190,16 +192,12 @@ struct pgo_handle {
   // internal pose numbering (opt.pose_ordering): perm[i] = internal position of the caller's pose i; empty = identity
   std::vector<int32_t> perm;
   int fixed_internal = -1;  // opt.fixed_pose in the internal numbering
-  // host <-> device pose-vector helpers honouring the permutation (n_cols doubles per pose)
-  void to_internal(const double* in, std::vector<double>* out, int n_cols) const {
-    const int64_t N = S.n_poses;
-    out->resize((size_t)N * n_cols);
-    for (int64_t i = 0; i < N; ++i) memcpy(&(*out)[(size_t)perm[i] * n_cols], in + i * n_cols, (size_t)n_cols * sizeof(double));
-  }
-  void to_caller(const std::vector<double>& in, double* out, int n_cols) const {
-    const int64_t N = S.n_poses;
-    for (int64_t i = 0; i < N; ++i) memcpy(out + i * n_cols, &in[(size_t)perm[i] * n_cols], (size_t)n_cols * sizeof(double));
-  }
+  // A caller-ordered pose vector (3 doubles per pose) to the device in the internal numbering, and back.  dst / src are the
+  // device rows [row0, row0 + rows) (rows < 0: all poses).  With a permutation the vector is staged on the host; the identity
+  // ordering copies straight from / to the caller's memory.  Both synchronise the stream; download leaves 0 in the rows outside
+  // the range (the peers' rows of a sharded handle).
+  int upload_pose_vector(double* dst, const double* caller_src, int64_t row0 = 0, int64_t rows = -1);
+  int download_pose_vector(double* caller_dst, const double* src, int64_t row0 = 0, int64_t rows = -1);
   // captured slice of PCG iterations (world == 1)
   hipGraphExec_t cg_graph_exec = nullptr;
   int cg_graph_len = 0;
@@ -354,6 +352,8 @@ struct pgo_handle {
   // make the owned rows of the gather vector visible where the peers need them: either everything
   // (all-gather) or only the rows their off-diagonal blocks reference (halo exchange)
   int share_gather_vector(double* full);
+  int pack_halo_rows(const double* full);                // the halo exchange's two ends (k_pack_rows / k_unpack_rows and their grid)
+  int unpack_halo_rows(double* full, hipStream_t on);
 
   // ---- K1
   dev::EdgeArgs edge_args(const double* x, const double* sw_vals, int apply_loss) const {
@@ -511,14 +511,14 @@ struct pgo_handle {
   // *n_part = number of dot partials written to dot_part.
   int spmv_with_halo(double* full, double* yout, double* dot_part, const int32_t* done, int* n_part);
 
-  dev::CgVec cg_vec() const {
+  dev::CgVec cg_vec(double* z_out = nullptr) const {   // z_out: where z = M^-1 r goes instead of the handle's z
     dev::CgVec V;
     V.n_loc = S.n_loc;
     V.lo = S.lo;
     V.minv = minv;
     V.y = y;
     V.r = r;
-    V.z = z;
+    V.z = z_out ? z_out : z;
     V.ap = ap;
     V.p = p_full;
     V.st = st;
@@ -535,10 +535,33 @@ struct pgo_handle {
     CP.n_pad = plan.own.chain_pad;
     return CP;
   }
-  // PCG start-up / first update kernel with the chain preconditioner
-  void launch_cg_init_chain(const double* b, double* part_rz, double* part_bb);
+  dev::GroupPre group_pre() const {
+    dev::GroupPre GP;
+    GP.ginv = ginv;
+    GP.B = plan.own.grp_B;
+    GP.nb = plan.own.grp_nb;
+    GP.nb_pad = plan.own.grp_pad;
+    GP.n_groups = plan.own.n_groups;
+    return GP;
+  }
+  // ---- launched once (solver_launch.hip)
+  // z = M^-1 b with the handle's preconditioner.  First level: the PCG start-up kernel of the handle's family (chain, pose
+  // groups, 3x3 blocks); it also starts y, r and the gather vector and writes cg_init_parts() partials of r.z and b.b.
+  int cg_init_parts() const { return plan.all.chain_len > 0 ? plan.own.g_chain : (plan.own.grp_B > 1 ? plan.own.g_grp : plan.own.g_vec); }
+  int launch_cg_init(const double* b, double* z_out, double* part_rz, double* part_bb);
+  // the coarse level's share P e_c added to z (and to the gather vector p, unless null), one rank or several
+  int launch_coarse_prolong(double* z_inout, double* p_or_null);
+  // both levels: launch_cg_init into part[0] / part[1], then (coarse_on()) coarse_solve with its partials of r_c . e_c in
+  // dot_part, then the prolongation.  Several ranks: r_c comes with the all-reduce of the start-up sums (coarse_restrict_reduce).
+  int precondition(const double* b, double* z_out, double* p_or_null, double* dot_part);
   void launch_cg_sr_chain(const dev::CgVec& V, double* part_gamma, double* part_rr);
   void launch_cg_update1_chain(const dev::CgVec& V, int par, const double* pap, int n_pap, double* part_rz, double* part_rr);
+  // Jacobi scales from the diagonal of J'J: pass 0 writes unit scales (0 on the constant poses), pass 1 the column norms
+  int launch_jacobi_scale(int pass);
+  int scatter_owned(const double* src);   // the owned rows of src into the gather vector p_full
+  // METHOD 2: the switches' elimination coefficients for `radius` (partials: part[2] max |g_s|, part[3] sum s^2; g_sw() each)
+  int g_sw() const { return std::min(std::max(1, (S.n_edges_local + dev::WG - 1) / dev::WG), 1024); }
+  int switch_prepare(double radius);
 
   // window solves (pgo_window_solve, solver_window.hip): the lists of a call are resolved on the host into win_host, uploaded
   // into win_in; win_work holds the per-edge records and the outputs.  Both buffers are grown on demand and kept.
@@ -617,7 +640,9 @@ struct pgo_handle {
   int lm_begin();
   int lm_iteration(bool* stop);
   int lm_iteration_tail(bool* stop, pgo_iter_record& R, double it0, double t0, int k_it, double rel);
-  int prepare_system();
+  // LM diagonal for `radius` (a batched handle: per problem, prob_radius) + the PCG preconditioner's set-up -- which a handle on
+  // the direct solve skips unless it is asked for
+  int prepare_system(double radius, bool preconditioner_also_on_direct = false);
   int pcg(int* iters, double* rel);
   int32_t direct_chain_lists(std::vector<int32_t>* chain, std::vector<int32_t>* lr, std::vector<int32_t>* va, std::vector<int32_t>* vb) const;
   int direct_build();   // the buffers and lists of the direct solve the plan sized (create, or lm_iteration's take-over)

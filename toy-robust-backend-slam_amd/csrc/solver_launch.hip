@@ -1,6 +1,7 @@
 // The handle's launch helpers for the kernels several translation units need (K1, K2, K3, the reductions to scalars, the
-// halo exchange, the chain-preconditioned PCG kernels): defined ONCE here, so that the other units do not carry copies of
-// those kernels.
+// halo exchange, the preconditioner apply z = M^-1 b of both levels, the Jacobi scales, METHOD 2's switch elimination): defined
+// ONCE here, so that the other units do not carry copies of those kernels -- and so that a test hook runs the lines the LM loop
+// runs.  The caller <-> internal numbering of a pose vector is stated here too.
 #include "solver_handle.hip.h"
 
 int pgo_handle::reduce_to_scal(std::initializer_list<PartRef> parts, int first, bool allreduce_max) {
@@ -33,21 +34,29 @@ int pgo_handle::reduce_parts(std::initializer_list<PartRef> parts, double* out, 
   return PGO_OK;
 }
 
+// the halo exchange's two ends: the rows the peers read, out of the gather vector into the send buffer, and the received rows into it
+static unsigned halo_rows_grid(int64_t n_rows) { return (unsigned)std::min<int64_t>((3 * n_rows + 255) / 256, 2048); }
+
+int pgo_handle::pack_halo_rows(const double* full) {
+  const int64_t ns = (int64_t)S.halo_send_row.size();
+  if (ns == 0) return PGO_OK;
+  hipLaunchKernelGGL(dev::k_pack_rows<>, dim3(halo_rows_grid(ns)), dim3(256), 0, stream, ns, (const int32_t*)halo_send_rows, full, halo_send_buf);
+  return check_launch("k_pack_rows");
+}
+
+int pgo_handle::unpack_halo_rows(double* full, hipStream_t on) {
+  const int64_t nr = (int64_t)S.halo_recv_row.size();
+  if (nr == 0) return PGO_OK;
+  hipLaunchKernelGGL(dev::k_unpack_rows<>, dim3(halo_rows_grid(nr)), dim3(256), 0, on, nr, (const int32_t*)halo_recv_rows, (const double*)halo_recv_buf, full);
+  return check_launch("k_unpack_rows");
+}
+
 int pgo_handle::share_gather_vector(double* full) {
   if (!multi_rank()) return PGO_OK;
   if (!plan.all.use_halo) return allgather(full, dev::PS);
-  const int64_t ns = (int64_t)S.halo_send_row.size(), nr = (int64_t)S.halo_recv_row.size();
-  if (ns > 0) {
-    hipLaunchKernelGGL(dev::k_pack_rows<>, dim3((unsigned)std::min<int64_t>((3 * ns + 255) / 256, 2048)), dim3(256), 0, stream, ns,
-                       (const int32_t*)halo_send_rows, (const double*)full, halo_send_buf);
-    PGOC(check_launch("k_pack_rows"));
-  }
+  PGOC(pack_halo_rows(full));
   PGOC(comm->exchange(halo_send_buf, halo_send_off3.data(), halo_recv_buf, halo_recv_off3.data(), stream));
-  if (nr > 0) {
-    hipLaunchKernelGGL(dev::k_unpack_rows<>, dim3((unsigned)std::min<int64_t>((3 * nr + 255) / 256, 2048)), dim3(256), 0, stream, nr,
-                       (const int32_t*)halo_recv_rows, (const double*)halo_recv_buf, full);
-    PGOC(check_launch("k_unpack_rows"));
-  }
+  PGOC(unpack_halo_rows(full, stream));
   return PGO_OK;
 }
 
@@ -109,12 +118,7 @@ int pgo_handle::spmv_with_halo(double* full, double* yout, double* dot_part, con
     *n_part = plan.own.g_spmv;
     return spmv_enqueue(full, yout, dot_part, 1, done);
   }
-  const int64_t ns = (int64_t)S.halo_send_row.size(), nr = (int64_t)S.halo_recv_row.size();
-  if (ns > 0) {
-    hipLaunchKernelGGL(dev::k_pack_rows<>, dim3((unsigned)std::min<int64_t>((3 * ns + 255) / 256, 2048)), dim3(256), 0, stream, ns,
-                       (const int32_t*)halo_send_rows, (const double*)full, halo_send_buf);
-    PGOC(check_launch("k_pack_rows"));
-  }
+  PGOC(pack_halo_rows(full));
   HIPC(hipEventRecord(ev_pack, stream));
   int used = 0;
   if (S.n_tiles() > 0) {  // enqueued before the exchange so that it also overlaps a host-blocking back-end
@@ -125,11 +129,7 @@ int pgo_handle::spmv_with_halo(double* full, double* yout, double* dot_part, con
   }
   HIPC(hipStreamWaitEvent(comm_stream, ev_pack, 0));
   PGOC(comm->exchange(halo_send_buf, halo_send_off3.data(), halo_recv_buf, halo_recv_off3.data(), comm_stream));
-  if (nr > 0) {
-    hipLaunchKernelGGL(dev::k_unpack_rows<>, dim3((unsigned)std::min<int64_t>((3 * nr + 255) / 256, 2048)), dim3(256), 0, comm_stream, nr,
-                       (const int32_t*)halo_recv_rows, (const double*)halo_recv_buf, full);
-    PGOC(check_launch("k_unpack_rows"));
-  }
+  PGOC(unpack_halo_rows(full, comm_stream));
   HIPC(hipEventRecord(ev_halo, comm_stream));
   HIPC(hipStreamWaitEvent(stream, ev_halo, 0));
   if (plan.own.n_rr > 0) {
@@ -153,27 +153,122 @@ int pgo_handle::spmv_with_halo(double* full, double* yout, double* dot_part, con
   return PGO_OK;
 }
 
-void pgo_handle::launch_cg_init_chain(const double* b, double* part_rz, double* part_bb) {
-  const dev::CgVec V = cg_vec();
-  const dev::ChainPre CP = chain_pre();
-  if (plan.all.chain_chunk == 2 && plan.own.chain_nw == 4) hipLaunchKernelGGL((dev::k_cg_init_cl<2, 4>), dim3(plan.own.g_chain), dim3(256), 0, stream, V, CP, plan.all.chain_steps, plan.own.chain_scan, b, part_rz, part_bb);
-  else if (plan.all.chain_chunk == 2) hipLaunchKernelGGL((dev::k_cg_init_cl<2, 1>), dim3(plan.own.g_chain), dim3(64), 0, stream, V, CP, plan.all.chain_steps, plan.own.chain_scan, b, part_rz, part_bb);
-  else if (plan.own.chain_nw == 4) hipLaunchKernelGGL((dev::k_cg_init_cl<4, 4>), dim3(plan.own.g_chain), dim3(256), 0, stream, V, CP, plan.all.chain_steps, plan.own.chain_scan, b, part_rz, part_bb);
-  else hipLaunchKernelGGL((dev::k_cg_init_cl<4, 1>), dim3(plan.own.g_chain), dim3(64), 0, stream, V, CP, plan.all.chain_steps, plan.own.chain_scan, b, part_rz, part_bb);
+
+// ---- the chain preconditioner's kernels: the (chain_chunk, chain_nw) instantiation the plan chose.  launch(chunk, waves) gets
+// both as integral constants; the workgroup is 64 x waves threads.
+template <class Launch>
+static void chain_dispatch(const pgo::Plan& plan, Launch&& launch) {
+  using std::integral_constant;
+  if (plan.all.chain_chunk == 2 && plan.own.chain_nw == 4) launch(integral_constant<int, 2>(), integral_constant<int, 4>());
+  else if (plan.all.chain_chunk == 2) launch(integral_constant<int, 2>(), integral_constant<int, 1>());
+  else if (plan.own.chain_nw == 4) launch(integral_constant<int, 4>(), integral_constant<int, 4>());
+  else launch(integral_constant<int, 4>(), integral_constant<int, 1>());
 }
 
 void pgo_handle::launch_cg_sr_chain(const dev::CgVec& V, double* part_gamma, double* part_rr) {
   const dev::ChainPre CP = chain_pre();
-  if (plan.all.chain_chunk == 2 && plan.own.chain_nw == 4) hipLaunchKernelGGL((dev::k_cg_sr_cl<2, 4>), dim3(plan.own.g_chain), dim3(256), 0, stream, V, CP, sr_s, plan.all.chain_steps, plan.own.chain_scan, part_gamma, part_rr);
-  else if (plan.all.chain_chunk == 2) hipLaunchKernelGGL((dev::k_cg_sr_cl<2, 1>), dim3(plan.own.g_chain), dim3(64), 0, stream, V, CP, sr_s, plan.all.chain_steps, plan.own.chain_scan, part_gamma, part_rr);
-  else if (plan.own.chain_nw == 4) hipLaunchKernelGGL((dev::k_cg_sr_cl<4, 4>), dim3(plan.own.g_chain), dim3(256), 0, stream, V, CP, sr_s, plan.all.chain_steps, plan.own.chain_scan, part_gamma, part_rr);
-  else hipLaunchKernelGGL((dev::k_cg_sr_cl<4, 1>), dim3(plan.own.g_chain), dim3(64), 0, stream, V, CP, sr_s, plan.all.chain_steps, plan.own.chain_scan, part_gamma, part_rr);
+  chain_dispatch(plan, [&](auto chunk, auto waves) {
+    hipLaunchKernelGGL((dev::k_cg_sr_cl<decltype(chunk)::value, decltype(waves)::value>), dim3(plan.own.g_chain), dim3(64 * decltype(waves)::value), 0, stream, V, CP,
+                       sr_s, plan.all.chain_steps, plan.own.chain_scan, part_gamma, part_rr);
+  });
 }
 
 void pgo_handle::launch_cg_update1_chain(const dev::CgVec& V, int par, const double* pap, int n_pap, double* part_rz, double* part_rr) {
   const dev::ChainPre CP = chain_pre();
-  if (plan.all.chain_chunk == 2 && plan.own.chain_nw == 4) hipLaunchKernelGGL((dev::k_cg_update1_cl<2, 4>), dim3(plan.own.g_chain), dim3(256), 0, stream, V, CP, plan.all.chain_steps, plan.own.chain_scan, par, pap, n_pap, part_rz, part_rr);
-  else if (plan.all.chain_chunk == 2) hipLaunchKernelGGL((dev::k_cg_update1_cl<2, 1>), dim3(plan.own.g_chain), dim3(64), 0, stream, V, CP, plan.all.chain_steps, plan.own.chain_scan, par, pap, n_pap, part_rz, part_rr);
-  else if (plan.own.chain_nw == 4) hipLaunchKernelGGL((dev::k_cg_update1_cl<4, 4>), dim3(plan.own.g_chain), dim3(256), 0, stream, V, CP, plan.all.chain_steps, plan.own.chain_scan, par, pap, n_pap, part_rz, part_rr);
-  else hipLaunchKernelGGL((dev::k_cg_update1_cl<4, 1>), dim3(plan.own.g_chain), dim3(64), 0, stream, V, CP, plan.all.chain_steps, plan.own.chain_scan, par, pap, n_pap, part_rz, part_rr);
+  chain_dispatch(plan, [&](auto chunk, auto waves) {
+    hipLaunchKernelGGL((dev::k_cg_update1_cl<decltype(chunk)::value, decltype(waves)::value>), dim3(plan.own.g_chain), dim3(64 * decltype(waves)::value), 0, stream, V,
+                       CP, plan.all.chain_steps, plan.own.chain_scan, par, pap, n_pap, part_rz, part_rr);
+  });
+}
+
+// ---- z = M^-1 b: the lines the LM loop's PCG, the covariance columns and the debug / bench hooks all run
+int pgo_handle::launch_cg_init(const double* b, double* z_out, double* part_rz, double* part_bb) {
+  const dev::CgVec V = cg_vec(z_out);
+  if (plan.all.chain_len > 0) {
+    const dev::ChainPre CP = chain_pre();
+    chain_dispatch(plan, [&](auto chunk, auto waves) {
+      hipLaunchKernelGGL((dev::k_cg_init_cl<decltype(chunk)::value, decltype(waves)::value>), dim3(plan.own.g_chain), dim3(64 * decltype(waves)::value), 0, stream, V,
+                         CP, plan.all.chain_steps, plan.own.chain_scan, b, part_rz, part_bb);
+    });
+  } else if (plan.own.grp_B > 1) {
+    hipLaunchKernelGGL(dev::k_cg_init_g<>, dim3(plan.own.g_grp), dim3(dev::WG), 0, stream, V, group_pre(), b, part_rz, part_bb);
+  } else {
+    hipLaunchKernelGGL(dev::k_cg_init<>, dim3(plan.own.g_vec), dim3(dev::WG), 0, stream, V, b, part_rz, part_bb);
+  }
+  return check_launch("k_cg_init");
+}
+
+int pgo_handle::launch_coarse_prolong(double* z_inout, double* p_or_null) {
+  const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((S.n_loc + 255) / 256, 512)));   // (at least one workgroup: a rank may own no rows)
+  if (co_multi()) {   // global aggregates and basis planes; the kernel finds the owned rows of p itself
+    hipLaunchKernelGGL(dev::k_coarse_prolong_m<>, grid, dim3(256), 0, stream, (int)S.n_loc, (int)S.lo, CO().co_agg, (const double*)co_pb, (int64_t)S.n_poses,
+                       (const double*)co_ec, z_inout, p_or_null, (const int32_t*)co_ok);
+    return check_launch("k_coarse_prolong_m");
+  }
+  hipLaunchKernelGGL(dev::k_coarse_prolong<>, grid, dim3(256), 0, stream, (int)S.n_loc, CO().co_agg, (const double*)co_pb, (const double*)co_ec, z_inout,
+                     p_or_null ? p_or_null + dev::PS * (int64_t)S.lo : (double*)nullptr, (const int32_t*)co_ok);
+  return check_launch("k_coarse_prolong");
+}
+
+int pgo_handle::precondition(const double* b, double* z_out, double* p_or_null, double* dot_part) {
+  PGOC(launch_cg_init(b, z_out, part[0], part[1]));
+  if (!coarse_on()) return PGO_OK;
+  if (co_multi()) PGOC(coarse_restrict_reduce(part[0], cg_init_parts(), part[1], cg_init_parts(), nullptr));
+  PGOC(coarse_solve(dot_part, nullptr));
+  return launch_coarse_prolong(z_out ? z_out : z, p_or_null);
+}
+
+// ---- launches several units need
+// (a batched handle's fixed_internal is -1, pgo_batch_create: fixed_mask carries one anchor per problem and the padding rows)
+int pgo_handle::launch_jacobi_scale(int pass) {
+  hipLaunchKernelGGL(dev::k_jacobi_scale<>, dim3(plan.own.g_rows), dim3(dev::WG), 0, stream, hd, S.n_loc, S.lo, fixed_internal, pass, scale, (const uint8_t*)fixed_mask);
+  return check_launch("k_jacobi_scale");
+}
+
+int pgo_handle::scatter_owned(const double* src) {
+  hipLaunchKernelGGL(dev::k_scatter_owned<>, dim3(plan.own.g_flat), dim3(dev::WG), 0, stream, (int)S.n_loc, (int)S.lo, src, p_full);
+  return check_launch("k_scatter_owned");
+}
+
+int pgo_handle::switch_prepare(double radius) {
+  hipLaunchKernelGGL(dev::k_switch_prepare<>, dim3(g_sw()), dim3(dev::WG), 0, stream, switch_arrays(), (const double*)jr, radius, opt.min_lm_diagonal,
+                     opt.max_lm_diagonal, part[2], part[3]);
+  return check_launch("k_switch_prepare");
+}
+
+// ---- caller's numbering <-> internal numbering
+int pgo_handle::upload_pose_vector(double* dst, const double* caller_src, int64_t row0, int64_t rows) {
+  if (rows < 0) rows = S.n_poses - row0;
+  if (rows == 0) return PGO_OK;
+  std::vector<double> staged;
+  const double* src = caller_src + 3 * row0;
+  if (!perm.empty()) {
+    staged.resize((size_t)3 * rows);
+    for (int64_t i = 0; i < S.n_poses; ++i) {
+      const int64_t k = perm[i] - row0;
+      if (k >= 0 && k < rows) memcpy(&staged[(size_t)3 * k], caller_src + 3 * i, 3 * sizeof(double));
+    }
+    src = staged.data();
+  }
+  HIPC(hipMemcpyAsync(dst, src, (size_t)3 * rows * sizeof(double), hipMemcpyHostToDevice, stream));
+  return sync();   // `staged` dies with this scope
+}
+
+int pgo_handle::download_pose_vector(double* caller_dst, const double* src, int64_t row0, int64_t rows) {
+  const int64_t N = S.n_poses;
+  if (rows < 0) rows = N - row0;
+  if (perm.empty()) {
+    if (rows < N) memset(caller_dst, 0, (size_t)3 * N * sizeof(double));
+    if (rows > 0) HIPC(hipMemcpyAsync(caller_dst + 3 * row0, src, (size_t)3 * rows * sizeof(double), hipMemcpyDeviceToHost, stream));
+    return sync();
+  }
+  std::vector<double> staged((size_t)3 * rows);
+  if (rows > 0) HIPC(hipMemcpyAsync(staged.data(), src, staged.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+  PGOC(sync());
+  for (int64_t i = 0; i < N; ++i) {
+    const int64_t k = perm[i] - row0;
+    if (k >= 0 && k < rows) memcpy(caller_dst + 3 * i, &staged[(size_t)3 * k], 3 * sizeof(double));
+    else memset(caller_dst + 3 * i, 0, 3 * sizeof(double));
+  }
+  return PGO_OK;
 }

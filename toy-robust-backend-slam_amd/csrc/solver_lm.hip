@@ -24,16 +24,13 @@ int pgo_handle::linearize(bool reuse_records, bool assemble) {
 // METHOD 2, at the top of every LM iteration (the radius has changed): elimination coefficients of the switches for
 // the current radius, re-assembly of the reduced pose system, gradient max-norm over poses AND switches, sum s^2.
 int pgo_handle::refresh_switch_system() {
-  const int g_sw = std::min(std::max(1, (S.n_edges_local + dev::WG - 1) / dev::WG), 1024);
-  hipLaunchKernelGGL(dev::k_switch_prepare<>, dim3(g_sw), dim3(dev::WG), 0, stream, switch_arrays(), (const double*)jr, tr.radius,
-                     opt.min_lm_diagonal, opt.max_lm_diagonal, part[2], part[3]);
-  PGOC(check_launch("k_switch_prepare"));
+  PGOC(switch_prepare(tr.radius));
   PGOC(assemble_enqueue());
   hipLaunchKernelGGL(dev::k_grad_max<>, dim3(plan.own.g_flat), dim3(dev::WG), 0, stream, (const double*)gs_full, (const double*)scale, S.n_loc,
                      S.lo, part[0]);
   PGOC(check_launch("k_grad_max"));
-  PGOC(reduce_to_scal({{part[0], plan.own.g_flat, 1}, {part[2], g_sw, 1}}, 10, true));
-  PGOC(reduce_to_scal({{part[3], g_sw, 0}}, 12));
+  PGOC(reduce_to_scal({{part[0], plan.own.g_flat, 1}, {part[2], g_sw(), 1}}, 10, true));
+  PGOC(reduce_to_scal({{part[3], g_sw(), 0}}, 12));
   PGOC(fetch_scal(10, 3));
   gmax = std::max(h_scal[10], h_scal[11]);
   sw_norm2 = h_scal[12];
@@ -60,7 +57,6 @@ int pgo_handle::lm_begin() {
   recs.clear();
   const double t_begin = wall_s();
   t_total = 0;
-  const int fixed = fixed_internal;
   if (has_sw) {  // switches start at 1.0 (main.cpp:117,139); nothing eliminated yet
     std::vector<double> ones((size_t)std::max(1, S.n_edges_local), 1.0);
     HIPC(hipMemcpyAsync(sw, ones.data(), (size_t)S.n_edges_local * sizeof(double), hipMemcpyHostToDevice, stream));
@@ -70,8 +66,7 @@ int pgo_handle::lm_begin() {
     PGOC(sync());  // `ones` dies with this scope
   }
   // pass 1: unit scales (0 on the constant pose) -> column norms for Jacobi scaling
-  hipLaunchKernelGGL(dev::k_jacobi_scale<>, dim3(plan.own.g_rows), dim3(dev::WG), 0, stream, hd, S.n_loc, S.lo, fixed, 0, scale, (const uint8_t*)fixed_mask);
-  PGOC(check_launch("k_jacobi_scale"));
+  PGOC(launch_jacobi_scale(0));
   PGOC(allgather(scale));
   PGOC(linearize(false));
   const double cost0 = h_scal[0];
@@ -81,8 +76,7 @@ int pgo_handle::lm_begin() {
     PGOC(check_launch("k_switch_scale"));
   }
   if (opt.jacobi_scaling) {
-    hipLaunchKernelGGL(dev::k_jacobi_scale<>, dim3(plan.own.g_rows), dim3(dev::WG), 0, stream, hd, S.n_loc, S.lo, fixed, 1, scale, (const uint8_t*)fixed_mask);
-    PGOC(check_launch("k_jacobi_scale"));
+    PGOC(launch_jacobi_scale(1));
     PGOC(allgather(scale));
     PGOC(linearize(true));  // the records do not depend on the scales: re-assemble only
   }
@@ -135,7 +129,7 @@ int pgo_handle::lm_iteration(bool* stop) {
 
   // LM diagonal + preconditioner, then the linear solve
   double t0 = wall_s();
-  PGOC(prepare_system());
+  PGOC(prepare_system(tr.radius));
   int k_it = 0;
   double rel = 0.0;
   // Ranks above DIRECT_AUTO_RANK in auto mode (dl_possible): which solver is cheaper depends on the conditioning and changes
@@ -211,8 +205,7 @@ int pgo_handle::lm_iteration_tail(bool* stop, pgo_iter_record& R, double it0, do
   // (rtol 0.1, ~100 iterations) keeps the recurrence residual; the direct solve writes the true residual itself.
   const bool true_residual = k_it > 0 && (opt.pcg_rtol < 1e-6 || k_it > 1000);
   if (has_sw || true_residual) {  // (the switch back-substitution below reads y of both endpoints from the gather vector)
-    hipLaunchKernelGGL(dev::k_scatter_owned<>, dim3(plan.own.g_flat), dim3(dev::WG), 0, stream, S.n_loc, S.lo, y, p_full);
-    PGOC(check_launch("k_scatter_owned"));
+    PGOC(scatter_owned(y));
     PGOC(share_gather_vector(p_full));
   }
   if (true_residual) {
@@ -231,11 +224,10 @@ int pgo_handle::lm_iteration_tail(bool* stop, pgo_iter_record& R, double it0, do
   PGOC(check_launch("k_candidate"));
   double model_sw = 0.0, step2_sw = 0.0;
   if (has_sw) {  // back-substitute the switches (needs y of both endpoints: in the gather vector after the share above)
-    const int g_sw = std::min(std::max(1, (S.n_edges_local + dev::WG - 1) / dev::WG), 1024);
-    hipLaunchKernelGGL(dev::k_switch_backsub<>, dim3(g_sw), dim3(dev::WG), 0, stream, switch_arrays(), (const int32_t*)e_ia,
+    hipLaunchKernelGGL(dev::k_switch_backsub<>, dim3(g_sw()), dim3(dev::WG), 0, stream, switch_arrays(), (const int32_t*)e_ia,
                        (const int32_t*)e_ib, (const double*)jr, (const double*)scale, (const double*)p_full, part[2], part[4]);
     PGOC(check_launch("k_switch_backsub"));
-    PGOC(reduce_to_scal({{part[2], g_sw, 0}, {part[4], g_sw, 0}}, 13));
+    PGOC(reduce_to_scal({{part[2], g_sw(), 0}, {part[4], g_sw(), 0}}, 13));
   }
   PGOC(reduce_to_scal({{part[1], plan.own.g_flat, 0}, {part[0], plan.own.g_flat, 0}, {part[3], plan.own.g_flat, 0}, {part[5], plan.own.g_flat, 0}}, 0));
   // the candidate's cost is evaluated in the same breath (scal[6..7]; wasted only when the step turns out invalid): one

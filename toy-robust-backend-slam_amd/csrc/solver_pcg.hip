@@ -138,18 +138,9 @@ int pgo_handle::coarse_solve(double* dot_part, const int32_t* done) {
 int pgo_handle::pcg(int* iters, double* rel) {
   dev::CgVec V = cg_vec();
   const bool multi = multi_rank();
-  dev::GroupPre GP;
-  GP.ginv = ginv;
-  GP.B = plan.own.grp_B;
-  GP.nb = plan.own.grp_nb;
-  GP.nb_pad = plan.own.grp_pad;
-  GP.n_groups = plan.own.n_groups;
+  const dev::GroupPre GP = group_pre();
   const bool grouped = plan.own.grp_B > 1, chained = plan.all.chain_len > 0;
-  const int g_u1 = chained ? plan.own.g_chain : (grouped ? plan.own.g_grp : plan.own.g_vec);  // grid (= number of partials) of the init / update1 kernels
-  if (chained) launch_cg_init_chain(gs, part[0], part[1]);
-  else if (grouped) hipLaunchKernelGGL(dev::k_cg_init_g<>, dim3(g_u1), dim3(dev::WG), 0, stream, V, GP, (const double*)gs, part[0], part[1]);
-  else hipLaunchKernelGGL(dev::k_cg_init<>, dim3(g_u1), dim3(dev::WG), 0, stream, V, gs, part[0], part[1]);
-  PGOC(check_launch("k_cg_init"));
+  const int g_u1 = cg_init_parts();  // grid (= number of partials) of the init / update1 kernels
   const bool sr = plan.all.use_sr && chained;
   // single-reduction loop: "make u visible to the peers, w = A u, reduce (gamma, rr, delta) together, new coefficients"
   auto sr_product_and_scalars = [&](int first) -> int {
@@ -164,38 +155,34 @@ int pgo_handle::pcg(int* iters, double* rel) {
     hipLaunchKernelGGL(dev::k_cg_sr_scal<>, dim3(1), dim3(1), 0, stream, st, (const double*)(scal + 4), opt.pcg_rtol, first);
     return check_launch("k_cg_sr_scal");
   };
+  // z = M^-1 b.  One rank: both levels in one call.  Several ranks with the coarse level run the pieces of precondition() below:
+  // r_c rides in the all-reduce of the start-up sums and the coarse share is added to the reduced r.z once (k_coarse_fin).
+  // (The single-reduction loop has no second level.)
+  const bool two_level_multi = coarse_on() && co_multi();
+  if (sr || two_level_multi) PGOC(launch_cg_init(gs, nullptr, part[0], part[1]));
+  else PGOC(precondition(gs, nullptr, p_full, part[0] + g_u1));
   if (sr) {
     // the start-up kernel left u = M^-1 b in the gather vector (and in z, which becomes p: beta = 0 in the first update)
     HIPC(hipMemsetAsync(sr_s, 0, (size_t)3 * S.n_loc * sizeof(double), stream));
     PGOC(sr_product_and_scalars(1));
   } else {
-    // two levels: z (= p) of the start-up kernel gets the coarse correction, r.z one more partial
+    // two levels: z (= p) of the start-up kernel got the coarse correction, r.z one more partial
     const int n_rz0 = coarse_on() ? g_u1 + CO().co_ndot : g_u1;
-    if (coarse_on() && co_multi()) {
-      // several ranks: r_c rides in the all-reduce of the start-up sums; the coarse share is added to the reduced r.z once
+    if (two_level_multi) {
       PGOC(coarse_restrict_reduce(part[0], g_u1, part[1], g_u1, nullptr));
       PGOC(coarse_solve(co_dotp, nullptr));
       hipLaunchKernelGGL(dev::k_coarse_fin<>, dim3(1), dim3(dev::WG), 0, stream, (const double*)(co_red + CO().co_Kp), (const double*)co_dotp, CO().co_ndot,
                          scal + 4);
       PGOC(check_launch("k_coarse_fin"));
-      hipLaunchKernelGGL(dev::k_coarse_prolong_m<>, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((S.n_loc + 255) / 256, 512))), dim3(256), 0,
-                         stream, (int)S.n_loc, (int)S.lo, CO().co_agg, (const double*)co_pb, (int64_t)S.n_poses, (const double*)co_ec, z, p_full,
-                         (const int32_t*)co_ok);
-      PGOC(check_launch("k_coarse_prolong_m"));
-      hipLaunchKernelGGL(dev::k_flag_to_double<>, dim3(1), dim3(1), 0, stream, (const int*)co_ok, scal + 15);
-      PGOC(check_launch("k_flag_to_double"));
-      co_flag_pending = true;
-    } else if (coarse_on()) {
-      PGOC(coarse_solve(part[0] + g_u1, nullptr));
-      hipLaunchKernelGGL(dev::k_coarse_prolong<>, dim3((unsigned)std::min<int64_t>((S.n_loc + 255) / 256, 512)), dim3(256), 0, stream, (int)S.n_loc,
-                         CO().co_agg, (const double*)co_pb, (const double*)co_ec, z, p_full + dev::PS * (int64_t)S.lo, (const int32_t*)co_ok);
-      PGOC(check_launch("k_coarse_prolong"));
+      PGOC(launch_coarse_prolong(z, p_full));
+    }
+    if (coarse_on()) {
       // whether this solve has the level: read back with the model terms (lm_iteration_tail), counted in co_off_iters
       hipLaunchKernelGGL(dev::k_flag_to_double<>, dim3(1), dim3(1), 0, stream, (const int*)co_ok, scal + 15);
       PGOC(check_launch("k_flag_to_double"));
       co_flag_pending = true;
     }
-    if (!(coarse_on() && co_multi())) PGOC(reduce_to_scal({{part[0], n_rz0, 0}, {part[1], g_u1, 0}}, 4));
+    if (!two_level_multi) PGOC(reduce_to_scal({{part[0], n_rz0, 0}, {part[1], g_u1, 0}}, 4));
     hipLaunchKernelGGL(dev::k_cg_init_fin<>, dim3(1), dim3(1), 0, stream, st, scal + 4, opt.pcg_rtol);
     PGOC(check_launch("k_cg_init_fin"));
     if (!plan.own.overlap) PGOC(share_gather_vector(p_full));
@@ -356,8 +343,7 @@ int pgo_handle::pcg(int* iters, double* rel) {
   if (plan.all.verify_residual) {
     // test hook: report |b - A y| / |b| of the solution instead of the recurrence residual the loop stopped on (one more
     // product; the recurrences of either loop drift from it on ill-conditioned systems)
-    hipLaunchKernelGGL(dev::k_scatter_owned<>, dim3(plan.own.g_flat), dim3(dev::WG), 0, stream, (int)S.n_loc, (int)S.lo, (const double*)V.y, p_full);
-    PGOC(check_launch("k_scatter_owned"));
+    PGOC(scatter_owned(y));
     PGOC(share_gather_vector(p_full));
     PGOC(spmv_enqueue(p_full, ap, part[0], 1, nullptr));
     hipLaunchKernelGGL(dev::k_residual_norm<>, dim3(plan.own.g_flat), dim3(dev::WG), 0, stream, (int64_t)3 * S.n_loc, (const double*)gs, (const double*)ap, part[1], part[2]);
@@ -412,13 +398,13 @@ int pgo_handle::factor_chain() {
   return check_launch("k_chain_factor");
 }
 
-// LM diagonal for the current radius (per problem in a batched handle) + the preconditioner's set-up
-int pgo_handle::prepare_system() {
-  hipLaunchKernelGGL(dev::k_prepare<>, dim3(plan.own.g_rows), dim3(dev::WG), 0, stream, hd, (const double*)diag_full, S.n_loc, S.lo, fixed_internal, tr.radius,
+// LM diagonal for `radius` (per problem in a batched handle) + the preconditioner's set-up
+int pgo_handle::prepare_system(double radius, bool preconditioner_also_on_direct) {
+  hipLaunchKernelGGL(dev::k_prepare<>, dim3(plan.own.g_rows), dim3(dev::WG), 0, stream, hd, (const double*)diag_full, S.n_loc, S.lo, fixed_internal, radius,
                      opt.min_lm_diagonal, opt.max_lm_diagonal, d2, minv, (const uint8_t*)fixed_mask, (const int32_t*)prob_of_256,
                      (const double*)prob_radius, plan.all.chain_len ? chain_c : (double*)nullptr, hdd);
   PGOC(check_launch("k_prepare"));
-  if (!direct()) PGOC(prepare_preconditioner());   // (the direct solve does not need it; its PCG fallback sets it up on demand)
+  // (the direct solve does not need the preconditioner; its PCG fallback sets it up on demand)
+  if (!direct() || preconditioner_also_on_direct) PGOC(prepare_preconditioner());
   return PGO_OK;
 }
-
