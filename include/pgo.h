@@ -1020,6 +1020,90 @@ int pgo_coarsen_info_plan(int32_t n_poses, int32_t n_edges, const int32_t* ia, c
 int pgo_coarsen_info(pgo_t* h, int32_t stride, pgo_graph** coarse_out, int32_t* origin_or_null, double* cov_or_null /* cap x 6 */,
                      int32_t cap, int32_t* n_coarse_edges_or_null);                                               /* [gpu] */
 
+/* ---------------------------------------------------------------- chordal initialisation (an estimate-free linear start)
+ * Poses from the measurements alone, by the two-stage linear relaxation of SE(2) (chordal rotations, then positions given the
+ * rotations: Martinec-Pajdla, LAGO, Carlone's "initialization techniques"): no basin, no estimate.  Both stages are one kind of
+ * system -- a Hermitian, complex-valued weighted graph Laplacian with a unit phase per edge -- solved by Jacobi-preconditioned
+ * CG.  Caller's numbering throughout; csrc/chordal.h is the one statement.
+ * - Weights.  Edge e = (a, b, m) has u_e = its weight (the edge weight plane, 1 without one; w of pgo_chordal_plan) if it is
+ *   active (pgo_set_active), else 0.  An edge with a == b has u_e = 0.
+ * - Constant poses C: what the handle holds constant (opt.fixed_pose, and under pgo_set_active the poses it resolved to
+ *   constant); constant_or_null of pgo_chordal_plan (NULL: pose 0).  They keep their current values.  c0 = the smallest.
+ * - Chain and trajectory: as pgo_loop_support -- the first edge between i and i + 1 in the caller's order, T_0 = (0, 0, 0),
+ *   T_{i+1} = T_i o Z_i, whatever the weight of the chain edge.  X_i = (P_c0 o T_c0^-1) o T_i is T moved rigidly onto c0.
+ * - Stage R.  Unknowns z_i complex, z_c = exp(i theta_c) on C: minimise sum_e u_e |z_b - exp(i m_theta) z_a|^2.  Then
+ *   theta_i = atan2(Im z_i, Re z_i), zh_i = z_i / |z_i|.  A pose with |z_i| < mag_min is degenerate: it is counted and keeps the
+ *   heading of X_i.
+ * - Stage T.  Unknowns t_i complex, t_c = x_c + i y_c on C: minimise sum_e u_e |t_b - t_a - zh_a (m_x + i m_y)|^2.
+ * - Both are H x = b with H_aa += u, H_bb += u, H_ba -= u phi, H_ab -= u conj(phi), phi = exp(i m_theta) in stage R and 1 in
+ *   stage T; the rows of C are eliminated (identity rows, their coupling moved into b).  A pose that is not constant and has no
+ *   positive-weight edge is an identity row as well: it keeps X_i.  Jacobi-PCG from x0 = X (stage R: its rotation) until
+ *   |r| <= rtol |b|, at most max_iters iterations; |r| and |b| run over the rows that are not identity rows.
+ * - Report per edge, caller's order: res_out[2e] = |t_b - t_a - zh_a m|, res_out[2e + 1] = |wrap(theta_b - theta_a - m_theta)|.
+ * - Reject rounds.  After each of the first `rounds` solves every edge with u_e > 0 that is not a chain edge and has
+ *   res_xy > reject_xy or res_th > reject_th gets u_e = 0, and the system is solved again; the rounds end early when a solve
+ *   rejects nothing.  The last solve rejects nothing.  With apply_weights the rejected edges get the weight 0 in the handle's
+ *   edge weight plane (created at all ones at its first use, every other edge keeps its weight; a solve begun with
+ *   pgo_lm_begin is stale afterwards; the refusals are those of pgo_set_edge_weights).
+ * - commit != 0 writes (Re t, Im t, theta) as the handle's poses, as pgo_prolong does: the constant poses stay bitwise as they
+ *   were and a solve begun with pgo_lm_begin is stale.  With commit == 0 and apply_weights == 0 the handle is left exactly as it
+ *   was: a following pgo_lm_step gives bitwise the records and poses it gives without the call.
+ * - Errors.  PGO_ERR_UNSUPPORTED: a component of the positive-weight edges without a constant pose (pgo_last_error names one of
+ *   its poses) -- at the start or after a round's rejections --, a pair (i, i + 1) without an edge, a communicator,
+ *   PGO_FORCE_COLLECTIVES=1, a batched handle.  PGO_ERR_NUMERIC: a measurement of a positive-weight edge or of a chain edge
+ *   that is not finite (pgo_last_error names the smallest such edge); a solution that is not finite.  PGO_ERR_INVALID_ARG: rtol
+ *   not finite or <= 0, max_iters < 1, check_every < 1, mag_min < 0, rounds outside 0 .. PGO_CHORDAL_MAX_ROUNDS, a reject
+ *   threshold that is NaN or <= 0, a null pointer, n_poses < 2, an endpoint out of range, a weight outside [0, 1].  Nothing
+ *   changes on error.
+ * pgo_chordal_plan is the serial statement on arrays (sums in the caller's order, the convergence test after every iteration).
+ * pgo_chordal_init runs it on the measurements the handle holds on the device.  The slot table (rows sorted by (pose, edge
+ * index), col and edge | orientation per slot, duplicates keep their slots) is built on the host once per handle; per stage
+ * k_chordal_assemble writes the 16-byte slot values, the real diagonal (summed in slot order), b and x0; k_chordal_spmv gives a
+ * wavefront 64 consecutive rows, whose slots are contiguous -- its lanes stride them with 16-byte value loads and gather x[col]
+ * as 16 bytes, the products of a row are added in slot order -- and writes the partials of Re(p^H q) of its tile of 256 rows;
+ * two fused vector kernels fold the partials in fixed order into alpha and beta and update x, r, z = r / d and p: three
+ * launches per iteration.  The host reads the residual norm once per check_every iterations: the device stops by itself at
+ * the iteration the plan stops at, the launches after it do nothing.  No atomics, fixed trees: two calls are bitwise equal, a
+ * handle with pose_ordering 1 gives bitwise what one with 0 gives, and the grid ("chordal_grid") plays no part; the result
+ * agrees with the plan up to the association of the dot products and of T.  fp64 throughout.                                  */
+#define PGO_CHORDAL_MAX_ROUNDS 8
+typedef struct pgo_chordal_options {
+  double  rtol;           /* 1e-8 */
+  double  mag_min;        /* 1e-3 */
+  double  reject_xy;      /* 2.0 (metres) */
+  double  reject_th;      /* 0.35 (radians) */
+  int32_t max_iters;      /* 20000, per stage */
+  int32_t check_every;    /* 50 */
+  int32_t rounds;         /* 0 */
+  int32_t commit;         /* 0 */
+  int32_t apply_weights;  /* 0 */
+  int32_t _pad;
+} pgo_chordal_options;
+typedef struct pgo_chordal_solve {   /* one solve of both stages: [0] stage R, [1] stage T */
+  int32_t iters[2];
+  int32_t converged[2];
+  double  rel_residual[2];   /* |r| / |b| at the end (the recurrence residual) */
+  double  min_mag;           /* the smallest |z_i| over the poses that are not constant (+inf: none; NaN: some |z_i| is) */
+  int32_t n_degenerate;
+  int32_t n_rejected;        /* edges this solve's residuals rejected */
+} pgo_chordal_solve;
+typedef struct pgo_chordal_summary {
+  int32_t n_solves;          /* 1 + the reject rounds that ran */
+  int32_t n_rejected;        /* in all */
+  int32_t n_degenerate;      /* of the last solve, as min_mag */
+  int32_t _pad;
+  double  min_mag;
+  double  seconds;
+  pgo_chordal_solve solve[PGO_CHORDAL_MAX_ROUNDS + 1];
+} pgo_chordal_summary;
+void pgo_chordal_options_default(pgo_chordal_options*);                                                           /* [host] */
+int  pgo_chordal_plan(int32_t n_poses, int32_t n_edges, const int32_t* ia, const int32_t* ib, const double* meas_xyt,
+                      const double* w_or_null /* E */, const uint8_t* constant_or_null /* N */, const double* poses_xyt /* N x 3 */,
+                      const pgo_chordal_options* opt, double* poses_out /* N x 3 */, double* res_out /* E x 2 */,
+                      double* w_out_or_null /* E: w with 0 on the rejected edges */, pgo_chordal_summary* summary);   /* [host] */
+int  pgo_chordal_init(pgo_t* h, const pgo_chordal_options* opt, double* poses_out_or_null /* N x 3 */,
+                      double* res_out_or_null /* E x 2 */, pgo_chordal_summary* summary_or_null);                    /* [gpu] */
+
 /* ------------------------------------------------ kernel-level entry points
  * Used by the parity tests and by bench.py's roofline leg: each launches exactly
  * one kind of kernel `reps` times on the handle's stream, brackets the launches
@@ -1094,6 +1178,8 @@ int pgo_debug_normal_eq(pgo_t* h, double* g_or_null, double* hdiag_or_null);    
  *   "support_grid"       n > 0 = pgo_loop_support launches n workgroups over its segments, poses, loops and chunks of 256 edges
  *                        instead of one per unit of work (read per call; the trajectory is computed at a handle's first call; the
  *                        results are bitwise the same)
+ *   "chordal_grid"       n > 0 = pgo_chordal_init launches n workgroups over its tiles of 256 rows and chunks of 256 edges instead
+ *                        of one per unit of work (read per call; the results are bitwise the same)
  * Unknown name: PGO_ERR_INVALID_ARG.                                                                     */
 int pgo_debug_set_knob(const char* name, long long value);                        /* [host] */
 /* sharding plan of a graph over `world` ranks: for rank r, rows [lo, hi) and the

@@ -28,7 +28,8 @@ __all__ = ["PgoError", "Options", "Summary", "IterRecord", "ReadG2O", "Graph", "
            "synth_manhattan_truth", "trajectory_error", "TrajOptions", "TrajError", "EdgeWeight", "SCORE_POSES_PER_WG",
            "coarsen_plan", "coarsen_info_plan", "prolong_eval", "COARSEN_MIN_STRIDE", "COARSEN_MAX_STRIDE",
            "gnc_weight_eval", "GncStats", "GncOptions", "GncRound", "GncSummary",
-           "loop_support_plan", "LoopSupportOptions", "LoopSupportRecord", "LoopSupportStats", "LOOP_SUPPORT_MAX_WINDOW"]
+           "loop_support_plan", "LoopSupportOptions", "LoopSupportRecord", "LoopSupportStats", "LOOP_SUPPORT_MAX_WINDOW",
+           "chordal_plan", "ChordalOptions", "ChordalSolve", "ChordalSummary", "CHORDAL_MAX_ROUNDS"]
 
 EDGE_ODOMETRY, EDGE_CLOSURE, EDGE_BOGUS = 0, 1, 2
 TERMINATION = {1: "CONVERGENCE_FTOL", 2: "CONVERGENCE_GTOL", 3: "CONVERGENCE_PTOL", 4: "NO_CONVERGENCE",
@@ -61,7 +62,9 @@ EXPORTS = [
     "pgo_coarsen_plan", "pgo_prolong_eval", "pgo_coarsen", "pgo_prolong", "pgo_coarsen_info_plan", "pgo_coarsen_info",
     "pgo_set_edge_weights", "pgo_get_edge_weights", "pgo_gnc_options_default", "pgo_gnc_weight_eval", "pgo_gnc_update", "pgo_gnc_solve",
     "pgo_loop_support_options_default", "pgo_loop_support_plan", "pgo_loop_support",
+    "pgo_chordal_options_default", "pgo_chordal_plan", "pgo_chordal_init",
 ]
+CHORDAL_MAX_ROUNDS = 8   # PGO_CHORDAL_MAX_ROUNDS
 LOOP_SUPPORT_MAX_WINDOW = 256   # PGO_LOOP_SUPPORT_MAX_WINDOW
 COARSEN_MIN_STRIDE, COARSEN_MAX_STRIDE = 2, 256   # PGO_COARSEN_*_STRIDE (include/pgo.h)
 SCORE_POSES_PER_WG = 512   # PGO_SCORE_POSES_PER_WG
@@ -343,6 +346,43 @@ class LoopSupportStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "_pad"}
 
 
+_CHORDAL_OPTS = ("rtol", "mag_min", "reject_xy", "reject_th", "max_iters", "check_every", "rounds", "commit", "apply_weights")
+
+
+class ChordalOptions(C.Structure):
+    """mirror of pgo_chordal_options (defaults: pgo_chordal_options_default)"""
+    _fields_ = [("rtol", C.c_double), ("mag_min", C.c_double), ("reject_xy", C.c_double), ("reject_th", C.c_double),
+                ("max_iters", C.c_int32), ("check_every", C.c_int32), ("rounds", C.c_int32), ("commit", C.c_int32),
+                ("apply_weights", C.c_int32), ("_pad", C.c_int32)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().pgo_chordal_options_default(C.byref(self))
+        for k, v in kw.items():
+            if k not in _CHORDAL_OPTS:
+                raise TypeError("unknown chordal option " + k)
+            setattr(self, k, int(v) if k in _CHORDAL_OPTS[4:] else float(v))
+
+
+class ChordalSolve(C.Structure):
+    """mirror of pgo_chordal_solve: one solve of both stages ([0] rotations, [1] positions)"""
+    _fields_ = [("iters", C.c_int32 * 2), ("converged", C.c_int32 * 2), ("rel_residual", C.c_double * 2), ("min_mag", C.c_double),
+                ("n_degenerate", C.c_int32), ("n_rejected", C.c_int32)]
+
+    def as_dict(self):
+        return {"iters": list(self.iters), "converged": list(self.converged), "rel_residual": list(self.rel_residual),
+                "min_mag": self.min_mag, "n_degenerate": self.n_degenerate, "n_rejected": self.n_rejected}
+
+
+class ChordalSummary(C.Structure):
+    _fields_ = [("n_solves", C.c_int32), ("n_rejected", C.c_int32), ("n_degenerate", C.c_int32), ("_pad", C.c_int32),
+                ("min_mag", C.c_double), ("seconds", C.c_double), ("solve", ChordalSolve * (8 + 1))]
+
+    def as_dict(self):
+        return {"n_solves": self.n_solves, "n_rejected": self.n_rejected, "n_degenerate": self.n_degenerate, "min_mag": self.min_mag,
+                "seconds": self.seconds, "solves": [self.solve[k].as_dict() for k in range(self.n_solves)]}
+
+
 _LIB = None
 
 
@@ -492,6 +532,10 @@ def lib():
     L.pgo_loop_support_plan.argtypes = [C.c_int32, C.c_int32, ip, ip, dp, bp, bp, C.POINTER(LoopSupportOptions), C.POINTER(LoopSupportRecord),
                                         C.POINTER(LoopSupportStats), dp]
     L.pgo_loop_support.argtypes = [vp, C.POINTER(LoopSupportOptions), bp, C.POINTER(LoopSupportRecord), C.POINTER(LoopSupportStats)]
+    L.pgo_chordal_options_default.argtypes = [C.POINTER(ChordalOptions)]
+    L.pgo_chordal_options_default.restype = None
+    L.pgo_chordal_plan.argtypes = [C.c_int32, C.c_int32, ip, ip, dp, dp, bp, dp, C.POINTER(ChordalOptions), dp, dp, dp, C.POINTER(ChordalSummary)]
+    L.pgo_chordal_init.argtypes = [vp, C.POINTER(ChordalOptions), dp, dp, C.POINTER(ChordalSummary)]
     _LIB = L
     return L
 
@@ -705,6 +749,33 @@ def loop_support_plan(n_poses, ia, ib, meas, kind, select=None, window=32, tol_x
                                        C.byref(o), res, C.byref(st), _dp(T)))
     rec = _support_records(res, len(ia))
     return (rec, st.as_dict(), T[:int(n_poses)]) if want_T else (rec, st.as_dict())
+
+
+def chordal_plan(n_poses, ia, ib, meas, poses, w=None, constant=None, **opts):
+    """pgo_chordal_plan (host only), the serial statement of Solver.chordal_init: chordal rotations, then positions given the
+    rotations, each a Hermitian system solved by Jacobi-PCG from the odometry trajectory; no estimate plays a part except on
+    the constant poses (constant: a mask over the poses, default pose 0), which keep their values in `poses`.  w: a weight in
+    [0, 1] per edge (default 1; 0 = the edge is not there).  opts: the fields of ChordalOptions (rtol, max_iters, check_every,
+    mag_min, rounds, reject_xy, reject_th).  Returns (poses (N, 3), res (E, 2): |position residual|, |heading residual| per
+    edge, w_out (E): w with 0 on the edges the rounds rejected, summary dict)."""
+    ia = np.ascontiguousarray(ia, np.int32)
+    ib = np.ascontiguousarray(ib, np.int32)
+    meas = np.ascontiguousarray(meas, np.float64).reshape(-1, 3)
+    poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
+    n, E = int(n_poses), len(ia)
+    if not (len(ib) == len(meas) == E) or len(poses) != n:
+        raise ValueError("chordal_plan: ia, ib and meas must have one entry per edge, poses one row per pose")
+    if w is not None:
+        w = np.ascontiguousarray(w, np.float64).reshape(-1)
+        if len(w) != E:
+            raise ValueError("chordal_plan: w must have one entry per edge")
+    m = _mask(constant, n, "constant")
+    o = ChordalOptions(**opts)
+    out, res, w_out = np.zeros((max(n, 1), 3)), np.zeros((max(E, 1), 2)), np.zeros(max(E, 1))
+    summ = ChordalSummary()
+    _check(lib().pgo_chordal_plan(n, E, _ip(ia), _ip(ib), _dp(meas), _dp(w) if w is not None else None, _bp(m) if m is not None else None,
+                                  _dp(poses), C.byref(o), _dp(out), _dp(res), _dp(w_out), C.byref(summ)))
+    return out[:n], res[:E], w_out[:E], summ.as_dict()
 
 
 def shard_plan(n_poses, ia, ib, world, rank, row_align=1):
@@ -1200,6 +1271,18 @@ class Solver:
         st = LoopSupportStats()
         _check(lib().pgo_loop_support(self._h, C.byref(o), _bp(m) if m is not None else None, res, C.byref(st)))
         return _support_records(res, self.n_edges), st.as_dict()
+
+    def chordal_init(self, commit=False, apply_weights=False, **opts):
+        """pgo_chordal_init: chordal_plan on the measurements the handle holds on the device, with the handle's weight plane,
+        active set and constant poses; the estimate plays no part except on the constant poses.  commit=True writes the result
+        as the handle's poses (constant poses are not moved; a solve begun with lm_begin is stale); apply_weights=True writes 0
+        into the weight plane on the edges the reject rounds (rounds, reject_xy, reject_th) dropped (METHOD 0 / 1).
+        Returns (poses (N, 3), res (E, 2), summary dict)."""
+        o = ChordalOptions(commit=int(bool(commit)), apply_weights=int(bool(apply_weights)), **opts)
+        out, res = np.zeros((max(self.n_poses, 1), 3)), np.zeros((max(self.n_edges, 1), 2))
+        summ = ChordalSummary()
+        _check(lib().pgo_chordal_init(self._h, C.byref(o), _dp(out), _dp(res), C.byref(summ)))
+        return out[:self.n_poses], res[:self.n_edges], summ.as_dict()
 
     def coarsen(self, stride: int, information: bool = False):
         """pgo_coarsen: the coarse graph of the handle's measurements at `stride` (see coarsen_plan), with the handle's current

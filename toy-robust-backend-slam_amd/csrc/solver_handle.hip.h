@@ -14,8 +14,9 @@
 //   solver_coarsen.hip  pgo_coarsen, pgo_prolong: a coarse graph along the odometry chain and back (coarsen.hip.h, coarsen.h)
 //   solver_gnc.hip      pgo_set_edge_weights, pgo_gnc_update, pgo_gnc_solve: the edge weight plane and GNC-TLS (gnc.hip.h, gnc.h)
 //   solver_support.hip  pgo_loop_support: loop edges judged by odometry cycle consistency (loop_support.hip.h, loop_support.h)
+//   solver_chordal.hip  pgo_chordal_init: a linear start, chordal rotations then positions (chordal.hip.h, chordal.h)
 // Every kernel header declares its kernels `static`: a translation unit carries the kernels it launches.
-// The add-on calls (the last five units) share the helpers below: requires() for their refusals, reserve() and the Layouts of
+// The add-on calls (the last six units) share the helpers below: requires() for their refusals, reserve() and the Layouts of
 // scratch.h for their staging and work buffers.
 //
 // Replaces, for DCS-ceres/main.cpp METHOD 0/1 (paths relative to /root/reference/DCS-ceres):
@@ -632,6 +633,18 @@ struct pgo_handle {
   pgo::Scratch ls_tab, ls_work;
   std::vector<uint8_t> ls_host;   // host image of a call's outputs
   int loop_support(const pgo_loop_support_options* o, const uint8_t* select_or_null, pgo_loop_support_record* out, pgo_loop_support_stats* stats);
+  int support_trajectory_alloc();     // ls_traj, before anything is enqueued
+  int support_trajectory_enqueue();   // T's three launches unless ls_traj_ready (the caller sets it after its synchronisation)
+
+  // chordal initialisation (pgo_chordal_init; solver_chordal.hip).  It starts from the trajectory above and walks the tables of
+  // pgo_coarsen.  ch_tab = the slot table -- rp [N + 1] | col | edge and orientation per slot | caller's edge -> local edge [E] --,
+  // built on the host at the first call and kept (ch_slots: its slot count); ch_work = a call's
+  // weights, mask, system, PCG vectors, partials, state and outputs.  Both are grown on demand and kept (reserve).
+  bool ch_tab_ready = false;
+  int64_t ch_slots = 0;
+  pgo::Scratch ch_tab, ch_work;
+  std::vector<uint8_t> ch_host;   // host image of a call's uploads, then of its outputs
+  int chordal_init(const pgo_chordal_options* o, double* poses_out, double* res_out, pgo_chordal_summary* summary);
 
   int create(int32_t N, const double* poses_h, int32_t E, const int32_t* ia, const int32_t* ib, const double* meas,
              const double* info6, const uint8_t* kind);

@@ -18,6 +18,38 @@ int check_options(const std::string& who, const pgo_loop_support_options* o) {
 }
 }  // namespace
 
+// The trajectory T (loop_support.h), once per handle: its buffer, before anything is enqueued, and its three launches.  The
+// caller sets ls_traj_ready after its synchronisation.  Shared with pgo_chordal_init, whose start it is.
+int pgo_handle::support_trajectory_alloc() {
+  const int64_t N = S.n_poses, P = pgo::SUPPORT_POSE, n_seg = (N + dev::SUPPORT_SEG - 1) / dev::SUPPORT_SEG;
+  if (!ls_traj) PGOC(dalloc(&ls_traj, (N + 2 * n_seg) * P));
+  return PGO_OK;
+}
+int pgo_handle::support_trajectory_enqueue() {
+  const int64_t N = S.n_poses, P = pgo::SUPPORT_POSE, n_seg = (N + dev::SUPPORT_SEG - 1) / dev::SUPPORT_SEG;
+  auto grid_for = [&](int64_t units) { return launch_grid("support_grid", units); };
+  auto per_lane = [&](int64_t n) { return grid_for((n + dev::WG - 1) / dev::WG); };
+  if (!ls_traj_ready) {
+    dev::SupportTrajArgs A;
+    A.mx = e_mx;
+    A.my = e_my;
+    A.mt = e_mt;
+    A.chain = cs_chain();
+    A.n = (int32_t)N;
+    A.n_seg = (int32_t)n_seg;
+    A.T = ls_traj;
+    A.Cend = ls_traj + N * P;
+    A.Tkey = ls_traj + (N + n_seg) * P;
+    hipLaunchKernelGGL(dev::k_support_segments<>, dim3(grid_for((n_seg + dev::WG / 64 - 1) / (dev::WG / 64))), dim3(dev::WG), 0, stream, A);
+    PGOC(check_launch("k_support_segments"));
+    hipLaunchKernelGGL(dev::k_support_keys<>, dim3(1), dim3(dev::WG), 0, stream, A);
+    PGOC(check_launch("k_support_keys"));
+    hipLaunchKernelGGL(dev::k_support_traj<>, dim3(per_lane(N)), dim3(dev::WG), 0, stream, A);
+    PGOC(check_launch("k_support_traj"));
+  }
+  return PGO_OK;
+}
+
 int pgo_handle::loop_support(const pgo_loop_support_options* o, const uint8_t* select, pgo_loop_support_record* out, pgo_loop_support_stats* stats) {
   const char* who = "pgo_loop_support";
   PGOC(requires(who, ONE_RANK | NOT_BATCH));
@@ -41,7 +73,7 @@ int pgo_handle::loop_support(const pgo_loop_support_options* o, const uint8_t* s
     }
   if (bad >= 0) return not_finite(who, bad);
   // ---- buffers, before anything is enqueued or changed
-  const int64_t P = pgo::SUPPORT_POSE, n_seg = (N + dev::SUPPORT_SEG - 1) / dev::SUPPORT_SEG;
+  const int64_t P = pgo::SUPPORT_POSE;
   const bool new_table = !ls_tab_ready || sel != ls_sel_h;
   std::vector<int32_t> s_edge, s_lo, s_hi, first, slot_of;
   int64_t n_sel = ls_n_sel;
@@ -58,7 +90,7 @@ int pgo_handle::loop_support(const pgo_loop_support_options* o, const uint8_t* s
   const auto w_part = LW.add<double>(dev::SUPPORT_NPART * nc), w_q = LW.add<double>(n_sel);
   const auto w_out = LW.add<pgo_loop_support_record>(E);
   const auto w_cnt = LW.add<int32_t>(3 * n_sel);
-  if (!ls_traj) PGOC(dalloc(&ls_traj, (N + 2 * n_seg) * P));
+  PGOC(support_trajectory_alloc());
   if (new_table) ls_tab_ready = false;   // (the buffer may move and is rewritten)
   PGOC(reserve(ls_tab, LT.bytes()));
   PGOC(reserve(ls_work, LW.bytes()));
@@ -67,25 +99,7 @@ int pgo_handle::loop_support(const pgo_loop_support_options* o, const uint8_t* s
   if (out) ls_host.resize((size_t)w_out.bytes());
   auto grid_for = [&](int64_t units) { return launch_grid("support_grid", units); };
   auto per_lane = [&](int64_t n) { return grid_for((n + dev::WG - 1) / dev::WG); };
-  // ---- the trajectory, once per handle
-  if (!ls_traj_ready) {
-    dev::SupportTrajArgs A;
-    A.mx = e_mx;
-    A.my = e_my;
-    A.mt = e_mt;
-    A.chain = cs_chain();
-    A.n = (int32_t)N;
-    A.n_seg = (int32_t)n_seg;
-    A.T = ls_traj;
-    A.Cend = ls_traj + N * P;
-    A.Tkey = ls_traj + (N + n_seg) * P;
-    hipLaunchKernelGGL(dev::k_support_segments<>, dim3(grid_for((n_seg + dev::WG / 64 - 1) / (dev::WG / 64))), dim3(dev::WG), 0, stream, A);
-    PGOC(check_launch("k_support_segments"));
-    hipLaunchKernelGGL(dev::k_support_keys<>, dim3(1), dim3(dev::WG), 0, stream, A);
-    PGOC(check_launch("k_support_keys"));
-    hipLaunchKernelGGL(dev::k_support_traj<>, dim3(per_lane(N)), dim3(dev::WG), 0, stream, A);
-    PGOC(check_launch("k_support_traj"));
-  }
+  PGOC(support_trajectory_enqueue());
   dev::SupportArgs A;
   A.mx = e_mx;
   A.my = e_my;

@@ -2,6 +2,7 @@
 //     ./main DATASET NUM_OUTLIER_LOOPS METHOD [--seed S] [--data DIR] [--save DIR] [--device D] [--precision P]
 //            [--loss NAME[:A]] [--loop-loss NAME[:A]] [--score FILE [--align]] [--init-stride S [--init-info]] [--gnc CBAR [--gnc-inner K]]
 //            [--loop-support MIN[:WINDOW[:TOL_XY[:TOL_TH]]]]
+//            [--chordal-init [ROUNDS[:REJECT_XY[:REJECT_TH]]]]
 // METHOD 0 = baseline, 1 = DCS, 2 = switchable constraints run on the MI355X backend; 3/4 are outside it (exit code 3).
 // Reads DIR/DATASET.g2o (default ../data, as the reference), writes init_/opt_ nodes+edges text files that
 // drawer/plot_results.py consumes (default ../save; unlike the reference the directory is created).
@@ -51,6 +52,9 @@ int main(int argc, char* argv[]) {
               << "       [--gnc CBAR [--gnc-inner K]]  (METHOD 0 only: graduated non-convexity with the TLS surrogate over the closure and bogus\n"
               << "       blocks, CBAR = the residual norm above which a block is an outlier, K LM iterations per round, default 5; prints the\n"
               << "       rounds and writes weights.txt, one weight per edge in the order of the edges files)\n"
+              << "       [--chordal-init [ROUNDS[:REJECT_XY[:REJECT_TH]]]]  (after --loop-support, before --init-stride: start from the linear\n"
+              << "       relaxation -- chordal rotations, then positions --; ROUNDS > 0 drops the blocks whose residual exceeds REJECT_XY metres\n"
+              << "       or REJECT_TH radians and solves again (METHOD 0 and 1: they stay dropped))\n"
               << "       [--loop-support MIN[:WINDOW[:TOL_XY[:TOL_TH]]]]  (METHOD 0 and 1: before anything else, judge the closure and bogus blocks\n"
               << "       by odometry cycle consistency and drop -- weight 0 -- those with fewer than MIN consistent neighbours within WINDOW\n"
               << "       poses, default 32; tolerances per sqrt(step), default 0.1 m and 0.05 rad: fit them to the dataset's odometry;\n"
@@ -65,7 +69,28 @@ int main(int argc, char* argv[]) {
   double gnc_cbar = 0.0;
   bool gnc_on = false, support_on = false, init_info = false;
   pgo::LoopSupportOptions support;
+  bool chordal_on = false;
+  pgo::ChordalOptions chordal;
   for (int i = 4; i < argc; i += 2) {
+    if (!strcmp(argv[i], "--chordal-init")) {   // [ROUNDS[:REJECT_XY[:REJECT_TH]]]: the value is optional
+      chordal_on = true;
+      if (i + 1 >= argc || !strncmp(argv[i + 1], "--", 2)) {
+        --i;
+        continue;
+      }
+      std::vector<std::string> f;
+      std::string spec = argv[i + 1];
+      for (size_t at = 0; at <= spec.size();) {
+        const size_t colon = std::min(spec.find(':', at), spec.size());
+        f.push_back(spec.substr(at, colon - at));
+        at = colon + 1;
+      }
+      if (f.size() > 3 || f[0].empty()) { std::cerr << "--chordal-init [ROUNDS[:REJECT_XY[:REJECT_TH]]]\n"; return -1; }
+      chordal.rounds = atoi(f[0].c_str());
+      if (f.size() > 1) chordal.reject_xy = atof(f[1].c_str());
+      if (f.size() > 2) chordal.reject_th = atof(f[2].c_str());
+      continue;
+    }
     if (!strcmp(argv[i], "--align")) {   // (the one option without a value)
       score_align = 1;
       --i;
@@ -186,6 +211,15 @@ int main(int argc, char* argv[]) {
                 << support.tol_th << ": " << ss.stats.n_selected << " selected blocks, " << ss.stats.n_supported << " supported, dropped "
                 << drop_clo << " closure and " << drop_bogus << " bogus; " << ss.stats.n_pairs_total << " pairs, at most " << ss.stats.max_pairs
                 << " per block" << std::endl;
+    }
+    if (chordal_on) {   // the linear start: chordal rotations, then positions; the blocks its reject rounds drop stay dropped
+      chordal.apply_weights = chordal.rounds > 0 && method != 2;
+      pgo::ChordalSummary cs;
+      pgo::ChordalInit(options, chordal, &problem, &cs);
+      const pgo_chordal_solve& last = cs.s.solve[cs.s.n_solves - 1];
+      std::cout << "chordal-init: rounds " << chordal.rounds << " reject_xy " << chordal.reject_xy << " reject_th " << chordal.reject_th << ": "
+                << cs.s.n_solves << " solves, " << cs.s.n_rejected << " blocks rejected, " << last.iters[0] << " + " << last.iters[1]
+                << " iterations, min |z| " << cs.s.min_mag << ", " << cs.s.n_degenerate << " degenerate" << std::endl;
     }
     if (init_stride != 0) {   // hierarchical initialisation: the parameter blocks start at the coarse graph's prolonged solution
       pgo::Solver::Options coarse_options;

@@ -213,6 +213,20 @@ struct LoopSupportSummary {
   std::vector<pgo_loop_support_record> blocks;   // per residual block
 };
 
+// An estimate-free linear start (include/pgo.h, "chordal initialisation"; pgo_chordal_init): chordal rotations, then positions
+// given the rotations, from the measurements and the constant blocks alone.  The defaults are pgo_chordal_options_default's.
+struct ChordalOptions {
+  double rtol = 1e-8, mag_min = 1e-3;
+  int max_iters = 20000, check_every = 50;
+  int rounds = 0;                          // reject rounds: after a solve, drop the blocks off the chain whose residual exceeds ...
+  double reject_xy = 2.0, reject_th = 0.35;   // ... these (metres, radians), and solve again
+  bool apply_weights = false;              // true: the dropped blocks get the residual block weight 0
+};
+struct ChordalSummary {
+  pgo_chordal_summary s{};
+  std::vector<double> residuals;           // per residual block: |position residual|, |heading residual|
+};
+
 struct SolverAccess {
   static void check(int st) {
     if (st != PGO_OK) throw std::runtime_error(std::string("pgo: ") + pgo_strerror(st) + ": " + pgo_last_error());
@@ -355,6 +369,35 @@ struct SolverAccess {
     pgo_destroy(h);
     if (st != PGO_OK) throw std::runtime_error(std::string("pgo: ") + pgo_strerror(st) + ": " + msg);
     if (ls.apply) pr->weights_.swap(w);
+  }
+  // the parameter blocks moved, in place, to the chordal start; constant blocks are not moved
+  static void ChordalInit(const Solver::Options& opt, const ChordalOptions& co, Problem* pr, ChordalSummary* sum) {
+    const int32_t N = (int32_t)pr->ptr_.size();
+    const size_t E = pr->ia_.size();
+    pgo_t* h = Prepare(opt, pr);
+    pgo_chordal_options o;
+    pgo_chordal_options_default(&o);
+    o.rtol = co.rtol;
+    o.mag_min = co.mag_min;
+    o.max_iters = co.max_iters;
+    o.check_every = co.check_every;
+    o.rounds = co.rounds;
+    o.reject_xy = co.reject_xy;
+    o.reject_th = co.reject_th;
+    o.apply_weights = co.apply_weights ? 1 : 0;
+    o.commit = 1;
+    ChordalSummary local;
+    ChordalSummary* cs = sum ? sum : &local;
+    cs->residuals.assign(2 * E, 0.0);
+    std::vector<double> poses((size_t)3 * N), w(E, 1.0);
+    int st = pgo_chordal_init(h, &o, poses.data(), E ? cs->residuals.data() : nullptr, &cs->s);
+    if (st == PGO_OK && co.apply_weights && E > 0) st = pgo_get_edge_weights(h, w.data());
+    const std::string msg = st != PGO_OK ? std::string(pgo_last_error()) : std::string();
+    pgo_destroy(h);
+    if (st != PGO_OK) throw std::runtime_error(std::string("pgo: ") + pgo_strerror(st) + ": " + msg);
+    for (int32_t i = 0; i < N; ++i)
+      for (int k = 0; k < 3; ++k) pr->ptr_[i][k] = poses[3 * (size_t)i + k];
+    if (co.apply_weights) pr->weights_.swap(w);
   }
   // Hierarchical initialisation (include/pgo.h): the problem's graph coarsened at `stride`, the coarse graph solved exactly (the
   // problem's METHOD, pcg_rtol 1e-10, everything else left to the library; a constant block that is a key pose stays the
@@ -539,6 +582,12 @@ inline void SolveGnc(const Solver::Options& opt, const GncOptions& gnc, Problem*
 // block weights, which every Solve, SolveGnc and InitializeHierarchical that follows honours
 inline void LoopSupport(const Solver::Options& opt, const LoopSupportOptions& options, Problem* problem, LoopSupportSummary* summary) {
   SolverAccess::LoopSupport(opt, options, problem, summary);
+}
+// The parameter blocks moved, in place, to the chordal start (pgo_chordal_init: no estimate plays a part except on the constant
+// blocks); the problem's residual block weights are honoured, and with options.apply_weights the blocks the reject rounds
+// dropped get the weight 0.  Call Solve next.
+inline void ChordalInit(const Solver::Options& opt, const ChordalOptions& options, Problem* problem, ChordalSummary* summary = nullptr) {
+  SolverAccess::ChordalInit(opt, options, problem, summary);
 }
 // many independent problems at once; summaries->size() == problems.size() afterwards
 inline void SolveBatch(const Solver::Options& opt, const std::vector<Problem*>& problems, std::vector<Solver::Summary>* summaries,
