@@ -1138,6 +1138,18 @@ int pgo_debug_system_spmv(pgo_t* h, const double* x, double* y, double* d2_or_nu
  * PGO_ERR_UNSUPPORTED on a handle that is not on the direct solve (pgo_handle_info.linear_solver), PGO_ERR_INVALID_ARG
  * for a null pointer, refine_steps outside -1 .. 3 or a handle without pgo_lm_begin.                                    */
 int pgo_debug_direct_solve(pgo_t* h, const double* b_3n, int32_t refine_steps, double* y_3n);   /* [gpu] */
+/* The linear solve of ONE LM iteration of every problem of a batch, through the launch a pgo_batch_solve iteration runs (one
+ * workgroup per problem), at the batch's current poses: the set-up of the solve's start (unit scales, Jacobi scales from this
+ * Jacobian), `radius` for every problem, at most max_it PCG iterations to |r| <= rtol |b| for every problem, all of them active.
+ * rhs, y_out: the problems' unknowns concatenated in problem order, 3 n_k doubles each in each problem's own pose numbering,
+ * scaled space (the conventions of pgo_debug_system_spmv); rhs == NULL: the scaled gradient, as LM solves.  The rows of each
+ * problem's constant pose must be 0 in rhs.  res[k]: the PCG state of problem k at exit and the sums of the step's epilogue
+ * (y.b, y.(H y) without the LM diagonal, |S y|^2).  Poses, per-problem LM state, records, losses / weights / active set are
+ * untouched: a pgo_batch_solve afterwards returns bitwise what it returns without the call.
+ * PGO_ERR_INVALID_ARG: a null b / y_out / res, radius not finite or <= 0, max_it outside 0 .. 1000000, rtol negative or not finite. */
+typedef struct pgo_solo_result { double rz, bb, rr, ydotg, yHy, step2; int32_t iters, done; } pgo_solo_result;
+int pgo_batch_debug_solve(pgo_batch_t* b, double radius, int32_t max_it, double rtol,
+                          const double* rhs_or_null, double* y_out, pgo_solo_result* res /* n */);   /* [gpu] */
 /* normal-equation pieces at the current point, caller's pose order (world == 1):
  * g: 3N gradient J'r (unscaled), hdiag: N x 9 diagonal 3x3 blocks of J'J; 0 on the constant pose.  The call re-evaluates the
  * residuals at the current poses, resets the pose scales to 1 and ends the solve begun with pgo_lm_begin.

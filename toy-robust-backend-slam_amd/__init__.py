@@ -21,7 +21,7 @@ import numpy as np
 from . import _build
 
 __all__ = ["PgoError", "Options", "Summary", "IterRecord", "ReadG2O", "Graph", "Solver", "Batch", "Comm", "lib", "build",
-           "HandleInfo", "synth_manhattan", "solve_batch", "shard_plan", "shard_halo", "pose_order", "set_knob", "KernelStats", "EXPORTS", "TERMINATION",
+           "HandleInfo", "synth_manhattan", "solve_batch", "shard_plan", "shard_halo", "pose_order", "set_knob", "KernelStats", "SoloResult", "EXPORTS", "TERMINATION",
            "CovarianceOptions", "CovarianceReport", "Loss", "LOSS_TYPES", "active_plan", "EdgeGateResult", "gate_evaluate",
            "GateJointOptions", "GateJointResult", "GateJointSummary", "gate_joint_evaluate", "GATE_JOINT_MAX",
            "window_plan", "WindowResult", "WINDOW_MAX_POSES", "WINDOW_MAX_EDGES", "WINDOW_MAX_ITERS",
@@ -50,6 +50,7 @@ EXPORTS = [
     "pgo_num_iter_records", "pgo_get_iter_records", "pgo_get_info", "pgo_get_poses", "pgo_set_poses", "pgo_get_switches",
     "pgo_write_switches",
     "pgo_bench_eval", "pgo_bench_assemble", "pgo_bench_spmv", "pgo_bench_precond", "pgo_debug_precond", "pgo_debug_spmv", "pgo_debug_system_spmv", "pgo_debug_direct_solve", "pgo_debug_normal_eq",
+    "pgo_batch_debug_solve",
     "pgo_debug_set_knob",
     "pgo_shard_plan", "pgo_shard_halo", "pgo_pose_order",
     "pgo_covariance_options_default", "pgo_pose_covariance",
@@ -137,6 +138,15 @@ class HandleInfo(C.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class SoloResult(C.Structure):
+    """mirror of pgo_solo_result"""
+    _fields_ = [("rz", C.c_double), ("bb", C.c_double), ("rr", C.c_double), ("ydotg", C.c_double), ("yHy", C.c_double),
+                ("step2", C.c_double), ("iters", C.c_int32), ("done", C.c_int32)]
+
+    def as_dict(self):
+        return {f[0]: getattr(self, f[0]) for f in self._fields_}
 
 
 class KernelStats(C.Structure):
@@ -478,6 +488,7 @@ def lib():
     L.pgo_debug_system_spmv.argtypes = [vp, dp, dp, dp]
     L.pgo_debug_direct_solve.argtypes = [vp, dp, C.c_int32, dp]
     L.pgo_debug_normal_eq.argtypes = [vp, dp, dp]
+    L.pgo_batch_debug_solve.argtypes = [vp, C.c_double, C.c_int32, C.c_double, dp, dp, C.POINTER(SoloResult)]
     L.pgo_shard_plan.argtypes = [C.c_int32, C.c_int32, ip, ip, C.c_int, C.c_int, C.c_int, ip, ip, ip, ip]
     L.pgo_shard_halo.argtypes = [C.c_int32, C.c_int32, ip, ip, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64),
                                  C.POINTER(C.c_int64)]
@@ -1136,6 +1147,24 @@ class Batch:
     def set_poses(self, k: int, poses):
         p = np.ascontiguousarray(poses, np.float64)
         _check(lib().pgo_batch_set_poses(self._h, k, _dp(p)))
+
+    def debug_solve(self, radius, max_it, rtol, rhs=None):
+        """pgo_batch_debug_solve: the one-workgroup PCG solve of every problem at the current poses.  rhs: None (the scaled
+        gradient), the concatenated right-hand side, or a list with one array of 3 n_k per problem.
+        Returns (list of y arrays per problem, list of result dicts)."""
+        sizes = [3 * g.n_poses for g in self.graphs]
+        b = None
+        if rhs is not None:
+            if isinstance(rhs, (list, tuple)):
+                rhs = np.concatenate([np.asarray(v, np.float64).reshape(-1) for v in rhs])
+            b = np.ascontiguousarray(rhs, np.float64).reshape(-1)
+            if b.size != sum(sizes):
+                raise ValueError("rhs: 3 n_k doubles per problem")
+        y = np.zeros(sum(sizes))
+        res = (SoloResult * max(self.n, 1))()
+        _check(lib().pgo_batch_debug_solve(self._h, float(radius), int(max_it), float(rtol), _dp(b) if b is not None else None,
+                                           _dp(y), res))
+        return np.split(y, np.cumsum(sizes)[:-1]), [res[i].as_dict() for i in range(self.n)]
 
     def iter_records(self, k: int):
         n = lib().pgo_batch_num_iter_records(self._h, k)

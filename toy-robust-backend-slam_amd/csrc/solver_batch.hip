@@ -42,23 +42,50 @@ struct pgo_batch {
     HIPC(hipMemcpyAsync(h_sums.data(), d_sums, (size_t)n * sizeof(dev::ProbSums), hipMemcpyDeviceToHost, H.stream));
     return H.sync();
   }
+  int linearize();
   int begin();
   int iterate(bool* all_done);
+  dev::SoloArgs solo_args(const double* b) const;
 };
+
+// iteration 0 at the current poses: unit scales -> column norms -> Jacobi scaling (per column, so per problem by construction)
+int pgo_batch::linearize() {
+  pgo_handle& H = *U;
+  PGOC(H.launch_jacobi_scale(0));
+  PGOC(H.eval_enqueue(H.poses, nullptr, 1, true, 0));
+  PGOC(H.assemble_enqueue());
+  if (H.opt.jacobi_scaling) {
+    PGOC(H.launch_jacobi_scale(1));
+    PGOC(H.assemble_enqueue());
+  }
+  return PGO_OK;
+}
+
+// the one-workgroup PCG's arguments: right-hand side b, the epilogue's candidate poses into H.cand
+dev::SoloArgs pgo_batch::solo_args(const double* b) const {
+  const pgo_handle& H = *U;
+  dev::SoloArgs A;
+  A.A = H.spmv_args(H.p_full, H.ap, H.part[0], 1, nullptr);
+  A.V = H.cg_vec();
+  A.C = H.chain_pre();
+  if (!H.plan.all.chain_len) A.C.cw = nullptr;
+  A.chain_steps = H.plan.all.solo_steps;
+  A.scan_levels = H.plan.all.solo_scan;
+  A.b = b;
+  A.prob = d_prob;
+  A.out = d_out;
+  A.x = H.poses;
+  A.scale = H.scale;
+  A.cand = H.cand;
+  return A;
+}
 
 int pgo_batch::begin() {
   pgo_handle& H = *U;
   HIPC(hipSetDevice(H.device));
   const pgo_options& o = H.opt;
   for (State& z : st) z = State();
-  // iteration 0: unit scales -> column norms -> Jacobi scaling (per column, so per problem by construction)
-  PGOC(H.launch_jacobi_scale(0));
-  PGOC(H.eval_enqueue(H.poses, nullptr, 1, true, 0));
-  PGOC(H.assemble_enqueue());
-  if (o.jacobi_scaling) {
-    PGOC(H.launch_jacobi_scale(1));
-    PGOC(H.assemble_enqueue());
-  }
+  PGOC(linearize());
   PGOC(reduce(true, true, H.poses));
   for (int k = 0; k < n; ++k) {
     State& z = st[k];
@@ -103,20 +130,7 @@ int pgo_batch::iterate(bool* all_done) {
   HIPC(hipMemcpyAsync(d_prob, h_prob.data(), (size_t)n * sizeof(dev::SoloProb), hipMemcpyHostToDevice, H.stream));
   HIPC(hipMemcpyAsync(H.prob_radius, h_radius.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, H.stream));
   PGOC(H.prepare_system(0.0));   // (not read: k_prepare takes every problem's radius from prob_radius, uploaded above)
-  dev::SoloArgs A;
-  A.A = H.spmv_args(H.p_full, H.ap, H.part[0], 1, nullptr);
-  A.V = H.cg_vec();
-  A.C = H.chain_pre();
-  if (!H.plan.all.chain_len) A.C.cw = nullptr;
-  A.chain_steps = H.plan.all.solo_steps;
-  A.scan_levels = H.plan.all.solo_scan;
-  A.b = H.gs;
-  A.prob = d_prob;
-  A.out = d_out;
-  A.x = H.poses;
-  A.scale = H.scale;
-  A.cand = H.cand;
-  hipLaunchKernelGGL(dev::k_pcg_solo<>, dim3(n), dim3(dev::SOLO_WG), 0, H.stream, A);
+  hipLaunchKernelGGL(dev::k_pcg_solo<>, dim3(n), dim3(dev::SOLO_WG), 0, H.stream, solo_args(H.gs));
   PGOC(H.check_launch("k_pcg_solo"));
   HIPC(hipMemcpyAsync(h_out.data(), d_out, (size_t)n * sizeof(dev::SoloOut), hipMemcpyDeviceToHost, H.stream));
   // candidate cost of every problem (the rows of idle problems: cand was not written this iteration -- never read below)
@@ -445,6 +459,70 @@ int pgo_batch_window_solve(pgo_batch_t* b, int32_t nw, const int32_t* problem, c
   PGOC(H.window_solve(who.c_str(), nw, pose_ptr, pi.empty() ? &none : pi.data(), edge_ptr, ei.empty() ? &none : ei.data(), an.data(),
                       max_iters, commit, poses_out, results, records));
   if (commit) b->begun = false;
+  return PGO_OK;
+}
+
+// Test hook: the linear solve of one LM iteration of every problem, as iterate() launches it, on the caller's right-hand side,
+// radius, iteration cap and tolerance.  The set-up is begin()'s; the per-problem LM state, the records, h_prob and the poses are
+// not touched (the solo arguments go to the device from a copy; d_prob, prob_radius and every vector the kernel writes are
+// rewritten by the next iterate() before they are read), so a pgo_batch_solve afterwards starts from begin() as it always does.
+int pgo_batch_debug_solve(pgo_batch_t* b, double radius, int32_t max_it, double rtol, const double* rhs, double* y_out,
+                          pgo_solo_result* res) {
+  if (!b || !y_out || !res) return fail(PGO_ERR_INVALID_ARG, "pgo_batch_debug_solve: null");
+  if (!std::isfinite(radius) || radius <= 0.0) return fail(PGO_ERR_INVALID_ARG, "pgo_batch_debug_solve: radius must be finite and > 0");
+  if (max_it < 0 || max_it > 1000000) return fail(PGO_ERR_INVALID_ARG, "pgo_batch_debug_solve: max_it is 0 .. 1000000");
+  if (!std::isfinite(rtol) || rtol < 0.0) return fail(PGO_ERR_INVALID_ARG, "pgo_batch_debug_solve: rtol must be finite and >= 0");
+  pgo_handle& H = *b->U;
+  HIPC(hipSetDevice(H.device));
+  const int32_t n = b->n;
+  const size_t n3 = (size_t)3 * H.S.n_loc;
+  std::vector<dev::SoloProb> prob(b->h_prob);
+  for (dev::SoloProb& P : prob) {
+    P.active = 1;
+    P.max_it = max_it;
+    P.rtol = rtol;
+  }
+  const std::vector<double> rad((size_t)n, radius);
+  std::vector<double> v;   // rhs on the way in (the union's rows, 0 on the padding rows), y on the way out
+  double* d_b = nullptr;
+  if (rhs) {
+    v.assign(n3, 0.0);
+    size_t off = 0;
+    for (int32_t k = 0; k < n; ++k) {
+      memcpy(&v[(size_t)3 * b->row0[k]], rhs + off, (size_t)3 * b->npos[k] * sizeof(double));
+      off += (size_t)3 * b->npos[k];
+    }
+    if (hipMalloc((void**)&d_b, n3 * sizeof(double)) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(PGO_ERR_NOMEM, "pgo_batch_debug_solve: hipMalloc");
+    }
+  }
+  std::vector<dev::SoloOut> out((size_t)n);
+  auto run = [&]() -> int {
+    if (d_b) HIPC(hipMemcpyAsync(d_b, v.data(), n3 * sizeof(double), hipMemcpyHostToDevice, H.stream));
+    PGOC(b->linearize());
+    HIPC(hipMemcpyAsync(b->d_prob, prob.data(), (size_t)n * sizeof(dev::SoloProb), hipMemcpyHostToDevice, H.stream));
+    HIPC(hipMemcpyAsync(H.prob_radius, rad.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, H.stream));
+    PGOC(H.prepare_system(0.0));   // (every problem's radius comes from prob_radius)
+    hipLaunchKernelGGL(dev::k_pcg_solo<>, dim3(n), dim3(dev::SOLO_WG), 0, H.stream, b->solo_args(d_b ? d_b : H.gs));
+    PGOC(H.check_launch("k_pcg_solo"));
+    HIPC(hipMemcpyAsync(out.data(), b->d_out, (size_t)n * sizeof(dev::SoloOut), hipMemcpyDeviceToHost, H.stream));
+    PGOC(H.sync());   // (v is read by the upload above until here)
+    v.resize(n3);
+    HIPC(hipMemcpyAsync(v.data(), H.y, n3 * sizeof(double), hipMemcpyDeviceToHost, H.stream));
+    return H.sync();
+  };
+  const int st = run();
+  if (st != PGO_OK) (void)hipStreamSynchronize(H.stream);
+  if (d_b) (void)hipFree(d_b);
+  PGOC(st);
+  size_t off = 0;
+  for (int32_t k = 0; k < n; ++k) {
+    memcpy(y_out + off, &v[(size_t)3 * b->row0[k]], (size_t)3 * b->npos[k] * sizeof(double));
+    off += (size_t)3 * b->npos[k];
+    const dev::SoloOut& q = out[k];
+    res[k] = pgo_solo_result{q.rz, q.bb, q.rr, q.ydotg, q.yHy, q.step2, q.iters, q.done};
+  }
   return PGO_OK;
 }
 
