@@ -852,6 +852,118 @@ int  pgo_gnc_update(pgo_t* h, double cbar, double mu, const uint8_t* select_or_n
 int  pgo_gnc_solve(pgo_t* h, const pgo_gnc_options* opt, pgo_gnc_summary* summary_or_null,
                    pgo_gnc_round* rounds_or_null, int32_t rounds_cap);                                            /* [gpu] */
 
+/* ---------------------------------------------------------------- max-mixture edges
+ * Max-Mixtures (Olson & Agarwal, RSS 2012 / IJRR 2013): an edge that is ONE OF SEVERAL measurements -- a loop closure that
+ * matches either of two corridors, an odometry step that happened or slipped, an inlier beside a wide null hypothesis.  Per
+ * edge and per linearisation point the most likely component is selected, and an ordinary Gaussian problem is optimised.  On a
+ * live handle the component of an edge is its entries of the measurement planes and of the edge weight plane; csrc/mixture.h is
+ * the one statement:
+ * - A mixture edge is an edge of the handle (caller's edge numbering) with K components, 1 <= K <= PGO_MIX_MAX_COMPONENTS.
+ *   Component k has a mean meas = (x, y, theta), a mixing weight weight = pi_k > 0 (relative: the weights need not sum to 1)
+ *   and an information scale info_scale = w_k in (0, 1]: in the handle's unit-information objective its information is w_k I.
+ *   Its constant is c_k = -log(pi_k) - 1.5 log(w_k), computed once on the host in double.
+ * - At poses x, s_k(x) is the plain |e|^2 for the measurement m_k -- the s_plain of pgo_edge_weights, heading asin(sin delta) --
+ *   and q_k(x) = w_k 1/2 rho(s_k) + c_k with rho the loss of the edge's loss class (pgo_set_losses).  A component whose s_k is
+ *   not finite has no q_k (NaN), whatever the loss.
+ * - Selection: k* = argmin q_k over the components with a finite q_k, ties to the lowest index.  Without a finite component
+ *   the edge keeps the selection it has and is counted in n_nonfinite.
+ * - Applying a selection writes m_k* into the edge's measurement planes and w_k* into its entry of the edge weight plane, which
+ *   is allocated at all ones at its first use (as pgo_gnc_update).
+ * Because q_k is stated with the handle's own loss and weight, F(x) = pgo_eval's cost under the applied selection + the sum of
+ * c_k* over the (active) mixture edges is non-increasing from round to round of pgo_mixture_solve, for any loss: with the
+ * selection fixed LM never raises its cost, and re-selecting at the new poses never raises any edge's q.
+ *
+ * pgo_set_mixtures stores the table: edge[n_mix] strictly ascending, comp_ptr[n_mix + 1] the CSR offsets into comps
+ * (comp_ptr[0] = 0).  No selection is applied yet and no plane is touched.  n_mix = 0 clears: the measurement planes of the
+ * former mixture edges are restored bitwise to what the handle was created with, their weights (if a plane is set) become 1,
+ * the table is dropped; after it and pgo_set_edge_weights(h, NULL), pgo_solve gives bitwise what a fresh handle gives.  Setting
+ * a new table over an old one clears the old one first.
+ * pgo_set_mixture_null is the classic robust use without a host table: every selected edge -- the active edges with kind !=
+ * PGO_EDGE_ODOMETRY, or the active edges with a non-zero byte in select (E bytes) -- gets two components at the mean it was
+ * created with, (pi = 1, w = 1) and (pi_null, scale_null): exactly the table pgo_set_mixtures would be given, in ascending
+ * edge order.  No selected edge, or a (pi_null, scale_null) that no component may have: PGO_ERR_INVALID_ARG.
+ *
+ * pgo_mixture_select runs the selection at the handle's current poses.  apply = 0 measures only: nothing is written and no
+ * plane is created.  chosen_or_null[n_mix] receives the component per mixture edge (an edge that was not evaluated: the
+ * selection it has, -1 where none); q_or_null[2 n_mix] receives q_best and the margin q_second - q_best (+inf with one finite
+ * component; NaN for both on an edge that was not evaluated).  stats: n_mix; n_changed, against the previous APPLIED selection
+ * (the first apply counts every evaluated edge); n_nonfinite; n_inactive -- edges masked by pgo_set_active keep their selection
+ * and their planes and count only here; offset = the sum of c_k* and mix_cost = the sum of q_k* over the evaluated edges;
+ * count[k] = the evaluated edges on component k.  One lane per mixture edge, per-chunk partials folded by one workgroup in
+ * fixed order, no atomics: two calls are bitwise equal, and neither the launch grid ("mix_grid") nor pose_ordering plays a
+ * part.  An applying select makes a solve begun with pgo_lm_begin stale, as pgo_gnc_update does (it rewrites the weights of
+ * its edges whether or not the selection moved: another writer may have been there).
+ * pgo_get_mixture_selection: the last applied selection per mixture edge, -1 where none.
+ *
+ * pgo_mixture_solve, METHOD 0, from the handle's current poses, under the handle's own options and losses.  A round:
+ *   1. select + apply;  2. the round's record {objective F, n_changed, count[], lm_iterations, lm_termination, seconds} (the LM
+ *   figures are those of step 4);  3. stop if this is not the first round and n_changed == 0;  4. pgo_lm_begin and up to
+ *   inner_iters LM iterations.
+ * After the stop, or after max_rounds rounds (hit_max_rounds = 1), one solve of final_iters, then one measuring select whose
+ * n_changed goes to n_would_change.  (An LM solve also ends at the handle's own max_iters, whichever is smaller.)  An inner
+ * solve that ends with PGO_TERM_FAILURE ends the call with PGO_ERR_NUMERIC; the poses are those of the last good round.
+ *
+ * Host only: pgo_mixture_eval is the statement on given s[n_comp] under one loss (NULL: Trivial); chosen = -1 and NaN when no
+ * component is finite.  pgo_mixture_plan is the whole select on arrays, serially, the sums in the caller's mixture order:
+ * mix_class[n_mix] is each mixture edge's loss class (NULL: class 0; losses NULL: Trivial), prev_or_null the previous applied
+ * selection (NULL: none, -1), active_or_null a byte per mixture edge (NULL: all active).
+ *
+ * Interplay: pgo_set_edge_weights and pgo_gnc_update may overwrite a mixture edge's weight and the next applied select
+ * overwrites it again -- last writer wins.  pgo_set_losses and pgo_set_active leave the table and the selection alone.
+ * pgo_window_solve stays PGO_ERR_UNSUPPORTED while a plane is set.  Everything that reads the planes -- pgo_eval and the solves,
+ * pgo_edge_weights, the covariances and the gates, pgo_coarsen, pgo_loop_support, pgo_chordal_init -- sees the selected problem
+ * (an apply that changes a measurement drops the trajectory pgo_loop_support keeps and the composites pgo_prolong relies on).
+ * Errors: PGO_ERR_INVALID_ARG for a null pointer, an edge list that is not strictly ascending or out of range, K outside 1 ..
+ * 8, a mean that is not finite, a weight that is not finite or <= 0, an info_scale that is not finite or outside (0, 1]
+ * (pgo_last_error names the first offending edge), pgo_mixture_select / pgo_mixture_solve / pgo_get_mixture_selection without
+ * a table, inner_iters / final_iters / max_rounds < 1; PGO_ERR_UNSUPPORTED for METHOD 1 or 2, info_weighting = 1, a
+ * communicator or PGO_FORCE_COLLECTIVES=1, a batched handle.  Nothing changes on error.                                        */
+#define PGO_MIX_MAX_COMPONENTS 8
+typedef struct pgo_mix_component {
+  double meas[3];      /* the mean (x, y, theta) */
+  double weight;       /* pi_k > 0, relative */
+  double info_scale;   /* w_k in (0, 1] */
+} pgo_mix_component;
+typedef struct pgo_mix_stats {
+  int32_t n_mix, n_changed, n_nonfinite, n_inactive;
+  double  offset;      /* sum of c_k* over the evaluated edges */
+  double  mix_cost;    /* sum of q_k* over the evaluated edges */
+  int32_t count[PGO_MIX_MAX_COMPONENTS];
+} pgo_mix_stats;
+typedef struct pgo_mixture_options {
+  int32_t inner_iters;    /* 2 */
+  int32_t final_iters;    /* 50 */
+  int32_t max_rounds;     /* 50 */
+  int32_t _pad;
+} pgo_mixture_options;
+typedef struct pgo_mixture_round {
+  double  objective;      /* F = pgo_eval's cost under the round's selection + offset */
+  int32_t n_changed, lm_iterations, lm_termination, _pad;
+  int32_t count[PGO_MIX_MAX_COMPONENTS];
+  double  seconds;        /* the round's wall time: select + inner solve */
+} pgo_mixture_round;
+typedef struct pgo_mixture_summary {
+  int32_t rounds, hit_max_rounds;
+  int32_t n_mix, n_would_change;    /* n_changed of a measuring select at the final poses */
+  double  objective, offset;        /* F and the sum of c_k* at the final poses, under the selection in force */
+  double  seconds_total;
+  pgo_summary final_solve;
+} pgo_mixture_summary;
+void pgo_mixture_options_default(pgo_mixture_options*);                                                           /* [host] */
+int  pgo_mixture_eval(int32_t n_comp, const pgo_mix_component* comps, const double* s, const pgo_loss* loss_or_null,
+                      int32_t* chosen, double* q_best, double* margin);                                           /* [host] */
+int  pgo_mixture_plan(int32_t n_poses, const double* poses, int32_t n_edges, const int32_t* ia, const int32_t* ib,
+                      int32_t n_mix, const int32_t* edge, const int32_t* comp_ptr, const pgo_mix_component* comps,
+                      int32_t n_classes, const pgo_loss* losses_or_null, const uint8_t* mix_class_or_null,
+                      const int32_t* prev_or_null, const uint8_t* active_or_null,
+                      int32_t* chosen /* n_mix */, double* q /* 2 n_mix */, pgo_mix_stats* stats_or_null);         /* [host] */
+int  pgo_set_mixtures(pgo_t* h, int32_t n_mix, const int32_t* edge, const int32_t* comp_ptr, const pgo_mix_component* comps); /* [gpu] */
+int  pgo_set_mixture_null(pgo_t* h, const uint8_t* select_or_null, double pi_null, double scale_null);            /* [gpu] */
+int  pgo_mixture_select(pgo_t* h, int32_t apply, pgo_mix_stats* stats_or_null, int32_t* chosen_or_null, double* q_or_null); /* [gpu] */
+int  pgo_get_mixture_selection(pgo_t* h, int32_t* chosen_out /* n_mix */);                                        /* [gpu] */
+int  pgo_mixture_solve(pgo_t* h, const pgo_mixture_options* opt_or_null, pgo_mixture_summary* summary_or_null,
+                       pgo_mixture_round* rounds_or_null, int32_t rounds_cap);                                    /* [gpu] */
+
 /* ---------------------------------------------------------------- loop support (odometry cycle consistency)
  * Judge loop edges WITHOUT looking at the estimate: two loop closures taken a few steps apart must close a 4-cycle through the
  * odometry between their ends (the pairwise check of PCM / RRR, restricted to neighbours along the chain, where the odometry
@@ -1192,6 +1304,8 @@ int pgo_debug_normal_eq(pgo_t* h, double* g_or_null, double* hdiag_or_null);    
  *                        results are bitwise the same)
  *   "chordal_grid"       n > 0 = pgo_chordal_init launches n workgroups over its tiles of 256 rows and chunks of 256 edges instead
  *                        of one per unit of work (read per call; the results are bitwise the same)
+ *   "mix_grid"           n > 0 = pgo_mixture_select (and pgo_mixture_solve through it) launches n workgroups over its chunks of
+ *                        256 mixture edges (read per call; the results are bitwise the same)
  * Unknown name: PGO_ERR_INVALID_ARG.                                                                     */
 int pgo_debug_set_knob(const char* name, long long value);                        /* [host] */
 /* sharding plan of a graph over `world` ranks: for rank r, rows [lo, hi) and the

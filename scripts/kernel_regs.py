@@ -12,7 +12,7 @@ def rows(txt, pat):
     for blk in txt.split("  - .agpr_count:")[1:]:
         g = lambda k: (re.search(r"\.%s:\s+(\S+)" % k, blk) or [None, "?"])[1]
         name = g("name")
-        if pat and not re.search(pat, name):
+        if pat and not re.search(pat, name, re.I):
             continue
         print("%-90s vgpr %4s agpr %3s sgpr %3s spill %3s scratch %4s lds %6s" % (
             name.replace("_ZN3pgo3dev", "")[:90], g("vgpr_count"), blk.split()[0], g("sgpr_count"), g("vgpr_spill_count"),

@@ -29,7 +29,8 @@ __all__ = ["PgoError", "Options", "Summary", "IterRecord", "ReadG2O", "Graph", "
            "coarsen_plan", "coarsen_info_plan", "prolong_eval", "COARSEN_MIN_STRIDE", "COARSEN_MAX_STRIDE",
            "gnc_weight_eval", "GncStats", "GncOptions", "GncRound", "GncSummary",
            "loop_support_plan", "LoopSupportOptions", "LoopSupportRecord", "LoopSupportStats", "LOOP_SUPPORT_MAX_WINDOW",
-           "chordal_plan", "ChordalOptions", "ChordalSolve", "ChordalSummary", "CHORDAL_MAX_ROUNDS"]
+           "chordal_plan", "ChordalOptions", "ChordalSolve", "ChordalSummary", "CHORDAL_MAX_ROUNDS",
+           "mixture_eval", "mixture_plan", "MixStats", "MixtureOptions", "MixtureRound", "MixtureSummary", "MIX_MAX_COMPONENTS"]
 
 EDGE_ODOMETRY, EDGE_CLOSURE, EDGE_BOGUS = 0, 1, 2
 TERMINATION = {1: "CONVERGENCE_FTOL", 2: "CONVERGENCE_GTOL", 3: "CONVERGENCE_PTOL", 4: "NO_CONVERGENCE",
@@ -64,7 +65,10 @@ EXPORTS = [
     "pgo_set_edge_weights", "pgo_get_edge_weights", "pgo_gnc_options_default", "pgo_gnc_weight_eval", "pgo_gnc_update", "pgo_gnc_solve",
     "pgo_loop_support_options_default", "pgo_loop_support_plan", "pgo_loop_support",
     "pgo_chordal_options_default", "pgo_chordal_plan", "pgo_chordal_init",
+    "pgo_mixture_options_default", "pgo_mixture_eval", "pgo_mixture_plan", "pgo_set_mixtures", "pgo_set_mixture_null",
+    "pgo_mixture_select", "pgo_get_mixture_selection", "pgo_mixture_solve",
 ]
+MIX_MAX_COMPONENTS = 8   # PGO_MIX_MAX_COMPONENTS
 CHORDAL_MAX_ROUNDS = 8   # PGO_CHORDAL_MAX_ROUNDS
 LOOP_SUPPORT_MAX_WINDOW = 256   # PGO_LOOP_SUPPORT_MAX_WINDOW
 COARSEN_MIN_STRIDE, COARSEN_MAX_STRIDE = 2, 256   # PGO_COARSEN_*_STRIDE (include/pgo.h)
@@ -328,6 +332,50 @@ class GncSummary(C.Structure):
         return d
 
 
+class MixStats(C.Structure):
+    """mirror of pgo_mix_stats: what Solver.mixture_select measured over the mixture edges"""
+    _fields_ = [("n_mix", C.c_int32), ("n_changed", C.c_int32), ("n_nonfinite", C.c_int32), ("n_inactive", C.c_int32),
+                ("offset", C.c_double), ("mix_cost", C.c_double), ("count", C.c_int32 * 8)]
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_ if n != "count"}
+        d["count"] = list(self.count)
+        return d
+
+
+class MixtureOptions(C.Structure):
+    """mirror of pgo_mixture_options (defaults: pgo_mixture_options_default)"""
+    _fields_ = [("inner_iters", C.c_int32), ("final_iters", C.c_int32), ("max_rounds", C.c_int32), ("_pad", C.c_int32)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().pgo_mixture_options_default(C.byref(self))
+        for k, v in kw.items():
+            if k not in ("inner_iters", "final_iters", "max_rounds"):
+                raise TypeError("unknown mixture option " + k)
+            setattr(self, k, v)
+
+
+class MixtureRound(C.Structure):
+    _fields_ = [("objective", C.c_double), ("n_changed", C.c_int32), ("lm_iterations", C.c_int32), ("lm_termination", C.c_int32),
+                ("_pad", C.c_int32), ("count", C.c_int32 * 8), ("seconds", C.c_double)]
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_ if n not in ("count", "_pad")}
+        d["count"] = list(self.count)
+        return d
+
+
+class MixtureSummary(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("hit_max_rounds", C.c_int32), ("n_mix", C.c_int32), ("n_would_change", C.c_int32),
+                ("objective", C.c_double), ("offset", C.c_double), ("seconds_total", C.c_double), ("final_solve", Summary)]
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_ if n != "final_solve"}
+        d["final_solve"] = self.final_solve.as_dict()
+        return d
+
+
 class LoopSupportOptions(C.Structure):
     """mirror of pgo_loop_support_options (defaults: pgo_loop_support_options_default)"""
     _fields_ = [("window", C.c_int32), ("min_support", C.c_int32), ("apply", C.c_int32), ("_pad", C.c_int32),
@@ -547,6 +595,16 @@ def lib():
     L.pgo_chordal_options_default.restype = None
     L.pgo_chordal_plan.argtypes = [C.c_int32, C.c_int32, ip, ip, dp, dp, bp, dp, C.POINTER(ChordalOptions), dp, dp, dp, C.POINTER(ChordalSummary)]
     L.pgo_chordal_init.argtypes = [vp, C.POINTER(ChordalOptions), dp, dp, C.POINTER(ChordalSummary)]
+    L.pgo_mixture_options_default.argtypes = [C.POINTER(MixtureOptions)]
+    L.pgo_mixture_options_default.restype = None
+    L.pgo_mixture_eval.argtypes = [C.c_int32, dp, dp, C.POINTER(Loss), ip, dp, dp]
+    L.pgo_mixture_plan.argtypes = [C.c_int32, dp, C.c_int32, ip, ip, C.c_int32, ip, ip, dp, C.c_int32, C.POINTER(Loss), bp, ip, bp, ip, dp,
+                                   C.POINTER(MixStats)]
+    L.pgo_set_mixtures.argtypes = [vp, C.c_int32, ip, ip, dp]
+    L.pgo_set_mixture_null.argtypes = [vp, bp, C.c_double, C.c_double]
+    L.pgo_mixture_select.argtypes = [vp, C.c_int32, C.POINTER(MixStats), ip, dp]
+    L.pgo_get_mixture_selection.argtypes = [vp, ip]
+    L.pgo_mixture_solve.argtypes = [vp, C.POINTER(MixtureOptions), C.POINTER(MixtureSummary), C.POINTER(MixtureRound), C.c_int32]
     _LIB = L
     return L
 
@@ -732,6 +790,55 @@ def gnc_weight_eval(cbar, mu, s):
     out = np.zeros(s.shape)
     _check(lib().pgo_gnc_weight_eval(float(cbar), float(mu), s.size, _dp(s.reshape(-1)), _dp(out.reshape(-1))))
     return out
+
+
+def _mix_table(edge, comp_ptr, comps):
+    """a mixture table as the C-ABI takes it: edge [n] and comp_ptr [n + 1] as int32, comps as an (n_comp, 5) array of
+    (x, y, theta, weight, info_scale) rows (pgo_mix_component)"""
+    edge = np.ascontiguousarray(edge, np.int32).reshape(-1)
+    comp_ptr = np.ascontiguousarray(comp_ptr, np.int32).reshape(-1)
+    comps = np.ascontiguousarray(comps, np.float64).reshape(-1, 5)
+    if comp_ptr.size != edge.size + 1 or (edge.size and int(comp_ptr.max()) > len(comps)):
+        raise ValueError("mixtures: comp_ptr must have one entry per mixture edge plus one, within comps")
+    return edge, comp_ptr, comps
+
+
+def mixture_eval(comps, s, loss=None):
+    """pgo_mixture_eval (host only): the max-mixture statement of csrc/mixture.h on one edge -- comps an (K, 5) array of
+    (x, y, theta, weight, info_scale) rows, s the K plain squared residuals, loss a Loss (None: Trivial).  Returns (chosen,
+    q_best, margin); chosen = -1 and NaN when no component is finite."""
+    comps = np.ascontiguousarray(comps, np.float64).reshape(-1, 5)
+    s = np.ascontiguousarray(s, np.float64).reshape(-1)
+    if s.size != len(comps):
+        raise ValueError("mixture_eval: one s per component")
+    k, qb, mg = np.zeros(1, np.int32), np.zeros(1), np.zeros(1)
+    _check(lib().pgo_mixture_eval(len(comps), _dp(comps), _dp(s), C.byref(loss) if loss is not None else None, _ip(k), _dp(qb), _dp(mg)))
+    return int(k[0]), float(qb[0]), float(mg[0])
+
+
+def mixture_plan(poses, ia, ib, edge, comp_ptr, comps, losses=None, mix_class=None, prev=None, active=None):
+    """pgo_mixture_plan (host only), the serial statement of Solver.mixture_select: poses (N, 3), the edges' endpoints, the
+    mixture table (edge, comp_ptr, comps as Solver.set_mixtures takes it), the loss classes (a Loss or a list; None: Trivial)
+    with each MIXTURE edge's class (None: 0), the previous applied selection (None: none) and a mask over the mixture edges
+    (None: all active).  Returns (chosen, q (n_mix, 2), stats dict)."""
+    poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
+    ia = np.ascontiguousarray(ia, np.int32)
+    ib = np.ascontiguousarray(ib, np.int32)
+    edge, comp_ptr, comps = _mix_table(edge, comp_ptr, comps)
+    n = edge.size
+    nl, larr = 1, None
+    if losses is not None:
+        nl, larr, _, _ = _loss_args(losses, None, 0)
+    cls = np.ascontiguousarray(mix_class, np.uint8).reshape(-1) if mix_class is not None else None
+    pv = np.ascontiguousarray(prev, np.int32).reshape(-1) if prev is not None else None
+    act = _mask(active, n, "active")
+    if any(a is not None and a.size != n for a in (cls, pv)):
+        raise ValueError("mixture_plan: mix_class and prev have one entry per mixture edge")
+    chosen, q, st = np.zeros(max(n, 1), np.int32), np.zeros((max(n, 1), 2)), MixStats()
+    _check(lib().pgo_mixture_plan(len(poses), _dp(poses), len(ia), _ip(ia), _ip(ib), n, _ip(edge), _ip(comp_ptr), _dp(comps), nl, larr,
+                                  _bp(cls) if cls is not None else None, _ip(pv) if pv is not None else None,
+                                  _bp(act) if act is not None else None, _ip(chosen), _dp(q), C.byref(st)))
+    return chosen[:n], q[:n], st.as_dict()
 
 
 def _support_records(res, n):
@@ -1185,6 +1292,7 @@ class Solver:
         _check(lib().pgo_create_from_graph(C.byref(self._h), graph._h, C.byref(self.options),
                                            comm._h if comm else None, device))
         self.n_poses, self.n_edges = graph.n_poses, graph.n_edges
+        self._n_mix = 0   # the mixture edges in force (set_mixtures, set_mixture_null): the size of the per-mixture outputs
         if losses is not None:
             self.set_losses(losses, edge_class)
 
@@ -1287,6 +1395,54 @@ class Solver:
         rounds = (GncRound * cap)()
         summ = GncSummary()
         _check(lib().pgo_gnc_solve(self._h, C.byref(o), C.byref(summ), rounds, cap))
+        return summ.as_dict(), [rounds[k].as_dict() for k in range(min(summ.rounds, cap))]
+
+    def set_mixtures(self, edge=None, comp_ptr=None, comps=None):
+        """pgo_set_mixtures (METHOD 0): the max-mixture edges of the handle -- edge: strictly ascending edge indices (caller's
+        order), comp_ptr: CSR offsets, comps: (n_comp, 5) rows (x, y, theta, weight, info_scale), 1 to 8 per edge.  No plane
+        is touched until mixture_select(apply=True).  set_mixtures() clears: the measurements are restored, the former
+        mixture edges' weights become 1."""
+        if edge is None:
+            _check(lib().pgo_set_mixtures(self._h, 0, None, None, None))
+            self._n_mix = 0
+            return
+        edge, comp_ptr, comps = _mix_table(edge, comp_ptr, comps)
+        _check(lib().pgo_set_mixtures(self._h, edge.size, _ip(edge), _ip(comp_ptr), _dp(comps)))
+        self._n_mix = int(edge.size)
+
+    def set_mixture_null(self, pi_null, scale_null, select=None):
+        """pgo_set_mixture_null: every selected edge (default: the active edges with kind != 0; else a mask over the edges)
+        gets an inlier component (pi = 1, w = 1) and a null hypothesis (pi_null, scale_null) at its own measurement"""
+        m = _mask(select, self.n_edges, "select")
+        _check(lib().pgo_set_mixture_null(self._h, _bp(m) if m is not None else None, float(pi_null), float(scale_null)))
+        st = MixStats()   # (the library resolved the selection: one measuring select, once per table, tells how many edges it took)
+        _check(lib().pgo_mixture_select(self._h, 0, C.byref(st), None, None))
+        self._n_mix = int(st.n_mix)
+
+    def mixture_selection(self):
+        """pgo_get_mixture_selection: the last applied component per mixture edge, -1 where none"""
+        out = np.zeros(max(self._n_mix, 1), np.int32)
+        _check(lib().pgo_get_mixture_selection(self._h, _ip(out)))
+        return out[:self._n_mix]
+
+    def mixture_select(self, apply=False):
+        """pgo_mixture_select at the current poses: per mixture edge the component with the smallest q; apply=True writes its
+        mean into the measurement planes and its info_scale into the edge weight plane.  Returns (chosen, q (n_mix, 2) =
+        q_best and margin, stats dict)."""
+        n = self._n_mix
+        chosen, q, st = np.zeros(max(n, 1), np.int32), np.zeros((max(n, 1), 2)), MixStats()
+        _check(lib().pgo_mixture_select(self._h, int(bool(apply)), C.byref(st), _ip(chosen), _dp(q)))
+        return chosen[:n], q[:n], st.as_dict()
+
+    def mixture_solve(self, **opts):
+        """pgo_mixture_solve (METHOD 0): rounds of select + apply and a short LM solve from the current poses until the
+        selection stands, then a final solve; opts: inner_iters, final_iters, max_rounds.  Returns (summary dict, list of round
+        dicts); the selection stays on the handle (mixture_selection, get_edge_weights)."""
+        o = MixtureOptions(**opts)
+        cap = max(int(o.max_rounds), 1)
+        rounds = (MixtureRound * cap)()
+        summ = MixtureSummary()
+        _check(lib().pgo_mixture_solve(self._h, C.byref(o), C.byref(summ), rounds, cap))
         return summ.as_dict(), [rounds[k].as_dict() for k in range(min(summ.rounds, cap))]
 
     def loop_support(self, select=None, window=32, tol_xy=0.1, tol_th=0.05, min_support=1, apply=False):

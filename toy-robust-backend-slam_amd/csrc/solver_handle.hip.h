@@ -15,8 +15,9 @@
 //   solver_gnc.hip      pgo_set_edge_weights, pgo_gnc_update, pgo_gnc_solve: the edge weight plane and GNC-TLS (gnc.hip.h, gnc.h)
 //   solver_support.hip  pgo_loop_support: loop edges judged by odometry cycle consistency (loop_support.hip.h, loop_support.h)
 //   solver_chordal.hip  pgo_chordal_init: a linear start, chordal rotations then positions (chordal.hip.h, chordal.h)
+//   solver_mixture.hip  pgo_set_mixtures, pgo_mixture_select, pgo_mixture_solve: max-mixture edges (mixture.hip.h, mixture.h)
 // Every kernel header declares its kernels `static`: a translation unit carries the kernels it launches.
-// The add-on calls (the last six units) share the helpers below: requires() for their refusals, reserve() and the Layouts of
+// The add-on calls (the last seven units) share the helpers below: requires() for their refusals, reserve() and the Layouts of
 // scratch.h for their staging and work buffers.
 //
 // Replaces, for DCS-ceres/main.cpp METHOD 0/1 (paths relative to /root/reference/DCS-ceres):
@@ -429,6 +430,23 @@ struct pgo_handle {
   int get_edge_weights(double* w_out);
   int gnc_update(double cbar, double mu, const uint8_t* select_or_null, bool reset_selected, pgo_gnc_stats* out);
   int gnc_solve(const pgo_gnc_options* o, pgo_gnc_summary* summary, pgo_gnc_round* rounds, int32_t rounds_cap);
+  // max-mixture edges (pgo_set_mixtures, pgo_mixture_select, pgo_mixture_solve; solver_mixture.hip, mixture.hip.h, mixture.h).
+  // The table of the mixtures in force, in the caller's mixture order: mix_edge_h = the caller's edge, mix_loc_h = its local
+  // edge, mix_ptr_h = its components (CSR).  mix_tab = the device copy -- local edge [n] | ptr [n + 1] | the applied selection
+  // [n] (-1: none yet) | the component records --, written when the table is set; mix_work = a call's partials, statistics and
+  // per-edge outputs.  Both are grown on demand and kept (reserve).  mix_applied: a select has written the planes since the
+  // table was set.  The poses a round of pgo_mixture_solve started from share gnc_x.
+  int32_t mix_n = 0;
+  bool mix_applied = false;
+  std::vector<int32_t> mix_edge_h, mix_loc_h, mix_ptr_h;
+  pgo::Scratch mix_tab, mix_work;
+  std::vector<uint8_t> mix_host;   // host image of a call's outputs
+  int mixtures_clear();
+  int set_mixtures(const char* who, int32_t n_mix, const int32_t* edge, const int32_t* comp_ptr, const pgo_mix_component* comps);
+  int set_mixture_null(const uint8_t* select_or_null, double pi_null, double scale_null);
+  int mixture_select(const char* who, int32_t apply, pgo_mix_stats* stats, int32_t* chosen, double* q);
+  int mixture_selection(int32_t* chosen_out);
+  int mixture_solve(const pgo_mixture_options* o, pgo_mixture_summary* summary, pgo_mixture_round* rounds, int32_t rounds_cap);
   dev::SwitchArrays switch_arrays() const {
     dev::SwitchArrays W;
     W.flags = e_flags;

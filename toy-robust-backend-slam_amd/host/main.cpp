@@ -2,13 +2,14 @@
 //     ./main DATASET NUM_OUTLIER_LOOPS METHOD [--seed S] [--data DIR] [--save DIR] [--device D] [--precision P]
 //            [--loss NAME[:A]] [--loop-loss NAME[:A]] [--score FILE [--align]] [--init-stride S [--init-info]] [--gnc CBAR [--gnc-inner K]]
 //            [--loop-support MIN[:WINDOW[:TOL_XY[:TOL_TH]]]]
-//            [--chordal-init [ROUNDS[:REJECT_XY[:REJECT_TH]]]]
+//            [--chordal-init [ROUNDS[:REJECT_XY[:REJECT_TH]]]] [--mixture-null PI:SCALE[:INNER]]
 // METHOD 0 = baseline, 1 = DCS, 2 = switchable constraints run on the MI355X backend; 3/4 are outside it (exit code 3).
 // Reads DIR/DATASET.g2o (default ../data, as the reference), writes init_/opt_ nodes+edges text files that
 // drawer/plot_results.py consumes (default ../save; unlike the reference the directory is created).
 #include <sys/stat.h>
 
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -59,6 +60,11 @@ int main(int argc, char* argv[]) {
               << "       by odometry cycle consistency and drop -- weight 0 -- those with fewer than MIN consistent neighbours within WINDOW\n"
               << "       poses, default 32; tolerances per sqrt(step), default 0.1 m and 0.05 rad: fit them to the dataset's odometry;\n"
               << "       --init-stride and --gnc then run without the dropped blocks; writes weights.txt)\n"
+              << "       [--mixture-null PI:SCALE[:INNER]]  (METHOD 0 only: max-mixtures -- every closure and bogus block gets a null hypothesis\n"
+              << "       beside its measurement, relative weight PI and information scale SCALE in (0, 1]; rounds of selection and INNER LM\n"
+              << "       iterations, default 2, until the selection stands.  The loop blocks run under the Trivial loss unless --loop-loss is\n"
+              << "       given: the null component wins where 1/2 rho(s) exceeds its constant -log PI - 1.5 log SCALE, and under the default\n"
+              << "       huber:0.01 rho grows like 0.02 |e|, so that it would win only kilometres out.  Writes weights.txt)\n"
               << "METHOD: 0=baseline, 1=DCS, 2=Switchable (3=Layer, 4=Simple Layer MCTS: not in this backend)\n"
               << "Example: " << argv[0] << " INTEL 50 1\n";
     return -1;
@@ -71,6 +77,8 @@ int main(int argc, char* argv[]) {
   pgo::LoopSupportOptions support;
   bool chordal_on = false;
   pgo::ChordalOptions chordal;
+  bool mixture_on = false;
+  pgo::MixtureOptions mixture;
   for (int i = 4; i < argc; i += 2) {
     if (!strcmp(argv[i], "--chordal-init")) {   // [ROUNDS[:REJECT_XY[:REJECT_TH]]]: the value is optional
       chordal_on = true;
@@ -113,6 +121,11 @@ int main(int argc, char* argv[]) {
     else if (!strcmp(argv[i], "--init-stride")) init_stride = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "--gnc")) { gnc_on = true; gnc_cbar = atof(argv[i + 1]); }
     else if (!strcmp(argv[i], "--gnc-inner")) gnc_inner = atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "--mixture-null")) {   // PI:SCALE[:INNER]
+      mixture_on = true;
+      const int got = sscanf(argv[i + 1], "%lf:%lf:%d", &mixture.pi_null, &mixture.scale_null, &mixture.inner_iterations);
+      if (got < 2) { std::cerr << "--mixture-null PI:SCALE[:INNER]\n"; return -1; }
+    }
     else if (!strcmp(argv[i], "--loop-support")) {   // MIN[:WINDOW[:TOL_XY[:TOL_TH]]]
       support_on = true;
       std::vector<std::string> f;
@@ -134,6 +147,7 @@ int main(int argc, char* argv[]) {
   try {
     loss_function = make_loss(loss_spec);
     if (!loop_spec.empty()) loop_loss = make_loss(loop_spec);
+    else if (mixture_on) loop_loss = make_loss("trivial");   // (see --help: under huber:0.01 the null component would never win)
   } catch (const std::exception& e) {
     std::cerr << "error: " << e.what() << std::endl;
     return -1;
@@ -150,6 +164,10 @@ int main(int argc, char* argv[]) {
   }
   if (gnc_on && method != 0) {
     std::cerr << "--gnc runs on METHOD 0 only (the weights take the place of DCS / the switches)\n";
+    return -1;
+  }
+  if (mixture_on && (method != 0 || gnc_on)) {
+    std::cerr << "--mixture-null runs on METHOD 0 only (the selection takes the place of DCS / the switches), and not with --gnc\n";
     return -1;
   }
   if (support_on && method == 2) {
@@ -252,6 +270,27 @@ int main(int argc, char* argv[]) {
       std::ofstream wf(save + "/weights.txt");
       wf.precision(17);
       for (double w : gs.weights) wf << w << "\n";
+      if (!wf) throw std::runtime_error("cannot write " + save + "/weights.txt");
+    } else if (mixture_on) {   // a null hypothesis beside the closure and bogus blocks (added after the odometry blocks, above)
+      mixture.select.assign(n_all, 1);
+      std::fill(mixture.select.begin(), mixture.select.begin() + (long)n_odo, (uint8_t)0);
+      pgo::MixtureSummary ms;
+      options.minimizer_progress_to_stdout = false;
+      pgo::SolveMixture(options, mixture, &problem, &ms);
+      std::cout.precision(12);
+      for (size_t k = 0; k < ms.rounds.size(); ++k)
+        std::cout << "mixture round " << k + 1 << ": objective " << ms.rounds[k].objective << " changed " << ms.rounds[k].n_changed << " inlier "
+                  << ms.rounds[k].count[0] << " null " << ms.rounds[k].count[1] << " lm_iterations " << ms.rounds[k].lm_iterations
+                  << " lm_termination " << ms.rounds[k].lm_termination << "\n";
+      size_t n_null = 0;
+      for (int32_t k : ms.selection) n_null += k == 1;
+      std::cout << "mixture: " << ms.m.rounds << " rounds" << (ms.m.hit_max_rounds ? " (max_rounds reached)" : "") << ", " << ms.m.n_mix
+                << " mixture blocks, " << n_null << " on the null hypothesis, " << ms.m.n_would_change << " would change" << std::endl;
+      std::cout.precision(6);
+      summary = ms.final_solve;
+      std::ofstream wf(save + "/weights.txt");
+      wf.precision(17);
+      for (double w : ms.weights) wf << w << "\n";
       if (!wf) throw std::runtime_error("cannot write " + save + "/weights.txt");
     } else {
       pgo::Solve(options, &problem, &summary);

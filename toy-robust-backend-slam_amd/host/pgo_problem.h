@@ -198,6 +198,25 @@ struct GncSummary {
   Solver::Summary final_solve;       // the last solve's summary and iteration records
 };
 
+// Max-mixture residual blocks (include/pgo.h, "max-mixture edges"; pgo_mixture_solve) around the problem's solves.  The problem
+// must be a METHOD 0 one (no DCS, no switchable blocks).  Either a table -- block[] strictly ascending in the order the blocks
+// were added, comp_ptr[] its CSR offsets into comps[] -- or, with block empty, the null hypothesis (pi_null, scale_null) beside
+// every block named by select (empty: the blocks the problem classifies as other than kind 0, as GncOptions::select).
+struct MixtureOptions {
+  int inner_iterations = 2, final_iterations = 50, max_rounds = 50;
+  std::vector<int32_t> block, comp_ptr;
+  std::vector<pgo_mix_component> comps;
+  double pi_null = 0.0, scale_null = 0.0;
+  std::vector<uint8_t> select;
+};
+struct MixtureSummary {
+  pgo_mixture_summary m{};
+  std::vector<pgo_mixture_round> rounds;
+  std::vector<int32_t> selection;    // per mixture block, in the table's order: the component in force after the call
+  std::vector<double> weights;       // per residual block, after the call
+  Solver::Summary final_solve;       // the last solve's summary and iteration records
+};
+
 // Loop edges judged by odometry cycle consistency (include/pgo.h, "loop support"; pgo_loop_support): no solve, no estimate.
 // The default tolerances fit pgo_synth_manhattan's odometry noise; a real dataset needs its own.
 struct LoopSupportOptions {
@@ -348,6 +367,32 @@ struct SolverAccess {
     sum->weights.assign(E, 1.0);
     if (st == PGO_OK && E > 0) st = pgo_get_edge_weights(h, sum->weights.data());
     sum->final_solve.s = sum->g.final_solve;
+    Finish(pr, h, st, &sum->final_solve);
+  }
+  static void SolveMixture(const Solver::Options& opt, const MixtureOptions& mix, Problem* pr, MixtureSummary* sum) {
+    const size_t E = pr->ia_.size();
+    if (!mix.select.empty() && mix.select.size() != E) throw std::invalid_argument("MixtureOptions::select: one byte per residual block");
+    if (!mix.block.empty() && mix.comp_ptr.size() != mix.block.size() + 1)
+      throw std::invalid_argument("MixtureOptions::comp_ptr: one entry per mixture block and one more");
+    if (!mix.block.empty() && (size_t)std::max(mix.comp_ptr.back(), 0) > mix.comps.size())
+      throw std::invalid_argument("MixtureOptions::comps: fewer components than comp_ptr names");
+    pgo_t* h = Prepare(opt, pr);
+    int st = mix.block.empty() ? pgo_set_mixture_null(h, mix.select.empty() ? nullptr : mix.select.data(), mix.pi_null, mix.scale_null)
+                               : pgo_set_mixtures(h, (int32_t)mix.block.size(), mix.block.data(), mix.comp_ptr.data(), mix.comps.data());
+    pgo_mixture_options o;
+    pgo_mixture_options_default(&o);
+    o.inner_iters = mix.inner_iterations;
+    o.final_iters = mix.final_iterations;
+    o.max_rounds = mix.max_rounds;
+    sum->rounds.assign((size_t)(mix.max_rounds > 0 ? mix.max_rounds : 0), pgo_mixture_round());
+    if (st == PGO_OK) st = pgo_mixture_solve(h, &o, &sum->m, sum->rounds.data(), (int32_t)sum->rounds.size());
+    sum->rounds.resize((size_t)(st == PGO_OK ? sum->m.rounds : 0));
+    sum->selection.assign(E, -1);
+    if (st == PGO_OK) st = pgo_get_mixture_selection(h, sum->selection.data());
+    sum->selection.resize((size_t)(st == PGO_OK ? sum->m.n_mix : 0));
+    sum->weights.assign(E, 1.0);
+    if (st == PGO_OK && E > 0) st = pgo_get_edge_weights(h, sum->weights.data());
+    sum->final_solve.s = sum->m.final_solve;
     Finish(pr, h, st, &sum->final_solve);
   }
   static void LoopSupport(const Solver::Options& opt, const LoopSupportOptions& ls, Problem* pr, LoopSupportSummary* sum) {
@@ -577,6 +622,11 @@ inline void InitializeHierarchical(Problem* problem, int stride, const Solver::O
 // Solve with graduated non-convexity: the parameter blocks end at the final solve's poses, summary->weights at the weights
 inline void SolveGnc(const Solver::Options& opt, const GncOptions& gnc, Problem* problem, GncSummary* summary) {
   SolverAccess::SolveGnc(opt, gnc, problem, summary);
+}
+// Solve with max-mixture blocks: rounds of selection and short solves until the selection stands, then a final solve; the
+// parameter blocks end at its poses, summary->selection at the components in force, summary->weights at their information scales
+inline void SolveMixture(const Solver::Options& opt, const MixtureOptions& mixture, Problem* problem, MixtureSummary* summary) {
+  SolverAccess::SolveMixture(opt, mixture, problem, summary);
 }
 // Judge the problem's loop blocks by odometry cycle consistency; with options.apply the verdict becomes the problem's residual
 // block weights, which every Solve, SolveGnc and InitializeHierarchical that follows honours
