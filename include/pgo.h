@@ -1216,6 +1216,58 @@ int  pgo_chordal_plan(int32_t n_poses, int32_t n_edges, const int32_t* ia, const
 int  pgo_chordal_init(pgo_t* h, const pgo_chordal_options* opt, double* poses_out_or_null /* N x 3 */,
                       double* res_out_or_null /* E x 2 */, pgo_chordal_summary* summary_or_null);                    /* [gpu] */
 
+/* ---------------------------------------------------------------- pose priors (absolute, unary SE(2) factors)
+ * "Pose i is at z, with information Lambda": a GPS or survey fix, a known start or end pose, a position-only anchor -- g2o's
+ * EDGE_PRIOR_SE2, a one-block AddResidualBlock in Ceres.  Every other residual block here joins two poses; the only gauge a
+ * handle had was hard (fixed_pose, pose_constant).  csrc/prior.h is the one statement:
+ *   d    = (x_i - z_x, y_i - z_y, remainder(theta_i - z_theta, 2 pi))   the IEEE remainder: d_theta in [-pi, pi]; the Jacobian
+ *                                                                       with respect to the pose is the identity
+ *   chi2 = max(0, d' Lambda d),   cost term 1/2 rho(chi2)
+ * with rho ONE pgo_loss for all priors of the handle (NULL = Trivial), evaluated by the function of csrc/loss.h, and the
+ * corrector the sqrt(rho') row scaling every loss here uses.  With S_i the Jacobi scales of pose i the scaled system gains
+ * hd_i += rho' S_i Lambda S_i and gs_i += rho' S_i Lambda d.  A constant pose has zero scale: it receives exactly nothing, but
+ * its prior still counts in the cost.  Lambda is symmetric, given as I11 I12 I13 I22 I23 I33 (the order of the edges'
+ * information), finite and positive SEMI-definite: diag(a, a, 0), a position-only fix, is legal and the common case.  The
+ * rounding allowance: the smallest eigenvalue may be as low as -1e-12 x the largest absolute eigenvalue (what forming Q Omega Q'
+ * in floating point leaves of an exact zero); a prior whose smallest eigenvalue is above +1e-12 x the largest is positive
+ * definite and counts as a gauge for the calls that refuse an unanchored problem (pgo_pose_covariance and the gates).  At most
+ * one prior per pose.
+ * - pgo_set_priors: n priors on the poses pose[k] (the caller's numbering); n = 0 clears them (the arrays are not read), and a
+ *   pgo_solve after clearing gives bitwise what a fresh handle gives.  Each call replaces the whole set.  A handle with priors
+ *   keeps whatever K1 instantiation it had: priors never touch K1, and a handle without priors launches neither of their kernels.
+ * - pgo_eval's cost, the LM loop (pgo_solve, pgo_lm_step), pgo_iter_record.cost and the gradient norm include the priors, and so
+ *   do pgo_gnc_solve and pgo_mixture_solve, which go through the LM loop.  pgo_eval's r and J outputs stay the EDGES' rows;
+ *   pgo_debug_normal_eq returns the system with the priors.  info_weighting = 1 is supported: the priors are independent of K1's
+ *   whitening.
+ * - pgo_pose_covariance, pgo_edge_gate and pgo_edge_gate_joint (both `solver` settings) see the problem WITH priors.  A positive
+ *   definite prior on a pose that is free at the time of the call is a gauge for them (pgo_set_active may free or fix the pose
+ *   later, in either order).  solver = 1 runs on handles on the direct solve, and those have a constant pose (below): with
+ *   solver = 1 the priors are only ever met NEXT to a hard anchor, never as the only gauge.
+ * - pgo_edge_weights, pgo_edge_chi2, pgo_loop_support, pgo_chordal_init, pgo_coarsen* and pgo_prolong do not know priors: they
+ *   report on, or start from, the edges alone.
+ * - pgo_set_losses, pgo_set_active and pgo_set_edge_weights leave the priors alone, in either call order.  A solve begun with
+ *   pgo_lm_begin becomes stale: pgo_lm_step returns PGO_ERR_INVALID_ARG until pgo_lm_begin runs again, as after pgo_set_losses.
+ * - The direct solve (linear_solver 2) adds the priors' blocks to the diagonal of its chain matrix T, which stays a sum of
+ *   positive semi-definite terms.  The solver of a handle is planned at pgo_create*, before any prior exists, and that plan
+ *   keeps its rule: the direct solve needs a constant pose (fixed_pose >= 0), so a handle whose gauge comes from priors alone
+ *   (fixed_pose = -1) solves by PCG, and linear_solver = 2 stays PGO_ERR_UNSUPPORTED for it.  Priors only add to T's
+ *   diagonal; a direct solve that fails all the same is redone by PCG as ever (pgo_handle_info.direct_fallbacks).
+ * - pgo_window_solve returns PGO_ERR_UNSUPPORTED while priors are set (its kernel evaluates its own system).  There is no batch
+ *   entry point.
+ * - pgo_get_prior_residuals: d (n x 3) and chi2 (n) of the plain residual at the handle's poses (or at poses_or_null, N x 3 in
+ *   the caller's order), in the order the priors were given; runs on the GPU.  Either output may be NULL.
+ * - pgo_prior_eval: the host evaluation of the same header -- d, chi2 and rho[0..2] = rho, rho', rho'' at chi2.
+ * Errors (nothing changes on error): PGO_ERR_INVALID_ARG for a null handle or a null array with n > 0, n < 0, a pose out of range
+ * or a duplicate pose (pgo_last_error names the first), a mean or information that is not finite, an information with a negative
+ * eigenvalue beyond the allowance, an invalid loss; PGO_ERR_UNSUPPORTED for METHOD 2, a communicator or
+ * PGO_FORCE_COLLECTIVES=1, a batched handle.                                                                                   */
+int     pgo_set_priors(pgo_t* h, int32_t n, const int32_t* pose, const double* mean_xyt /* n x 3 */, const double* info6 /* n x 6 */,
+                       const pgo_loss* loss_or_null);                                                                  /* [gpu] */
+int32_t pgo_num_priors(const pgo_t* h);                                                                                /* [host] */
+int     pgo_get_prior_residuals(pgo_t* h, const double* poses_or_null, double* d_out /* n x 3 */, double* chi2_out /* n */);  /* [gpu] */
+int     pgo_prior_eval(const double pose[3], const double mean[3], const double info6[6], const pgo_loss* loss_or_null, double d[3],
+                       double* chi2, double rho[3]);                                                                   /* [host] */
+
 /* ------------------------------------------------ kernel-level entry points
  * Used by the parity tests and by bench.py's roofline leg: each launches exactly
  * one kind of kernel `reps` times on the handle's stream, brackets the launches
@@ -1306,6 +1358,8 @@ int pgo_debug_normal_eq(pgo_t* h, double* g_or_null, double* hdiag_or_null);    
  *                        of one per unit of work (read per call; the results are bitwise the same)
  *   "mix_grid"           n > 0 = pgo_mixture_select (and pgo_mixture_solve through it) launches n workgroups over its chunks of
  *                        256 mixture edges (read per call; the results are bitwise the same)
+ *   "prior_add_grid"     n > 0 = k_prior_add, which adds the pose priors to the assembled system, launches n workgroups over its
+ *                        chunks of 256 priors (read per launch; the results are bitwise the same)
  * Unknown name: PGO_ERR_INVALID_ARG.                                                                     */
 int pgo_debug_set_knob(const char* name, long long value);                        /* [host] */
 /* sharding plan of a graph over `world` ranks: for rank r, rows [lo, hi) and the

@@ -30,7 +30,8 @@ __all__ = ["PgoError", "Options", "Summary", "IterRecord", "ReadG2O", "Graph", "
            "gnc_weight_eval", "GncStats", "GncOptions", "GncRound", "GncSummary",
            "loop_support_plan", "LoopSupportOptions", "LoopSupportRecord", "LoopSupportStats", "LOOP_SUPPORT_MAX_WINDOW",
            "chordal_plan", "ChordalOptions", "ChordalSolve", "ChordalSummary", "CHORDAL_MAX_ROUNDS",
-           "mixture_eval", "mixture_plan", "MixStats", "MixtureOptions", "MixtureRound", "MixtureSummary", "MIX_MAX_COMPONENTS"]
+           "mixture_eval", "mixture_plan", "MixStats", "MixtureOptions", "MixtureRound", "MixtureSummary", "MIX_MAX_COMPONENTS",
+           "prior_eval"]
 
 EDGE_ODOMETRY, EDGE_CLOSURE, EDGE_BOGUS = 0, 1, 2
 TERMINATION = {1: "CONVERGENCE_FTOL", 2: "CONVERGENCE_GTOL", 3: "CONVERGENCE_PTOL", 4: "NO_CONVERGENCE",
@@ -67,6 +68,7 @@ EXPORTS = [
     "pgo_chordal_options_default", "pgo_chordal_plan", "pgo_chordal_init",
     "pgo_mixture_options_default", "pgo_mixture_eval", "pgo_mixture_plan", "pgo_set_mixtures", "pgo_set_mixture_null",
     "pgo_mixture_select", "pgo_get_mixture_selection", "pgo_mixture_solve",
+    "pgo_set_priors", "pgo_num_priors", "pgo_get_prior_residuals", "pgo_prior_eval",
 ]
 MIX_MAX_COMPONENTS = 8   # PGO_MIX_MAX_COMPONENTS
 CHORDAL_MAX_ROUNDS = 8   # PGO_CHORDAL_MAX_ROUNDS
@@ -605,6 +607,11 @@ def lib():
     L.pgo_mixture_select.argtypes = [vp, C.c_int32, C.POINTER(MixStats), ip, dp]
     L.pgo_get_mixture_selection.argtypes = [vp, ip]
     L.pgo_mixture_solve.argtypes = [vp, C.POINTER(MixtureOptions), C.POINTER(MixtureSummary), C.POINTER(MixtureRound), C.c_int32]
+    L.pgo_set_priors.argtypes = [vp, C.c_int32, ip, dp, dp, C.POINTER(Loss)]
+    L.pgo_num_priors.argtypes = [vp]
+    L.pgo_num_priors.restype = C.c_int32
+    L.pgo_get_prior_residuals.argtypes = [vp, dp, dp, dp]
+    L.pgo_prior_eval.argtypes = [dp, dp, dp, C.POINTER(Loss), dp, dp, dp]
     _LIB = L
     return L
 
@@ -814,6 +821,28 @@ def mixture_eval(comps, s, loss=None):
     k, qb, mg = np.zeros(1, np.int32), np.zeros(1), np.zeros(1)
     _check(lib().pgo_mixture_eval(len(comps), _dp(comps), _dp(s), C.byref(loss) if loss is not None else None, _ip(k), _dp(qb), _dp(mg)))
     return int(k[0]), float(qb[0]), float(mg[0])
+
+
+def prior_eval(pose, mean, info, loss=None):
+    """pgo_prior_eval (host only): the pose prior of csrc/prior.h at one pose -- pose and mean (x, y, theta), info the six values
+    I11 I12 I13 I22 I23 I33 or a symmetric 3x3 matrix, loss a Loss (None: Trivial).  Returns (d, chi2, rho): the plain residual
+    with the heading wrapped to [-pi, pi], d' info d, and rho, rho', rho'' of the loss at chi2."""
+    pose = np.ascontiguousarray(pose, np.float64).reshape(3)
+    mean = np.ascontiguousarray(mean, np.float64).reshape(3)
+    info = _info6(info, 1).reshape(6)
+    d, chi2, rho = np.zeros(3), np.zeros(1), np.zeros(3)
+    _check(lib().pgo_prior_eval(_dp(pose), _dp(mean), _dp(info), C.byref(loss) if loss is not None else None, _dp(d), _dp(chi2), _dp(rho)))
+    return d, float(chi2[0]), rho
+
+
+def _info6(info, n):
+    """(n, 6) information rows I11 I12 I13 I22 I23 I33 from (n, 6), or from (n, 3, 3) symmetric matrices (the upper triangle is read)"""
+    a = np.asarray(info, np.float64)
+    if a.size == 9 * n and a.shape[-2:] == (3, 3):
+        a = a.reshape(n, 3, 3)[:, [0, 0, 0, 1, 1, 2], [0, 1, 2, 1, 2, 2]]
+    if a.size != 6 * n:
+        raise ValueError(f"info: {n} rows of six values (I11 I12 I13 I22 I23 I33) or {n} 3x3 matrices")
+    return np.ascontiguousarray(a.reshape(n, 6))
 
 
 def mixture_plan(poses, ia, ib, edge, comp_ptr, comps, losses=None, mix_class=None, prev=None, active=None):
@@ -1368,6 +1397,40 @@ class Solver:
         if a.size != self.n_edges:
             raise ValueError(f"set_edge_weights: {a.size} entries for {self.n_edges} edges")
         _check(lib().pgo_set_edge_weights(self._h, _dp(a)))
+
+    def set_priors(self, poses, means, info, loss=None):
+        """pgo_set_priors: absolute pose priors -- poses = the pose of each prior (at most one per pose), means (n, 3) = its
+        (x, y, theta), info = (n, 6) rows I11 I12 I13 I22 I23 I33 or (n, 3, 3) symmetric positive SEMI-definite matrices
+        (diag(a, a, 0) is a position-only fix), loss = ONE Loss for all priors (None: Trivial).  Each call replaces the whole
+        set; no priors (or clear_priors) restores the handle.  A solve begun with lm_begin is stale afterwards."""
+        idx = np.ascontiguousarray(poses, np.int32).reshape(-1)
+        n = idx.size
+        if n == 0:
+            return self.clear_priors()
+        z = np.ascontiguousarray(means, np.float64)
+        if z.size != 3 * n:
+            raise ValueError(f"set_priors: means must be ({n}, 3)")
+        w = _info6(info, n)
+        _check(lib().pgo_set_priors(self._h, n, _ip(idx), _dp(z), _dp(w), C.byref(loss) if loss is not None else None))
+
+    def clear_priors(self):
+        """pgo_set_priors(h, 0, ...): no priors -- a solve afterwards gives bitwise what a fresh handle gives"""
+        _check(lib().pgo_set_priors(self._h, 0, None, None, None, None))
+
+    @property
+    def n_priors(self):
+        return int(lib().pgo_num_priors(self._h))
+
+    def prior_residuals(self, poses=None):
+        """pgo_get_prior_residuals: (d (n, 3), chi2 (n,)) of the priors' plain residual at the current poses (or at `poses`),
+        in the order the priors were given; computed on the device"""
+        p = np.ascontiguousarray(poses, np.float64) if poses is not None else None
+        if p is not None and p.size != 3 * self.n_poses:
+            raise ValueError("prior_residuals: poses must be (n_poses, 3)")
+        n = self.n_priors
+        d, chi2 = np.zeros((n, 3)), np.zeros(n)
+        _check(lib().pgo_get_prior_residuals(self._h, _dp(p), _dp(d), _dp(chi2)))
+        return d, chi2
 
     def get_edge_weights(self):
         """pgo_get_edge_weights: the plane in the caller's edge order (all ones when none is set)"""

@@ -18,6 +18,7 @@ constexpr int SOLO_CH = 4;                // chain layout: 256-row wave tiles
 constexpr int CHOL_NB = 32;
 constexpr int DLR_MAX_SEP = 15;  // separator poses: the chain factorisation runs nsep + 1 pieces side by side (3 separators up to ~2000 poses)
 constexpr int DLR_MAX_SEG = 64;
+constexpr int PRIOR_MAX_GRID = 256;   // workgroups of k_prior_eval = cost partials appended to K1's (a grid-stride loop above 65536 priors)
 }  // namespace dev
 
 constexpr int DIRECT_MAX_POSES = 65536;   // largest graph the direct (chain + low-rank) solve takes

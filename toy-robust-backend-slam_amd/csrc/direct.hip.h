@@ -67,6 +67,9 @@ struct DlrArgs {
   const double* sw_c;
   int32_t rec_n;              // doubles per edge record (REC, or REC_INFO in the information-weighted mode)
   int32_t rec_info;           // 1: information-weighted records (the last column of d e / d P2 is stored: b3)
+  // pose priors (pgo_set_priors): their scaled blocks S (rho' Lambda) S as dense planes [6][n] (00 01 02 11 12 22), zero on the
+  // rows without a prior -- what k_prior_add added to hd, which this solve does not read; nullptr without priors
+  const double* prior;
 };
 
 // scaled Jacobian blocks of edge e (record layouts: kernels.hip.h REC / REC_INFO; the second block is implied up to its
@@ -137,6 +140,10 @@ __global__ void k_dlr_setup(DlrArgs A) {
 #pragma unroll
           for (int c = 0; c < 3; ++c) C[3 * r + c] = Xi[r] * Xo[c] + Xi[3 + r] * Xo[3 + c] + Xi[6 + r] * Xo[6 + c];
       }
+    }
+    if (A.prior != nullptr) {   // T = chain + priors + D'D: a sum of positive semi-definite terms still
+#pragma unroll
+      for (int k = 0; k < 6; ++k) M[k] += A.prior[(int64_t)k * A.n + i];
     }
     // separator s: the couplings (s, s-1) and (s+1, s) leave T (they come back through k_dlr_sep_*), so that the chain
     // falls into independently factorised pieces; the diagonal blocks keep every edge's contribution (anchored pieces)

@@ -11,7 +11,7 @@ struct Knob {
   const char* name;
   std::atomic<long long> value;
 };
-Knob g_knobs[] = {{"spmv_pipe", {-1}}, {"fused_p", {-1}}, {"direct_fail_at", {-1}}, {"direct_setup_fail", {-1}}, {"single_reduction", {-1}}, {"verify_residual", {-1}}, {"shm_timeout_s", {-1}}, {"pad_tiles", {-1}}, {"cov_poses_per_pass", {-1}}, {"cov_direct_cols", {-1}}, {"gate_joint_shape", {-1}}, {"score_grid", {-1}}, {"coarsen_grid", {-1}}, {"gnc_grid", {-1}}, {"support_grid", {-1}}, {"chordal_grid", {-1}}, {"mix_grid", {-1}}};
+Knob g_knobs[] = {{"spmv_pipe", {-1}}, {"fused_p", {-1}}, {"direct_fail_at", {-1}}, {"direct_setup_fail", {-1}}, {"single_reduction", {-1}}, {"verify_residual", {-1}}, {"shm_timeout_s", {-1}}, {"pad_tiles", {-1}}, {"cov_poses_per_pass", {-1}}, {"cov_direct_cols", {-1}}, {"gate_joint_shape", {-1}}, {"score_grid", {-1}}, {"coarsen_grid", {-1}}, {"gnc_grid", {-1}}, {"support_grid", {-1}}, {"chordal_grid", {-1}}, {"mix_grid", {-1}}, {"prior_add_grid", {-1}}};
 }  // namespace
 
 long long knob(const char* name) {

@@ -151,6 +151,9 @@ inline PlanShard plan_shard(const pgo_options& opt, const PlanEnv& env, const Pl
   O.g_spmv = plan_up8(std::min(std::max(1, F.n_tiles), 2048));
   O.g_asm = plan_up8(std::min(std::max(1, F.n_tiles), 1 << 20));
   O.part_cap = std::max(std::max(O.g_edge, 2048), plan_up8(std::max(1, F.n_tiles))) + 8 + 512;   // (k_spmv_1: one dot partial per tile)   // (+ the coarse level's dot partials behind the one-level r.z partials)
+  // The same 512 behind K1's g_edge cost partials take k_prior_eval's (eval_enqueue appends them in part[5], which holds nothing
+  // of the coarse level then): whoever shrinks that slack meets this line, and pgo_set_priors checks the sum at run time.
+  static_assert(dev::PRIOR_MAX_GRID <= 512, "part_cap: no room for the pose priors' cost partials behind K1's");
   {
     // the software-pipelined product kernel (k_spmv_p) needs plain tiles: no chunked heavy row, at most 85 rows
     // (one row-phase pass).  Measured on one box at 1M poses: k_spmv_t 185.7 us (8 workgroups per CU), k_spmv_p

@@ -36,6 +36,7 @@ int pgo_handle::direct_factor(const double* rhs, bool fine_prefix, DirectLaunch*
   A.sw_c = has_sw ? sw_c : nullptr;
   A.rec_n = rec_doubles;
   A.rec_info = info_mode ? 1 : 0;
+  A.prior = pri_n > 0 ? pri_dense : nullptr;
   hipLaunchKernelGGL(dev::k_dlr_setup<>, dim3((n + plan.dl.dl_m + 255) / 256), dim3(256), 0, stream, A);
   PGOC(check_launch("k_dlr_setup"));
   hipLaunchKernelGGL(dev::k_dlr_factor<>, dim3(plan.dl.dl_nsep + 1), dim3(64), 0, stream, (const double*)dl_trec, n, dl_fac, A);

@@ -16,8 +16,9 @@
 //   solver_support.hip  pgo_loop_support: loop edges judged by odometry cycle consistency (loop_support.hip.h, loop_support.h)
 //   solver_chordal.hip  pgo_chordal_init: a linear start, chordal rotations then positions (chordal.hip.h, chordal.h)
 //   solver_mixture.hip  pgo_set_mixtures, pgo_mixture_select, pgo_mixture_solve: max-mixture edges (mixture.hip.h, mixture.h)
+//   solver_prior.hip    pgo_set_priors, pgo_get_prior_residuals, pgo_prior_eval: absolute pose priors (prior.hip.h, prior.h)
 // Every kernel header declares its kernels `static`: a translation unit carries the kernels it launches.
-// The add-on calls (the last seven units) share the helpers below: requires() for their refusals, reserve() and the Layouts of
+// The add-on calls (the last eight units) share the helpers below: requires() for their refusals, reserve() and the Layouts of
 // scratch.h for their staging and work buffers.
 //
 // Replaces, for DCS-ceres/main.cpp METHOD 0/1 (paths relative to /root/reference/DCS-ceres):
@@ -404,7 +405,12 @@ struct pgo_handle {
   int32_t n_active_edges = 0, n_constant_poses = 0;   // resolved (pgo_handle_info)
   bool act_chain_cut = false;         // an edge of the direct solve's chain is inactive: PCG until it is active again
   int co_dead_cap = 0;                // entries co_dead can hold
-  bool has_anchor() const { return fixed_internal >= 0 || act_anchor; }
+  bool has_anchor() const {   // (... or a positive definite pose prior on a pose that is free NOW: pgo_set_active may change that)
+    if (fixed_internal >= 0 || act_anchor) return true;
+    for (int32_t r : pri_pd_rows)
+      if (act_const_h.empty() || !act_const_h[r]) return true;
+    return false;
+  }
   void coarse_dead_list(std::vector<int32_t>* dead) const;
   int set_active(const uint8_t* edge_active, const uint8_t* pose_constant);
   // edge weights (pgo_set_edge_weights) and graduated non-convexity (pgo_gnc_update, pgo_gnc_solve; solver_gnc.hip, gnc.hip.h,
@@ -447,6 +453,24 @@ struct pgo_handle {
   int mixture_select(const char* who, int32_t apply, pgo_mix_stats* stats, int32_t* chosen, double* q);
   int mixture_selection(int32_t* chosen_out);
   int mixture_solve(const pgo_mixture_options* o, pgo_mixture_summary* summary, pgo_mixture_round* rounds, int32_t rounds_cap);
+  // absolute pose priors (pgo_set_priors, pgo_get_prior_residuals; solver_prior.hip, prior.hip.h, prior.h).  pri_tab = the
+  // priors in force sorted by internal row -- row [n] | caller's position [n] | mean planes [3][n] | information planes [6][n] |
+  // the record of k_prior_eval<true> [9][n] --, pri_out = the outputs of pgo_get_prior_residuals; both are grown on demand and
+  // kept (reserve).  pri_dense = the scaled blocks as dense planes [6][n_loc] for the direct solve's k_dlr_setup: allocated at
+  // the first pgo_set_priors of a handle whose plan allows the direct solve, zeroed whenever the priors change.
+  int32_t pri_n = 0;
+  std::vector<int32_t> pri_pd_rows;   // internal rows of the positive definite priors: each is a gauge while its pose is free (has_anchor)
+  pgo::LossClass pri_loss = {};
+  pgo::Scratch pri_tab, pri_out;
+  double* pri_dense = nullptr;
+  pgo::Span<int32_t> pri_row_s, pri_order_s;
+  pgo::Span<double> pri_mean_s, pri_info_s, pri_rec_s;
+  int set_priors(int32_t n, const int32_t* pose, const double* mean_xyt, const double* info6, const pgo_loss* loss_or_null);
+  int get_prior_residuals(const double* poses_or_null, double* d_out, double* chi2_out);
+  // the two launch helpers (solver_launch.hip); called with pri_n > 0 only -- a handle without priors launches neither kernel
+  int prior_grid() const { return (int)std::min<int64_t>(((int64_t)pri_n + dev::WG - 1) / dev::WG, dev::PRIOR_MAX_GRID); }
+  int prior_eval_enqueue(const double* x, int apply_loss, bool with_jac, double* cost_part, double* d_out = nullptr, double* chi2_out = nullptr);
+  int prior_add_enqueue();
   dev::SwitchArrays switch_arrays() const {
     dev::SwitchArrays W;
     W.flags = e_flags;

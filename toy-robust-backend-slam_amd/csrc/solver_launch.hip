@@ -3,6 +3,7 @@
 // ONCE here, so that the other units do not carry copies of those kernels -- and so that a test hook runs the lines the LM loop
 // runs.  The caller <-> internal numbering of a pose vector is stated here too.
 #include "solver_handle.hip.h"
+#include "prior.hip.h"
 
 int pgo_handle::reduce_to_scal(std::initializer_list<PartRef> parts, int first, bool allreduce_max) {
   return reduce_parts(parts, scal + first, scal + first, (int)parts.size(), allreduce_max);
@@ -84,13 +85,62 @@ int pgo_handle::eval_enqueue(const double* x, const double* sw_vals, int apply_l
   HIPC(hipMemsetAsync(bad, 0, sizeof(int), stream));
   launch_eval(x, sw_vals, apply_loss, with_jac);
   PGOC(check_launch("k_edge_eval"));
+  // pose priors (pgo_set_priors): their cost partials are appended to K1's, so that ONE cost scalar comes back with no further
+  // host synchronisation; a handle without priors launches nothing more and reduces the partials it always did
+  int n_cost = plan.own.g_edge;
+  if (pri_n > 0) {
+    PGOC(prior_eval_enqueue(x, apply_loss, with_jac, part[5] + n_cost));
+    n_cost += prior_grid();
+  }
   // the flag rides along as a "partial array" of length 1 after conversion to double
   hipLaunchKernelGGL(dev::k_flag_to_double<>, dim3(1), dim3(1), 0, stream, bad, part[4]);
-  return reduce_to_scal({{part[5], plan.own.g_edge, 0}, {part[4], 1, 0}}, slot);
+  return reduce_to_scal({{part[5], n_cost, 0}, {part[4], 1, 0}}, slot);
+}
+
+// k_prior_eval at x: the workgroups' cost partials into cost_part[0 .. prior_grid()), the `bad` flag, with_jac: the per-prior
+// records k_prior_add reads; d_out / chi2_out (device, the caller's prior order): pgo_get_prior_residuals
+int pgo_handle::prior_eval_enqueue(const double* x, int apply_loss, bool with_jac, double* cost_part, double* d_out, double* chi2_out) {
+  dev::PriorArgs A;
+  A.poses = x;
+  A.row = pri_row_s.in(pri_tab.p);
+  A.mean = pri_mean_s.in(pri_tab.p);
+  A.info = pri_info_s.in(pri_tab.p);
+  A.rec = pri_rec_s.in(pri_tab.p);
+  A.n = pri_n;
+  A.apply_loss = apply_loss;
+  A.loss = pri_loss;
+  A.order = pri_order_s.in(pri_tab.p);
+  A.d_out = d_out;
+  A.chi2_out = chi2_out;
+  if (with_jac) hipLaunchKernelGGL(dev::k_prior_eval<true>, dim3(prior_grid()), dim3(dev::WG), 0, stream, A, cost_part, bad);
+  else hipLaunchKernelGGL(dev::k_prior_eval<false>, dim3(prior_grid()), dim3(dev::WG), 0, stream, A, cost_part, bad);
+  return check_launch("k_prior_eval");
+}
+
+// k_prior_add: the priors' blocks and gradients, with the current Jacobi scales, onto what k_assemble left in hd / gs
+int pgo_handle::prior_add_enqueue() {
+  dev::PriorAddArgs A;
+  A.row = pri_row_s.in(pri_tab.p);
+  A.rec = pri_rec_s.in(pri_tab.p);
+  A.scale = scale;
+  A.hd = hd;
+  A.gs = gs;
+  A.dense = pri_dense;
+  A.n = pri_n;
+  A.n_loc = S.n_loc;
+  A.lo = S.lo;
+  hipLaunchKernelGGL(dev::k_prior_add<>, dim3(launch_grid("prior_add_grid", ((int64_t)pri_n + dev::WG - 1) / dev::WG)), dim3(dev::WG), 0, stream, A);
+  return check_launch("k_prior_add");
 }
 
 int pgo_handle::assemble_enqueue() {
-  if (S.n_tiles() == 0) return PGO_OK;
+  if (S.n_tiles() == 0) {
+    if (pri_n == 0) return PGO_OK;
+    // a graph without edges: k_assemble, which overwrites hd and gs, does not run -- k_prior_add adds to zeros
+    HIPC(hipMemsetAsync(hd, 0, (size_t)6 * S.n_loc * sizeof(double), stream));
+    HIPC(hipMemsetAsync(gs, 0, (size_t)3 * S.n_loc * sizeof(double), stream));
+    return prior_add_enqueue();
+  }
   if (has_sw) hipLaunchKernelGGL((dev::k_assemble<true, false>), dim3(plan.own.g_asm), dim3(dev::WG), 0, stream, asm_args());
   else if (info_mode) hipLaunchKernelGGL((dev::k_assemble<false, true>), dim3(plan.own.g_asm), dim3(dev::WG), 0, stream, asm_args());
   else hipLaunchKernelGGL((dev::k_assemble<false, false>), dim3(plan.own.g_asm), dim3(dev::WG), 0, stream, asm_args());
@@ -100,6 +150,7 @@ int pgo_handle::assemble_enqueue() {
                        (const int32_t*)inc_ptr, (const int32_t*)inc_col, (const double*)hoff, S.lo, chain_c);
     PGOC(check_launch("k_chain_dupfix"));
   }
+  if (pri_n > 0) PGOC(prior_add_enqueue());   // (pose priors, pgo_set_priors: no launch without them)
   return PGO_OK;
 }
 

@@ -12,6 +12,8 @@ int pgo_handle::window_solve(const char* who, int32_t nw, const int32_t* pose_pt
   PGOC(requires(who, METHOD_01 | NO_INFO | ONE_RANK));   // (a batch is allowed: pgo_batch_window_solve)
   if (w_set)   // (k_window_solve evaluates the edges itself and does not read the plane)
     return fail(PGO_ERR_UNSUPPORTED, W + "not while edge weights are set (pgo_set_edge_weights(h, NULL) first)");
+  if (pri_n > 0)   // (k_window_solve assembles its own system, which does not know the pose priors)
+    return fail(PGO_ERR_UNSUPPORTED, W + "not while pose priors are set (pgo_set_priors(h, 0, ...) first)");
   if (nw < 0) return fail(PGO_ERR_INVALID_ARG, W + "n_windows < 0");
   if (nw == 0) return PGO_OK;
   if (!pose_ptr || !pose_idx || !edge_ptr || !edge_idx || !anchor || !results) return fail(PGO_ERR_INVALID_ARG, W + "null pointer");

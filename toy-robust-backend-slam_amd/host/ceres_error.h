@@ -11,9 +11,10 @@
 
 namespace pgo {
 struct CostFunction {   // stands in for ceres::CostFunction* on this path
-  enum Kind { PLAIN, DCS, SWITCHABLE, SWITCH_PRIOR };
-  double dx, dy, dtheta;   // SWITCH_PRIOR: dx holds lambda
+  enum Kind { PLAIN, DCS, SWITCHABLE, SWITCH_PRIOR, POSE_PRIOR };
+  double dx, dy, dtheta;   // SWITCH_PRIOR: dx holds lambda; POSE_PRIOR: the mean (x, y, theta)
   Kind kind;
+  double info[6];          // POSE_PRIOR: I11 I12 I13 I22 I23 I33; zero otherwise
 };
 }  // namespace pgo
 
@@ -88,6 +89,23 @@ struct SwitchPriorResidue {
   }
   static pgo::CostFunction* Create(double lambda) { return new pgo::CostFunction{lambda, 0.0, 0.0, pgo::CostFunction::SWITCH_PRIOR}; }
   double lambda;
+};
+
+// An absolute pose prior (g2o's EDGE_PRIOR_SE2; include/pgo.h, "pose priors"): pose P is at (x, y, theta) with the symmetric
+// positive semi-definite information I11 I12 I13 I22 I23 I33.  operator() gives the PLAIN residual d = (P - mean) with the
+// heading wrapped to [-pi, pi] by the IEEE remainder; the block's cost is 1/2 rho(d' I d).
+struct PosePriorResidue {
+  PosePriorResidue(double x_, double y_, double theta_) : x(x_), y(y_), theta(theta_) {}
+  bool operator()(const double* const P, double* e) const {
+    e[0] = P[0] - x;
+    e[1] = P[1] - y;
+    e[2] = std::remainder(P[2] - theta, 6.283185307179586476925286766559);
+    return true;
+  }
+  static pgo::CostFunction* Create(double x, double y, double theta, const double info6[6]) {
+    return new pgo::CostFunction{x, y, theta, pgo::CostFunction::POSE_PRIOR, {info6[0], info6[1], info6[2], info6[3], info6[4], info6[5]}};
+  }
+  double x, y, theta;
 };
 
 #endif

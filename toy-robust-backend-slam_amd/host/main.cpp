@@ -3,6 +3,7 @@
 //            [--loss NAME[:A]] [--loop-loss NAME[:A]] [--score FILE [--align]] [--init-stride S [--init-info]] [--gnc CBAR [--gnc-inner K]]
 //            [--loop-support MIN[:WINDOW[:TOL_XY[:TOL_TH]]]]
 //            [--chordal-init [ROUNDS[:REJECT_XY[:REJECT_TH]]]] [--mixture-null PI:SCALE[:INNER]]
+//            [--priors FILE [--prior-loss NAME[:A]]]
 // METHOD 0 = baseline, 1 = DCS, 2 = switchable constraints run on the MI355X backend; 3/4 are outside it (exit code 3).
 // Reads DIR/DATASET.g2o (default ../data, as the reference), writes init_/opt_ nodes+edges text files that
 // drawer/plot_results.py consumes (default ../save; unlike the reference the directory is created).
@@ -15,6 +16,7 @@
 #include <fstream>
 #include <iostream>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "ceres_error.h"
@@ -65,11 +67,14 @@ int main(int argc, char* argv[]) {
               << "       iterations, default 2, until the selection stands.  The loop blocks run under the Trivial loss unless --loop-loss is\n"
               << "       given: the null component wins where 1/2 rho(s) exceeds its constant -log PI - 1.5 log SCALE, and under the default\n"
               << "       huber:0.01 rho grows like 0.02 |e|, so that it would win only kilometres out.  Writes weights.txt)\n"
+              << "       [--priors FILE [--prior-loss NAME[:A]]]  (METHOD 0 and 1: absolute pose priors, one g2o-format line each,\n"
+              << "       EDGE_PRIOR_SE2 id x y th I11 I12 I13 I22 I23 I33 -- id a vertex id of the dataset, the information positive SEMI-definite\n"
+              << "       (a 0 0 a 0 0 is a position-only fix); --prior-loss: one loss for all of them, default trivial)\n"
               << "METHOD: 0=baseline, 1=DCS, 2=Switchable (3=Layer, 4=Simple Layer MCTS: not in this backend)\n"
               << "Example: " << argv[0] << " INTEL 50 1\n";
     return -1;
   }
-  std::string base = "../data", save = "../save", loss_spec = "huber:0.01", loop_spec, score_file;
+  std::string base = "../data", save = "../save", loss_spec = "huber:0.01", loop_spec, score_file, priors_file, prior_loss_spec = "trivial";
   long long seed = -1;
   int device = 0, precision = 0, score_align = 0, init_stride = 0, gnc_inner = 5;
   double gnc_cbar = 0.0;
@@ -118,6 +123,8 @@ int main(int argc, char* argv[]) {
     else if (!strcmp(argv[i], "--precision")) precision = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "--loss")) loss_spec = argv[i + 1];
     else if (!strcmp(argv[i], "--loop-loss")) loop_spec = argv[i + 1];
+    else if (!strcmp(argv[i], "--priors")) priors_file = argv[i + 1];
+    else if (!strcmp(argv[i], "--prior-loss")) prior_loss_spec = argv[i + 1];
     else if (!strcmp(argv[i], "--init-stride")) init_stride = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "--gnc")) { gnc_on = true; gnc_cbar = atof(argv[i + 1]); }
     else if (!strcmp(argv[i], "--gnc-inner")) gnc_inner = atoi(argv[i + 1]);
@@ -143,8 +150,9 @@ int main(int argc, char* argv[]) {
     }
     else { std::cerr << "unknown option " << argv[i] << "\n"; return -1; }
   }
-  std::unique_ptr<pgo::LossFunction> loss_function, loop_loss;
+  std::unique_ptr<pgo::LossFunction> loss_function, loop_loss, prior_loss;
   try {
+    prior_loss = make_loss(prior_loss_spec);
     loss_function = make_loss(loss_spec);
     if (!loop_spec.empty()) loop_loss = make_loss(loop_spec);
     else if (mixture_on) loop_loss = make_loss("trivial");   // (see --help: under huber:0.01 the null component would never win)
@@ -168,6 +176,10 @@ int main(int argc, char* argv[]) {
   }
   if (mixture_on && (method != 0 || gnc_on)) {
     std::cerr << "--mixture-null runs on METHOD 0 only (the selection takes the place of DCS / the switches), and not with --gnc\n";
+    return -1;
+  }
+  if (!priors_file.empty() && method == 2) {
+    std::cerr << "--priors: METHOD 0 and 1 only\n";
     return -1;
   }
   if (support_on && method == 2) {
@@ -208,6 +220,26 @@ int main(int argc, char* argv[]) {
         }
       }
     problem.SetParameterBlockConstant(g2o_manager.nNodes[0]->p);
+    if (!priors_file.empty()) {   // EDGE_PRIOR_SE2 id x y th I11 I12 I13 I22 I23 I33 (the g2o parser itself does not know the tag)
+      std::ifstream in(priors_file);
+      if (!in) throw std::runtime_error("cannot open " + priors_file);
+      std::string tag;
+      int id;
+      double z[3], w[6];
+      int n_priors = 0;
+      std::unordered_map<int, Node*> by_id;   // vertex id -> node, built once
+      for (Node* nd : g2o_manager.nNodes) by_id[nd->index] = nd;
+      while (in >> tag) {
+        if (tag != "EDGE_PRIOR_SE2" || !(in >> id >> z[0] >> z[1] >> z[2] >> w[0] >> w[1] >> w[2] >> w[3] >> w[4] >> w[5]))
+          throw std::runtime_error(priors_file + ": expected EDGE_PRIOR_SE2 id x y th I11 I12 I13 I22 I23 I33");
+        const auto found = by_id.find(id);
+        Node* at = found == by_id.end() ? nullptr : found->second;
+        if (!at) throw std::runtime_error(priors_file + ": vertex " + std::to_string(id) + " is not in the dataset");
+        problem.AddResidualBlock(PosePriorResidue::Create(z[0], z[1], z[2], w), prior_loss.get(), at->p);
+        ++n_priors;
+      }
+      std::cout << "total pose priors : " << n_priors << std::endl;
+    }
 
     pgo::Solver::Options options;
     options.minimizer_progress_to_stdout = true;

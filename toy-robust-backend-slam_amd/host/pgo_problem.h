@@ -78,12 +78,28 @@ class Problem {
     any_sc_ = true;
     class_.push_back(cls);
   }
-  // SwitchPriorResidue: (S), no loss  (reference main.cpp:124-125,144-145)
-  void AddResidualBlock(CostFunction* cost, LossFunction* loss, double* s) {
+  // One parameter block.  SwitchPriorResidue: (S), no loss  (reference main.cpp:124-125,144-145).  PosePriorResidue: (P), an
+  // absolute prior on the pose block P (include/pgo.h, "pose priors") -- at most one per block, and ONE loss (NULL = Trivial) for
+  // all pose priors of a problem; they are no residual blocks of NumResidualBlocks() and carry no residual block weight.
+  void AddResidualBlock(CostFunction* cost, LossFunction* loss, double* p) {
     std::unique_ptr<CostFunction> own(cost);
-    if (cost->kind != CostFunction::SWITCH_PRIOR || loss) throw std::invalid_argument("one parameter block: SwitchPriorResidue without loss only");
-    prior_lambda_[s] = cost->dx;
+    if (cost->kind == CostFunction::POSE_PRIOR) {
+      const pgo_loss l = loss ? loss->loss() : TrivialLoss().loss();
+      if (!prior_pose_.empty() && (l.type != prior_loss_.type || l.a != prior_loss_.a))
+        throw std::invalid_argument("this backend takes one loss function for all pose priors of a problem");
+      const int32_t k = block(p);
+      for (int32_t q : prior_pose_)
+        if (q == k) throw std::invalid_argument("this backend takes at most one pose prior per parameter block");
+      prior_loss_ = l;
+      prior_pose_.push_back(k);
+      prior_mean_.insert(prior_mean_.end(), {cost->dx, cost->dy, cost->dtheta});
+      prior_info_.insert(prior_info_.end(), cost->info, cost->info + 6);
+      return;
+    }
+    if (cost->kind != CostFunction::SWITCH_PRIOR || loss) throw std::invalid_argument("one parameter block: SwitchPriorResidue without loss, or PosePriorResidue");
+    prior_lambda_[p] = cost->dx;
   }
+  int NumPosePriors() const { return (int)prior_pose_.size(); }
   // Any number of blocks may be made constant.  The first one is the handle's fixed pose (one block, called once: exactly
   // the path of a problem with a single anchor); the others, and the blocks that appear in no residual block, are applied
   // through pgo_set_active when the problem is solved.
@@ -143,6 +159,9 @@ class Problem {
   std::unordered_map<double*, double> prior_lambda_;  // switch -> lambda of its prior
   bool any_dcs_ = false, any_sc_ = false;
   std::vector<double> weights_;                    // per residual block, or empty (SetResidualBlockWeights)
+  std::vector<int32_t> prior_pose_;                // pose priors (PosePriorResidue): the block, the mean (x 3), the information (x 6)
+  std::vector<double> prior_mean_, prior_info_;
+  pgo_loss prior_loss_ = {PGO_LOSS_TRIVIAL, 0, 0.0};
 };
 
 namespace Solver {
@@ -317,6 +336,8 @@ struct SolverAccess {
       w.resize((size_t)E, 1.0);
       st = pgo_set_edge_weights(h, w.data());
     }
+    if (st == PGO_OK && !pr->prior_pose_.empty())   // (every solve goes through here: Solve, SolveGnc, SolveMixture carry the priors)
+      st = pgo_set_priors(h, (int32_t)pr->prior_pose_.size(), pr->prior_pose_.data(), pr->prior_mean_.data(), pr->prior_info_.data(), &pr->prior_loss_);
     if (st != PGO_OK) {
       const std::string msg = pgo_last_error();
       pgo_destroy(h);
@@ -524,7 +545,8 @@ struct SolverAccess {
     if (prs.empty()) return false;
     for (Problem* pr : prs)
       if (pr->any_sc_ || pr->any_dcs_ != prs[0]->any_dcs_ || !SameLosses(pr, prs[0]) || pr->fixed_ != prs[0]->fixed_ ||
-          pr->ptr_.empty() || !ConstantMask(pr).empty())   // (several constant blocks: ordinary handles, pgo_set_active)
+          pr->ptr_.empty() || !ConstantMask(pr).empty() ||   // (several constant blocks: ordinary handles, pgo_set_active)
+          !pr->prior_pose_.empty())                          // (pose priors: there is no batch entry point for them)
         return false;
     return true;
   }
