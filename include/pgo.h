@@ -513,6 +513,50 @@ int  pgo_pose_covariance(pgo_t* h, int32_t n, const int32_t* poses /* caller's n
                          const pgo_covariance_options* opt_or_null, double* out,
                          pgo_covariance_report* report_or_null);                           /* [gpu]  */
 
+/* ---------------------------------------------------- posterior sampling
+ * How uncertain is EVERY pose?  pgo_pose_covariance costs three solves per pose; this call draws samples of the Gaussian
+ * posterior N(0, (J'J)^-1) of the increments around the handle's CURRENT poses by perturb-and-MAP, one solve per sample:
+ *   eps ~ N(0, I) in residual space (one triple per edge, one per pose prior),   (J'J) delta = J' eps   (+ R eps_p, R R' = rho' Lambda)
+ * so that cov(delta) = H^-1 J'J H^-1 = H^-1 exactly.  J is what pgo_pose_covariance uses: K1's records as the last
+ * linearisation left them (loss correctors, DCS, the edge weight plane, the mixtures' selected means, the active mask), on the
+ * same undamped Jacobi-scaled system, through the same session: solver = 0 multi-column PCG with per-column stopping on the TRUE
+ * residual, solver = 1 the handle's direct solve with refinement (768 columns a pass at most, never a fallback).
+ *   delta_out   n_samples x N x 3, the caller's numbering: increments (x, y, theta) of sample first_sample + s; zero on constant poses
+ *   cov_out     N x 9: (1 / n_samples) sum_s delta_s delta_s' per pose, row-major symmetric 3x3 blocks.  It is the second moment
+ *               about the KNOWN mean 0 (divisor n_samples, not n_samples - 1); the whitened block is Wishart(n_samples, I) /
+ *               n_samples, so its relative error depends on n_samples only: E || L^-1 C L^-T - I ||_F^2 = 12 / n_samples.
+ * The noise is a pure function of (seed, stream, index, sample) -- Philox4x32-10 with key = seed and counter = (index, word,
+ * sample, stream), Box-Muller on 53-bit uniforms (csrc/sample.h; pgo_sample_noise_eval evaluates it on the host): stream 0 =
+ * edges, index = the edge's index in the CALLER's edge order; stream 1 = priors, index = the prior's position in the order
+ * given to pgo_set_priors; sample = the global sample number.  So an edge's noise does not depend on the internal ordering, the
+ * pass width or the other samples of a call, duplicate edges get independent noise, and draws compose: two calls over
+ * [0, k) and [k, n) return bitwise the deltas of one call over [0, n).  Samples are summed in global sample order: cov_out is
+ * bitwise independent of the pass width and of whether delta_out is asked for.  The LM state is left as it was.
+ * report.columns = n_samples; the other fields as pgo_pose_covariance.
+ * Errors: PGO_ERR_UNSUPPORTED as pgo_pose_covariance (world > 1, batched handles, info_weighting = 1, no constant pose, solver = 1
+ * on a handle that is not on the direct solve) and for METHOD 2 (its pose marginal needs noise on the switch rows: left out);
+ * PGO_ERR_INVALID_ARG for n_samples < 1, samples_per_pass outside 1..48, first_sample < 0, both outputs NULL, every pose constant;
+ * PGO_ERR_NUMERIC as pgo_pose_covariance (a non-finite pose is named, a pose without edges, a stalled residual: "sample k"). */
+typedef struct pgo_sample_options {
+  double   rtol;             /* 1e-10, as pgo_covariance_options: TRUE residual per sample                         */
+  int32_t  max_iters;        /* 20000                                                                              */
+  int32_t  samples_per_pass; /* 24 (1 .. 48); solver = 1: the library's choice, not read                           */
+  int32_t  solver;           /* 0 PCG, 1 the handle's direct solve (never a fallback)                              */
+  int32_t  first_sample;     /* 0: this call draws samples first_sample .. first_sample + n - 1 of the seed's stream */
+  uint64_t seed;
+} pgo_sample_options;
+void pgo_sample_options_default(pgo_sample_options* o);                                                     /* [host] */
+/* the standard normal triple of (seed, stream 0 | 1, index in 0 .. 2^32 - 1, sample >= 0); else PGO_ERR_INVALID_ARG */
+int  pgo_sample_noise_eval(uint64_t seed, int32_t stream, int64_t index, int32_t sample, double z[3]);      /* [host] */
+int  pgo_posterior_sample(pgo_t* h, int32_t n_samples, const pgo_sample_options* opt_or_null,
+                          double* delta_out_or_null /* n x N x 3, caller's numbering, (x, y, theta) increments */,
+                          double* cov_out_or_null   /* N x 9 */, pgo_covariance_report* report_or_null);   /* [gpu]  */
+/* test hook: the noise and the right-hand side of ONE sample.  eps_out (or NULL): E x 3 in the caller's edge order (inactive
+ * edges included: their noise exists and is not used); b_out (or NULL): N x 3 in the caller's numbering, UNSCALED: J' eps
+ * (+ R eps_p) on the free poses, 0 on the constant ones.  Refusals as pgo_posterior_sample.                            */
+int  pgo_debug_sample_rhs(pgo_t* h, uint64_t seed, int32_t sample, double* eps_out /* E x 3, caller's edge order */,
+                          double* b_out /* N x 3, caller's numbering, UNSCALED: J' eps (+ R eps_p) */);     /* [gpu]  */
+
 /* ------------------------------------------------------------- edge gate
  * Is a candidate loop edge consistent with the current estimate, and what would it add?  For candidate k = (a, b, meas, Omega)
  * in the caller's pose numbering -- it need NOT be an edge of the graph -- at the handle's CURRENT poses:
@@ -1342,7 +1386,8 @@ int pgo_debug_normal_eq(pgo_t* h, double* g_or_null, double* hdiag_or_null);    
  *   "cov_poses_per_pass" 1..16 = overrides pgo_covariance_options.poses_per_pass of every pgo_pose_covariance / pgo_edge_gate call (read per call;
  *                        the results agree with every value up to the solver tolerance)
  *   "cov_direct_cols"    a multiple of 3 in 3..768 = columns per pass of pgo_pose_covariance / pgo_edge_gate with solver = 1 (read per
- *                        call; any other value >= 0: PGO_ERR_INVALID_ARG from that call; the results are bitwise the same for every width)
+ *                        call; any other value >= 0: PGO_ERR_INVALID_ARG from that call; the results are bitwise the same for every width);
+ *                        pgo_posterior_sample with solver = 1 draws that many samples per pass
  *   "gate_joint_shape"   0 = pgo_edge_gate_joint runs its elimination as ONE launch of one workgroup instead of one launch per
  *                        candidate with a grid of workgroups over the trailing rows (read per call; the results are bitwise the same)
  *   "score_grid"         n > 0 = pgo_trajectory_error launches n workgroups over its chunks instead of one per chunk (read per

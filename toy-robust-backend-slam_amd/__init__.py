@@ -31,7 +31,7 @@ __all__ = ["PgoError", "Options", "Summary", "IterRecord", "ReadG2O", "Graph", "
            "loop_support_plan", "LoopSupportOptions", "LoopSupportRecord", "LoopSupportStats", "LOOP_SUPPORT_MAX_WINDOW",
            "chordal_plan", "ChordalOptions", "ChordalSolve", "ChordalSummary", "CHORDAL_MAX_ROUNDS",
            "mixture_eval", "mixture_plan", "MixStats", "MixtureOptions", "MixtureRound", "MixtureSummary", "MIX_MAX_COMPONENTS",
-           "prior_eval"]
+           "prior_eval", "SampleOptions", "sample_noise_eval"]
 
 EDGE_ODOMETRY, EDGE_CLOSURE, EDGE_BOGUS = 0, 1, 2
 TERMINATION = {1: "CONVERGENCE_FTOL", 2: "CONVERGENCE_GTOL", 3: "CONVERGENCE_PTOL", 4: "NO_CONVERGENCE",
@@ -69,6 +69,7 @@ EXPORTS = [
     "pgo_mixture_options_default", "pgo_mixture_eval", "pgo_mixture_plan", "pgo_set_mixtures", "pgo_set_mixture_null",
     "pgo_mixture_select", "pgo_get_mixture_selection", "pgo_mixture_solve",
     "pgo_set_priors", "pgo_num_priors", "pgo_get_prior_residuals", "pgo_prior_eval",
+    "pgo_sample_options_default", "pgo_sample_noise_eval", "pgo_posterior_sample", "pgo_debug_sample_rhs",
 ]
 MIX_MAX_COMPONENTS = 8   # PGO_MIX_MAX_COMPONENTS
 CHORDAL_MAX_ROUNDS = 8   # PGO_CHORDAL_MAX_ROUNDS
@@ -170,6 +171,20 @@ class CovarianceOptions(C.Structure):
         for k, v in kw.items():
             if k not in dict(self._fields_):
                 raise TypeError("unknown covariance option " + k)
+            setattr(self, k, v)
+
+
+class SampleOptions(C.Structure):
+    """mirror of pgo_sample_options (defaults: pgo_sample_options_default)"""
+    _fields_ = [("rtol", C.c_double), ("max_iters", C.c_int32), ("samples_per_pass", C.c_int32), ("solver", C.c_int32),
+                ("first_sample", C.c_int32), ("seed", C.c_uint64)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().pgo_sample_options_default(C.byref(self))
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError("unknown sample option " + k)
             setattr(self, k, v)
 
 
@@ -547,6 +562,11 @@ def lib():
     L.pgo_covariance_options_default.argtypes = [C.POINTER(CovarianceOptions)]
     L.pgo_covariance_options_default.restype = None
     L.pgo_pose_covariance.argtypes = [vp, C.c_int32, ip, C.POINTER(CovarianceOptions), dp, C.POINTER(CovarianceReport)]
+    L.pgo_sample_options_default.argtypes = [C.POINTER(SampleOptions)]
+    L.pgo_sample_options_default.restype = None
+    L.pgo_sample_noise_eval.argtypes = [C.c_uint64, C.c_int32, C.c_int64, C.c_int32, dp]
+    L.pgo_posterior_sample.argtypes = [vp, C.c_int32, C.POINTER(SampleOptions), dp, dp, C.POINTER(CovarianceReport)]
+    L.pgo_debug_sample_rhs.argtypes = [vp, C.c_uint64, C.c_int32, dp, dp]
     L.pgo_loss_evaluate.argtypes = [C.POINTER(Loss), C.c_double, dp]
     L.pgo_set_losses.argtypes = [vp, C.c_int32, C.POINTER(Loss), bp]
     L.pgo_batch_set_losses.argtypes = [vp, C.c_int32, C.POINTER(Loss), bp]
@@ -1105,6 +1125,13 @@ def _window_solve(fn, h, windows, with_problem, max_iters, commit, want_records)
     return poses, results, [[recs[w * rows + k].as_dict() for k in range(results[w].n_records)] for w in range(n)]
 
 
+def sample_noise_eval(seed, stream, index, sample):
+    """pgo_sample_noise_eval (host only): the standard normal triple of (seed, stream 0 = edges | 1 = priors, index, sample)"""
+    z = np.zeros(3)
+    _check(lib().pgo_sample_noise_eval(int(seed), int(stream), int(index), int(sample), _dp(z)))
+    return z
+
+
 def gate_evaluate(r, P, info=None):
     """pgo_gate_evaluate (host only), the 3x3 algebra of Solver.gate: (chi2, chi2_marginal, info_gain) from the residual r,
     the covariance P (3x3) of the predicted residual and the information (I11 I12 I13 I22 I23 I33), None = the identity"""
@@ -1640,6 +1667,25 @@ class Solver:
         rep = CovarianceReport()
         _check(lib().pgo_pose_covariance(self._h, n, _ip(idx), C.byref(o), _dp(out), C.byref(rep)))
         return out, rep.as_dict()
+
+    def sample(self, n, seed=0, first=0, want_deltas=True, want_cov=True, **opts):
+        """pgo_posterior_sample: n draws delta ~ N(0, (J'J)^-1) around the current poses (samples first .. first + n - 1 of the
+        seed's stream) and their second moment per pose.  Returns (deltas (n, N, 3) or None, cov (N, 3, 3) or None, report
+        dict); opts: the other SampleOptions fields (rtol, max_iters, samples_per_pass, solver)."""
+        o = SampleOptions(seed=int(seed), first_sample=int(first), **opts)
+        n = int(n)
+        deltas = np.zeros((max(n, 0), self.n_poses, 3)) if want_deltas else None
+        cov = np.zeros((self.n_poses, 3, 3)) if want_cov else None
+        rep = CovarianceReport()
+        _check(lib().pgo_posterior_sample(self._h, n, C.byref(o), _dp(deltas), _dp(cov), C.byref(rep)))
+        return deltas, cov, rep.as_dict()
+
+    def debug_sample_rhs(self, seed, sample):
+        """pgo_debug_sample_rhs: (eps (E, 3) in the caller's edge order, b (N, 3) = J' eps (+ R eps_p), unscaled, 0 on the
+        constant poses) of one sample"""
+        eps, b = np.zeros((self.n_edges, 3)), np.zeros((self.n_poses, 3))
+        _check(lib().pgo_debug_sample_rhs(self._h, int(seed), int(sample), _dp(eps), _dp(b)))
+        return eps, b
 
     @staticmethod
     def _gate_args(ia, ib, meas, info):

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libpgo.so")
 SOURCES = ["host_graph.cpp", "structure.cpp", "comm.cpp", "knobs.cpp", "solver_create.hip", "solver_lm.hip", "solver_pcg.hip", "solver_direct.hip",
            "solver_batch.hip", "solver_abi.hip", "solver_launch.hip", "solver_covariance.hip", "solver_window.hip", "solver_score.hip", "solver_coarsen.hip", "solver_gnc.hip", "solver_support.hip", "solver_chordal.hip", "solver_mixture.hip", "solver_prior.hip"]
-HEADERS = ["pgo_internal.h", "constants.h", "plan.h", "scratch.h", "comm.h", "loss.h", "gate.h", "edge_model.h", "trust_region.h", "kernels.hip.h", "solo.hip.h", "direct.hip.h", "coarse.hip.h", "covariance.hip.h", "window.hip.h", "traj_error.h", "score.hip.h", "coarsen.h", "coarsen.hip.h", "gnc.h", "gnc.hip.h", "loop_support.h", "loop_support.hip.h", "chordal.h", "chordal.hip.h", "mixture.h", "mixture.hip.h", "prior.h", "prior.hip.h", "solver_handle.hip.h",
+HEADERS = ["pgo_internal.h", "constants.h", "plan.h", "scratch.h", "comm.h", "loss.h", "gate.h", "edge_model.h", "trust_region.h", "kernels.hip.h", "solo.hip.h", "direct.hip.h", "coarse.hip.h", "covariance.hip.h", "sample.h", "sample.hip.h", "window.hip.h", "traj_error.h", "score.hip.h", "coarsen.h", "coarsen.hip.h", "gnc.h", "gnc.hip.h", "loop_support.h", "loop_support.hip.h", "chordal.h", "chordal.hip.h", "mixture.h", "mixture.hip.h", "prior.h", "prior.hip.h", "solver_handle.hip.h",
            os.path.join(ROOT, "include", "pgo.h")]
 
 

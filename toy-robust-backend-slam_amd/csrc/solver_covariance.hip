@@ -7,10 +7,13 @@
 // every pass) and the sequential elimination on it (k_gate_joint_step, one launch per candidate).
 // With pgo_covariance_options.solver = 1 the columns go through the handle's direct solve instead (Session::pass_direct):
 // its factorisation once per call at D'D = 0, up to 768 columns per pass, iterative refinement against the same A.
+// pgo_posterior_sample is the same session on dense right-hand sides b = S J' eps (sample.hip.h): one column per draw
+// delta ~ N(0, (J'J)^-1), and the second moment of the draws per pose.
 #include <functional>
 
 #include "solver_handle.hip.h"
 #include "covariance.hip.h"
+#include "sample.hip.h"
 
 namespace {
 
@@ -104,11 +107,13 @@ int setup_system(pgo_handle* h, bool with_preconditioner) {
 }
 
 // the right-hand sides of one pass: unit vectors S e_rows[c] (pgo_pose_covariance), or with rec != nullptr the sparse
-// columns S J' of the candidates cand[0 .. m / 3) (pgo_edge_gate)
+// columns S J' of the candidates cand[0 .. m / 3) (pgo_edge_gate), or with panel != nullptr the dense columns of a panel
+// of their own, column c at panel + c * ld (pgo_posterior_sample)
 struct PassRhs {
   const int32_t* rows = nullptr;
   const dev::GateRec* rec = nullptr;
   const int32_t* cand = nullptr;
+  const double* panel = nullptr;
 };
 
 // One call on the undamped system: the checks and the set-up both entry points share, the PCG panels, and the solve of a pass.
@@ -260,21 +265,28 @@ struct Session {
 
   int launch_rhs(int m, const PassRhs& B) {
     double* p0 = direct ? AP : P;   // (solver = 1 has no search directions: the kernel's zeros go into the product's panel)
-    if (B.rec)
+    if (B.panel)
+      hipLaunchKernelGGL(dev::k_cov_rhs<dev::RhsDense>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, dev::RhsDense{B.panel, ld}, X, R, p0, part_a);
+    else if (B.rec)
       hipLaunchKernelGGL(dev::k_cov_rhs<dev::RhsSparse>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, dev::RhsSparse{B.rec, B.cand, h->scale}, X, R, p0, part_a);
     else
       hipLaunchKernelGGL(dev::k_cov_rhs<dev::RhsUnit>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, dev::RhsUnit{B.rows, h->scale}, X, R, p0, part_a);
     return h->check_launch("k_cov_rhs");
   }
   int launch_resid(int m, const PassRhs& B) {
-    if (B.rec)
+    if (B.panel)
+      hipLaunchKernelGGL(dev::k_cov_resid<dev::RhsDense>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, dev::RhsDense{B.panel, ld}, (const double*)AP, part_b);
+    else if (B.rec)
       hipLaunchKernelGGL(dev::k_cov_resid<dev::RhsSparse>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, dev::RhsSparse{B.rec, B.cand, h->scale}, (const double*)AP, part_b);
     else
       hipLaunchKernelGGL(dev::k_cov_resid<dev::RhsUnit>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, dev::RhsUnit{B.rows, h->scale}, (const double*)AP, part_b);
     return h->check_launch("k_cov_resid");
   }
   void launch_replace(int m, const PassRhs& B) {
-    if (B.rec)
+    if (B.panel)
+      hipLaunchKernelGGL(dev::k_cov_replace<dev::RhsDense>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, dev::RhsDense{B.panel, ld}, (const double*)AP, R,
+                         (const uint8_t*)rmask);
+    else if (B.rec)
       hipLaunchKernelGGL(dev::k_cov_replace<dev::RhsSparse>, dim3(g, m), dim3(dev::WG), 0, h->stream, n3, ld, dev::RhsSparse{B.rec, B.cand, h->scale}, (const double*)AP, R,
                          (const uint8_t*)rmask);
     else
@@ -800,6 +812,193 @@ int pgo_edge_gate_joint(pgo_t* h, int32_t n, const int32_t* ia, const int32_t* i
   PGOC(joint_options(fn, n, force_or_null, jopt_or_null, &jc.o));
   memset(sum, 0, sizeof *sum);
   return gate_call("pgo_edge_gate_joint", h, n, ia, ib, meas_xyt, info6_or_null, opt_or_null, out, report, &jc);
+}
+
+}  // extern "C"
+
+// ====================================================================== posterior sampling
+namespace {
+
+// What pgo_posterior_sample and pgo_debug_sample_rhs share: the refusals, the open session, the tables of the right-hand side.
+struct SampleCall {
+  Session S;
+  pgo_handle* h;
+  int32_t* d_orig = nullptr;   // local edge -> the caller's edge
+  int32_t* d_inv = nullptr;    // internal row -> the caller's pose (nullptr: the identity)
+  SampleCall(pgo_handle* hh, const char* name) : S(hh, name), h(hh) {}
+
+  int open(const pgo_covariance_options& o) {
+    if (h->has_sw || h->opt.method == 2)   // (its pose marginal needs noise on the switch rows too)
+      return fail(PGO_ERR_UNSUPPORTED, S.fn + ": METHOD 2 is not supported (METHOD 0 and 1 only)");
+    PGOC(S.check(&o));
+    PGOC(S.open());
+    const int64_t EL = h->S.n_edges_local;
+    PGOC(S.buf.alloc(&d_orig, EL));
+    if (EL > 0) HIPC(hipMemcpyAsync(d_orig, h->S.orig_edge.data(), (size_t)EL * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    if (!h->perm.empty()) {
+      std::vector<int32_t> inv((size_t)S.N);
+      for (int64_t i = 0; i < S.N; ++i) inv[(size_t)h->perm[i]] = (int32_t)i;
+      PGOC(S.buf.alloc(&d_inv, S.N));
+      HIPC(hipMemcpyAsync(d_inv, inv.data(), inv.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+      PGOC(h->sync());   // (`inv` dies with this scope)
+    }
+    return h->sync();
+  }
+
+  // b (m columns at stride ld, samples sample0 ..) = S J' eps + S R eps_p;  unit: without the scales (0 on constant poses stays)
+  int rhs(int m, int32_t sample0, uint64_t seed, int unit, double* b) {
+    dev::SampleRhsArgs A;
+    A.jr = h->jr;
+    A.inc_ptr = h->inc_ptr;
+    A.inc_edge = h->inc_edge;
+    A.orig = d_orig;
+    A.scale = h->scale;
+    A.n = (int32_t)S.N;
+    A.m = m;
+    A.sample0 = sample0;
+    A.seed = seed;
+    A.ld = S.ld;
+    A.b = b;
+    const dim3 grid((unsigned)((S.N + dev::WG - 1) / dev::WG), m);
+    if (unit) hipLaunchKernelGGL(dev::k_sample_rhs<true>, grid, dim3(dev::WG), 0, h->stream, A);
+    else hipLaunchKernelGGL(dev::k_sample_rhs<false>, grid, dim3(dev::WG), 0, h->stream, A);
+    PGOC(h->check_launch("k_sample_rhs"));
+    if (h->pri_n > 0) {
+      dev::SamplePriorArgs Q;
+      Q.row = h->pri_row_s.in(h->pri_tab.p);
+      Q.order = h->pri_order_s.in(h->pri_tab.p);
+      Q.rec = h->pri_rec_s.in(h->pri_tab.p);
+      Q.scale = h->scale;
+      Q.n = h->pri_n;
+      Q.m = m;
+      Q.sample0 = sample0;
+      Q.unit = unit;
+      Q.seed = seed;
+      Q.ld = S.ld;
+      Q.b = b;
+      hipLaunchKernelGGL(dev::k_sample_prior<>, dim3(h->prior_grid(), m), dim3(dev::WG), 0, h->stream, Q);
+      PGOC(h->check_launch("k_sample_prior"));
+    }
+    return PGO_OK;
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+void pgo_sample_options_default(pgo_sample_options* o) {
+  if (!o) return;
+  memset(o, 0, sizeof *o);
+  o->rtol = 1e-10;
+  o->max_iters = 20000;
+  o->samples_per_pass = 24;
+  o->solver = 0;
+  o->first_sample = 0;
+  o->seed = 0;
+}
+
+int pgo_sample_noise_eval(uint64_t seed, int32_t stream, int64_t index, int32_t sample, double z[3]) {
+  if (!z) return fail(PGO_ERR_INVALID_ARG, "pgo_sample_noise_eval: null");
+  if ((stream != 0 && stream != 1) || index < 0 || index > (int64_t)UINT32_MAX || sample < 0)
+    return fail(PGO_ERR_INVALID_ARG, "pgo_sample_noise_eval: stream is 0 (edges) or 1 (priors), 0 <= index < 2^32, sample >= 0");
+  pgo::sample_triple(seed, (uint32_t)stream, (uint32_t)index, (uint32_t)sample, z);
+  return PGO_OK;
+}
+
+int pgo_posterior_sample(pgo_t* h, int32_t n_samples, const pgo_sample_options* opt_or_null, double* delta_out, double* cov_out,
+                         pgo_covariance_report* report) {
+  const double t0 = wall_s();
+  const std::string fn = "pgo_posterior_sample";
+  if (!h) return fail(PGO_ERR_INVALID_ARG, fn + ": null handle");
+  pgo_sample_options so;
+  if (opt_or_null) so = *opt_or_null;
+  else pgo_sample_options_default(&so);
+  if (n_samples < 1) return fail(PGO_ERR_INVALID_ARG, fn + ": n_samples >= 1 required");
+  if (!delta_out && !cov_out) return fail(PGO_ERR_INVALID_ARG, fn + ": delta_out and cov_out are both null");
+  if (so.solver == 0 && (so.samples_per_pass < 1 || so.samples_per_pass > dev::COV_MAX_COLS))
+    return fail(PGO_ERR_INVALID_ARG, fn + ": samples_per_pass in 1..48 required");
+  if (so.first_sample < 0 || (int64_t)so.first_sample + n_samples > (int64_t)INT32_MAX)
+    return fail(PGO_ERR_INVALID_ARG, fn + ": first_sample >= 0 and first_sample + n_samples < 2^31 required");
+  pgo_covariance_options co;
+  pgo_covariance_options_default(&co);
+  co.rtol = so.rtol;
+  co.max_iters = so.max_iters;
+  co.solver = so.solver;
+  SampleCall C(h, "pgo_posterior_sample");
+  Session& S = C.S;
+  if (report) memset(report, 0, sizeof *report);
+  PGOC(C.open(co));
+  const int64_t N = S.N, n3 = S.n3, ld = S.ld;
+  {   // every pose constant: b is identically zero
+    std::vector<double> sc((size_t)n3);
+    HIPC(hipMemcpyAsync(sc.data(), h->scale, sc.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PGOC(h->sync());
+    if (std::all_of(sc.begin(), sc.end(), [](double v) { return v == 0.0; }))
+      return fail(PGO_ERR_INVALID_ARG, fn + ": every pose is constant (the right-hand side of a sample is zero)");
+  }
+  // samples per pass.  solver = 1: the library's choice, as the columns of pgo_pose_covariance
+  const int per = S.direct ? 3 * S.per_pass() : so.samples_per_pass;
+  const int mcap = (int)std::min<int64_t>(per, n_samples);
+  PGOC(S.alloc(mcap));
+  // b in a panel of its own: the true-residual and replacement steps read it again; after a pass it stages the deltas
+  double *Bp, *acc, *d_cov = nullptr;
+  PGOC(S.buf.alloc(&Bp, (int64_t)mcap * ld));
+  PGOC(S.buf.alloc(&acc, 6 * N));
+  if (cov_out) PGOC(S.buf.alloc(&d_cov, 9 * N));
+  HIPC(hipMemsetAsync(acc, 0, (size_t)(6 * N) * sizeof(double), h->stream));
+  for (int32_t s0 = 0; s0 < n_samples; s0 += per) {
+    const int m = (int)std::min<int32_t>(per, n_samples - s0);
+    const int32_t first = so.first_sample + s0;
+    PGOC(C.rhs(m, first, so.seed, 0, Bp));
+    PassRhs B;
+    B.panel = Bp;
+    PGOC(S.pass(m, B, [&](int c) { return "sample " + std::to_string(first + c); }));
+    hipLaunchKernelGGL(dev::k_sample_accum<>, dim3(S.gs), dim3(dev::WG), 0, h->stream, (int32_t)N, m, ld, (const double*)S.X, (const double*)h->scale,
+                       (const int32_t*)C.d_inv, acc, delta_out ? Bp : nullptr);
+    PGOC(h->check_launch("k_sample_accum"));
+    if (delta_out) {
+      HIPC(hipMemcpyAsync(delta_out + (int64_t)s0 * n3, Bp, (size_t)m * n3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      PGOC(h->sync());
+    }
+  }
+  if (cov_out) {
+    hipLaunchKernelGGL(dev::k_sample_finish<>, dim3(S.gs), dim3(dev::WG), 0, h->stream, (int32_t)N, (double)n_samples, (const double*)acc,
+                       (const int32_t*)C.d_inv, d_cov);
+    PGOC(h->check_launch("k_sample_finish"));
+    HIPC(hipMemcpyAsync(cov_out, d_cov, (size_t)(9 * N) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  }
+  PGOC(h->sync());
+  S.fill(report, n_samples, t0);
+  return PGO_OK;
+}
+
+int pgo_debug_sample_rhs(pgo_t* h, uint64_t seed, int32_t sample, double* eps_out, double* b_out) {
+  const std::string fn = "pgo_debug_sample_rhs";
+  if (!h) return fail(PGO_ERR_INVALID_ARG, fn + ": null handle");
+  if (sample < 0 || (!eps_out && !b_out)) return fail(PGO_ERR_INVALID_ARG, fn + ": sample >= 0 and an output required");
+  pgo_covariance_options co;
+  pgo_covariance_options_default(&co);
+  SampleCall C(h, "pgo_debug_sample_rhs");
+  Session& S = C.S;
+  PGOC(C.open(co));
+  const int64_t E = h->n_edges_total, EL = h->S.n_edges_local;
+  if (eps_out && E > 0) {
+    double* d_eps;
+    PGOC(S.buf.alloc(&d_eps, 3 * E));
+    hipLaunchKernelGGL(dev::k_sample_eps<>, dim3((unsigned)std::min<int64_t>((EL + dev::WG - 1) / dev::WG, 1024)), dim3(dev::WG), 0, h->stream, EL,
+                       (const int32_t*)C.d_orig, seed, sample, d_eps);
+    PGOC(h->check_launch("k_sample_eps"));
+    HIPC(hipMemcpyAsync(eps_out, d_eps, (size_t)(3 * E) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PGOC(h->sync());
+  }
+  if (b_out) {
+    double* b;
+    PGOC(S.buf.alloc(&b, S.ld));
+    PGOC(C.rhs(1, sample, seed, 1, b));
+    PGOC(h->download_pose_vector(b_out, b));
+  }
+  return PGO_OK;
 }
 
 }  // extern "C"

@@ -3,7 +3,7 @@
 //            [--loss NAME[:A]] [--loop-loss NAME[:A]] [--score FILE [--align]] [--init-stride S [--init-info]] [--gnc CBAR [--gnc-inner K]]
 //            [--loop-support MIN[:WINDOW[:TOL_XY[:TOL_TH]]]]
 //            [--chordal-init [ROUNDS[:REJECT_XY[:REJECT_TH]]]] [--mixture-null PI:SCALE[:INNER]]
-//            [--priors FILE [--prior-loss NAME[:A]]]
+//            [--priors FILE [--prior-loss NAME[:A]]] [--sample-cov S[:SEED]]
 // METHOD 0 = baseline, 1 = DCS, 2 = switchable constraints run on the MI355X backend; 3/4 are outside it (exit code 3).
 // Reads DIR/DATASET.g2o (default ../data, as the reference), writes init_/opt_ nodes+edges text files that
 // drawer/plot_results.py consumes (default ../save; unlike the reference the directory is created).
@@ -71,12 +71,15 @@ int main(int argc, char* argv[]) {
               << "       EDGE_PRIOR_SE2 id x y th I11 I12 I13 I22 I23 I33 -- id a vertex id of the dataset, the information positive SEMI-definite\n"
               << "       (a 0 0 a 0 0 is a position-only fix); --prior-loss: one loss for all of them, default trivial)\n"
               << "METHOD: 0=baseline, 1=DCS, 2=Switchable (3=Layer, 4=Simple Layer MCTS: not in this backend)\n"
+              << "       [--sample-cov S[:SEED]]  (METHOD 0 and 1: after the solve, S posterior samples (seed SEED, default 0) estimate every\n"
+              << "       pose's marginal covariance; writes cov_nodes.txt, one line <index> sxx sxy sxt syy syt stt per pose)\n"
               << "Example: " << argv[0] << " INTEL 50 1\n";
     return -1;
   }
   std::string base = "../data", save = "../save", loss_spec = "huber:0.01", loop_spec, score_file, priors_file, prior_loss_spec = "trivial";
   long long seed = -1;
-  int device = 0, precision = 0, score_align = 0, init_stride = 0, gnc_inner = 5;
+  int device = 0, precision = 0, score_align = 0, init_stride = 0, gnc_inner = 5, sample_n = 0;
+  unsigned long long sample_seed = 0;
   double gnc_cbar = 0.0;
   bool gnc_on = false, support_on = false, init_info = false;
   pgo::LoopSupportOptions support;
@@ -126,6 +129,11 @@ int main(int argc, char* argv[]) {
     else if (!strcmp(argv[i], "--priors")) priors_file = argv[i + 1];
     else if (!strcmp(argv[i], "--prior-loss")) prior_loss_spec = argv[i + 1];
     else if (!strcmp(argv[i], "--init-stride")) init_stride = atoi(argv[i + 1]);
+    else if (!strcmp(argv[i], "--sample-cov")) {   // S[:SEED]
+      unsigned long long sd = 0;
+      if (sscanf(argv[i + 1], "%d:%llu", &sample_n, &sd) < 1 || sample_n < 1) { std::cerr << "--sample-cov S[:SEED]\n"; return -1; }
+      sample_seed = sd;
+    }
     else if (!strcmp(argv[i], "--gnc")) { gnc_on = true; gnc_cbar = atof(argv[i + 1]); }
     else if (!strcmp(argv[i], "--gnc-inner")) gnc_inner = atoi(argv[i + 1]);
     else if (!strcmp(argv[i], "--mixture-null")) {   // PI:SCALE[:INNER]
@@ -180,6 +188,10 @@ int main(int argc, char* argv[]) {
   }
   if (!priors_file.empty() && method == 2) {
     std::cerr << "--priors: METHOD 0 and 1 only\n";
+    return -1;
+  }
+  if (sample_n > 0 && method == 2) {
+    std::cerr << "--sample-cov: METHOD 0 and 1 only (the switch rows would need noise of their own)\n";
     return -1;
   }
   if (support_on && method == 2) {
@@ -335,6 +347,22 @@ int main(int argc, char* argv[]) {
     }
     std::cout << summary.FullReport() << std::endl;
 
+    if (sample_n > 0) {   // every pose's marginal covariance at the result, from sample_n posterior samples
+      pgo::SampleOptions so;
+      so.num_samples = sample_n;
+      so.seed = sample_seed;
+      pgo::SampleSummary ss;
+      pgo::SamplePosterior(options, so, &problem, &ss);
+      std::ofstream cf(save + "/cov_nodes.txt");
+      cf.precision(17);
+      for (size_t i = 0; i < g2o_manager.nNodes.size(); ++i) {
+        const double* c = &ss.covariance[9 * i];
+        cf << g2o_manager.nNodes[i]->index << " " << c[0] << " " << c[1] << " " << c[2] << " " << c[4] << " " << c[5] << " " << c[8] << "\n";
+      }
+      if (!cf) throw std::runtime_error("cannot write " + save + "/cov_nodes.txt");
+      std::cout << "sample-cov: " << sample_n << " samples in " << ss.report.passes << " passes, " << ss.report.pcg_iters_total
+                << " PCG iterations, max relative residual " << ss.report.max_rel_residual << ", " << ss.report.seconds << " s" << std::endl;
+    }
     g2o_manager.writePoseGraph_nodes(save + "/opt_nodes.txt", precision);
     g2o_manager.writePoseGraph_edges(save + "/opt_edges.txt");
     if (SC_ON) g2o_manager.writePoseGraph_switches(save + "/switches.txt", switch_priors, switch_variables);

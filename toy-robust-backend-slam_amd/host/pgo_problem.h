@@ -265,6 +265,23 @@ struct ChordalSummary {
   std::vector<double> residuals;           // per residual block: |position residual|, |heading residual|
 };
 
+// Posterior sampling (include/pgo.h, "posterior sampling"): draws delta ~ N(0, (J'J)^-1) around the problem's CURRENT parameter
+// blocks (call Solve first) and their second moment per parameter block.  The defaults are pgo_sample_options_default's.
+struct SampleOptions {
+  int num_samples = 256;
+  uint64_t seed = 0;
+  int first_sample = 0;
+  double rtol = 1e-10;
+  int max_iters = 20000, samples_per_pass = 24;
+  bool direct = false;          // true: the handle's direct solve (problems the direct solve covers only; never a fallback)
+  bool keep_samples = false;    // true: SampleSummary::samples holds the draws
+};
+struct SampleSummary {
+  pgo_covariance_report report{};
+  std::vector<double> covariance;   // per parameter block: row-major 3x3 in (x, y, theta); zero on constant blocks
+  std::vector<double> samples;      // keep_samples: num_samples x blocks x 3 increments
+};
+
 struct SolverAccess {
   static void check(int st) {
     if (st != PGO_OK) throw std::runtime_error(std::string("pgo: ") + pgo_strerror(st) + ": " + pgo_last_error());
@@ -435,6 +452,24 @@ struct SolverAccess {
     pgo_destroy(h);
     if (st != PGO_OK) throw std::runtime_error(std::string("pgo: ") + pgo_strerror(st) + ": " + msg);
     if (ls.apply) pr->weights_.swap(w);
+  }
+  static void SamplePosterior(const Solver::Options& opt, const SampleOptions& so, Problem* pr, SampleSummary* sum) {
+    const size_t N = pr->ptr_.size();
+    pgo_t* h = Prepare(opt, pr);
+    pgo_sample_options o;
+    pgo_sample_options_default(&o);
+    o.rtol = so.rtol;
+    o.max_iters = so.max_iters;
+    o.samples_per_pass = so.samples_per_pass;
+    o.solver = so.direct ? 1 : 0;
+    o.first_sample = so.first_sample;
+    o.seed = so.seed;
+    sum->covariance.assign(9 * N, 0.0);
+    sum->samples.assign(so.keep_samples ? (size_t)std::max(so.num_samples, 0) * 3 * N : 0, 0.0);
+    const int st = pgo_posterior_sample(h, so.num_samples, &o, so.keep_samples ? sum->samples.data() : nullptr, sum->covariance.data(), &sum->report);
+    const std::string msg = st != PGO_OK ? std::string(pgo_last_error()) : std::string();
+    pgo_destroy(h);
+    if (st != PGO_OK) throw std::runtime_error(std::string("pgo: ") + pgo_strerror(st) + ": " + msg);
   }
   // the parameter blocks moved, in place, to the chordal start; constant blocks are not moved
   static void ChordalInit(const Solver::Options& opt, const ChordalOptions& co, Problem* pr, ChordalSummary* sum) {
@@ -660,6 +695,11 @@ inline void LoopSupport(const Solver::Options& opt, const LoopSupportOptions& op
 // dropped get the weight 0.  Call Solve next.
 inline void ChordalInit(const Solver::Options& opt, const ChordalOptions& options, Problem* problem, ChordalSummary* summary = nullptr) {
   SolverAccess::ChordalInit(opt, options, problem, summary);
+}
+// All-pose marginal covariances by posterior sampling at the problem's current parameter blocks (after Solve: the estimate's);
+// METHOD 2 problems (switchable blocks) are refused
+inline void SamplePosterior(const Solver::Options& opt, const SampleOptions& options, Problem* problem, SampleSummary* summary) {
+  SolverAccess::SamplePosterior(opt, options, problem, summary);
 }
 // many independent problems at once; summaries->size() == problems.size() afterwards
 inline void SolveBatch(const Solver::Options& opt, const std::vector<Problem*>& problems, std::vector<Solver::Summary>* summaries,
